@@ -14,11 +14,19 @@ the timed region (BASELINE configs[2]).
     python bench.py --gpus 8 --workload sweep100 --steps 1      # BASELINE configs[2]: 100-view pose sweep
     python bench.py --gpus 8 --workload models21 --steps 1      # BASELINE configs[4]: 21 models, one stream each
 
-Prints ONE JSON line on rank 0.  Objects beside the contract fields:
+    python bench.py --full                            # also everything beside the headline (see below)
+    python bench.py --dump-outputs DIR                # also write the last timed step's outputs as DIR/<name>.npy
+
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step), `config`, `roofline` from the timed steps' own kernel times
+(with the offline `traffic` below), `range_status`, `ranks_seen` and `kernel_ms_per_rank`.  `--full` (view400, N=1) adds
+the rest of what is listed here, which takes runs of its own (--no-cpu-baseline / --no-extras trim it):
   roofline       -- dominant kernel nsr::k_render16p (k_render16 with the global-phases schedule): algorithmic FLOP per launch / HIP-event kernel time, against the
                     fp32-input MFMA peak (157.3 TFLOP/s, MI355X_MICROARCH.md) -- the datatype actually issued;
                     `traffic` comes from a rocprofv3 --pmc profile ONLY if that profile was collected from exactly
-                    the kernel sources in this tree (hash check), else null;
+                    the kernel sources in this tree (hash check), else null; --full measures it live when rocprofv3 is
+                    present, and samples power and clock over the timed steps;
+  strict_fp32    -- the same view on the strict-fp32 kernel when the main line runs another arithmetic;
   roofline_vjp   -- the same for nsr::k_render_vjp16p (render_path_grad's forward+input-gradient launch, config 4's render leg);
   cpu_baseline   -- the oracle (CPU restatement of the reference path, "port") timed on this host's cores on a bounded
                     sample (a smaller view of the same scene, ~15 s of CPU work), rank 0, N=1 only;
@@ -74,6 +82,24 @@ H2_ISSUED_FLOP_PER_POINT_BWD = 2 * 3 * ((64 + 256) * 128 + 256 * 256 + 2 * 256 *
 MLP_DTYPE = {"bf16x3": "bf16x3: fp32 operands as three bf16 pieces each, six piece products per fp32 product, fp32 accumulate",
              "f16x2": "f16x2: fp32 operands as two fp16 pieces each (power-of-two range management), three piece products per "
                       "fp32 product, fp32 accumulate"}
+DUMP_BYTES = 60 << 20                      # --dump-outputs: data bytes in all (64 MB with room for the .npy headers)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: arrays {name: tensor / array} -> dirname/<name>.npy, float64 for float64 / int64 inputs, float32 for
+    the rest.  Over DUMP_BYTES in all, every array is cut to the same fraction of its elements: a seeded sample of flat
+    indices (sorted; the same for the same shapes on every run), saved flat."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        host[name] = a.astype(np.float64 if a.dtype in (np.float64, np.int64) else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_BYTES:
+            k = a.size * DUMP_BYTES // total
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def forward_kernel_name(model):
@@ -901,6 +927,12 @@ def main():
                                                  if os.path.exists(f)), os.path.join(ROOT, "profiles", "r05", "pmc_k_render.json")))
     ap.add_argument("--mlp", choices=MLP_MODES, default=None,
                     help="layer-GEMM arithmetic of the forward kernel (default: the engine's, engine.DEFAULT_MLP / $NSR_MLP)")
+    ap.add_argument("--full", action="store_true",
+                    help="view400 at N=1: also power and clock over the timed steps, the live PMC traffic, strict_fp32, "
+                         "cpu_baseline + parity, roofline_vjp and extra_workloads (off: only the headline is measured)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all: a fixed seeded sample of larger outputs)")
     args = ap.parse_args()
 
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ
@@ -971,7 +1003,7 @@ def main():
             dummy = torch.zeros((args.steps, H * W, 3), device=cdev)
             dist.all_gather([torch.empty_like(dummy) for _ in range(world)], dummy)
             del dummy
-        sampler = PowerSampler(local) if rank == 0 else None      # (a reader thread / child process: nothing on the GPU)
+        sampler = PowerSampler(local) if (rank == 0 and args.full) else None      # (a reader thread / child process: nothing on the GPU)
         barrier()
         if sampler is not None:
             sampler.start()
@@ -988,12 +1020,15 @@ def main():
         barrier()
         dt = allmax(time.perf_counter() - t0)
         power = sampler.stop() if sampler is not None else None
+        if args.dump_outputs and rank == 0:                 # the last timed step's render (+ the gathered images, N > 1)
+            dump_outputs(args.dump_outputs, dict(out, **({"images_gathered": torch.stack(gathered, 0)} if dist is not None else {})))
         k_ms = float(np.mean(kernel_ms))
         ranks_seen, per_rank = rank_stats(k_ms)
         if rank == 0:
             rays = args.steps * H * W * world
             roof = forward_roofline(model, k_ms)
-            roof["power_and_clock_over_the_timed_steps"] = power
+            if args.full:
+                roof["power_and_clock_over_the_timed_steps"] = power
             if model.mlp == "bf16x3":
                 traffic, traffic_note = pmc_traffic(args.pmc_file, "bf16x3")
                 kernel_desc = "fused persistent kernel k_render_b3 (one workgroup per CU, 32 points per wave, layer GEMMs on bf16 MFMAs with three-way split fp32 operands)"
@@ -1007,7 +1042,7 @@ def main():
                 kernel_desc = "fp32, fused persistent kernel (x16: 2 workgroups per CU, %s schedule)" % model.schedule
             traffic_source = ("offline rocprofv3 --pmc passes of this kernel, used only if their recorded kernel-source hash "
                               "equals this tree's (else null)")
-            if world == 1 and not args.no_extras:            # measured in this run when rocprofv3 is on the box
+            if world == 1 and args.full and not args.no_extras:            # measured in this run when rocprofv3 is installed
                 live, live_note, clock = live_traffic(model.mlp)
                 if live is not None:
                     traffic, traffic_note, traffic_source = live, live_note, "live"
@@ -1019,11 +1054,12 @@ def main():
                                           "the profiler; profiled passes clock ~3 %% below un-profiled ones, MI355X_MICROARCH.md "
                                           "DVFS note); peak 2.4 GHz" % clock["kernel_ms_under_pmc"])
             roof.update({"traffic": traffic, "traffic_source": traffic_source, "traffic_note": traffic_note})
-            if world == 1 and model.mlp != "fp32":
+            if world == 1 and args.full and model.mlp != "fp32":
                 roof["strict_fp32"] = strict_fp32_line(sd_c, sd_f, local, poses[args.warmup])
                 # (r06: also at the top level of the line -- the figure a reader who takes BASELINE configs[1]'s "fp32" literally wants)
                 line["strict_fp32"] = roof["strict_fp32"]
-            line["power_and_clock_over_the_timed_steps"] = power
+            if args.full:
+                line["power_and_clock_over_the_timed_steps"] = power
             line["range_status"] = model.range_status()      # f16x2 range safety net: all zero = nothing left the fp16 range
             line.update({
                 "value": round(rays * SAMPLES_PER_RAY / dt / 1e6, 3), "ms_per_step": round(dt / args.steps * 1e3, 3),
@@ -1041,7 +1077,7 @@ def main():
                 "roofline": roof,
             })
             cpu_setting, cpu_sample = None, None
-            if world == 1 and not args.no_cpu_baseline:
+            if world == 1 and args.full and not args.no_cpu_baseline:
                 cpu, par, cpu_setting, cpu_sample = cpu_baseline_and_parity(model, sd_c, sd_f, poses[args.warmup],
                                                                             side=args.cpu_sample_side)
                 line["cpu_baseline"] = cpu
@@ -1049,7 +1085,7 @@ def main():
                 line["parity_summary"] = {"rays": par["census"]["rays"], "rays_above_tol": par["census"]["rays_above_tol"],
                                           "unattributed": par["census"]["unattributed"], "psnr_delta_db": par["psnr_delta_db"],
                                           "inds_exact": par["inds_exact_match_rate"], "passes": par["passes"]}
-            if world == 1 and not args.no_extras:
+            if world == 1 and args.full and not args.no_extras:
                 line["roofline_vjp"] = vjp_roofline(model, poses[args.warmup], args.pmc_file)
                 line["extra_workloads"] = {"config1": config1_workload(sd_c, poses[args.warmup], local, cpu_setting),
                                            "handoff": handoff_workload(model, not args.no_cpu_baseline),
@@ -1115,6 +1151,8 @@ def main():
         barrier()
         dt = allmax(time.perf_counter() - t0)
         phases = {k: round(allmax(v) / args.steps, 4) for k, v in phases.items()}
+        if args.dump_outputs and rank == 0:                 # the last sweep: this rank's render + the gathered images
+            dump_outputs(args.dump_outputs, dict(out, images_u8=all_u8, **({"images_f32": all_f32} if world > 1 else {})))
         ranks_seen, per_rank = rank_stats(float(np.mean(kernel_ms)))
         assert tuple(all_u8.shape) == (n_views, H, W, 3) and tuple(all_f32.shape) == (n_views, H, W, 3)
         if rank == 0:
@@ -1163,6 +1201,8 @@ def main():
             outs = sweep()
         barrier()
         dt = allmax(time.perf_counter() - t0)
+        if args.dump_outputs and rank == 0:                 # the last step's image of each of this rank's models
+            dump_outputs(args.dump_outputs, {"rgb_map_model%02d" % m: o for m, o in zip(mine, outs)})
         k_ms = float(np.mean([m.last_kernel_ms() for m in models])) if models else 0.0
         ranks_seen, per_rank = rank_stats(k_ms)
         if rank == 0:

@@ -1,10 +1,9 @@
 """f-4: on-disk readers of the render path's inputs -- the PNG decoder (all five scan-line filters) and
-load_LINEMOD_data (LL:97-163) on a synthetic dataset written in the reference's format; when the reference checkout
-is present the reader is pinned against the reference's own function on the same files."""
+load_LINEMOD_data (LL:97-163) on a synthetic dataset written in the reference's format, pinned against what the
+reference's own function returned for the same files (tests/golden/g27_linemod_reader.npz)."""
 import json
 import os
 import struct
-import subprocess
 import sys
 import zlib
 
@@ -108,39 +107,24 @@ def test_load_linemod_data_semantics(tmp_path):
     assert np.allclose(h_imgs[3, 2, 1], imgs[3, 4:6, 2:4].reshape(4, 4).mean(0), atol=1e-6)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/optimization"), reason="needs the reference checkout")
 def test_load_linemod_data_matches_reference(tmp_path):
-    """Pinned against LL:97-163 itself on the same files.  Two shims, both outside the arithmetic under test: imageio
-    (absent here) is replaced by this package's PNG decoder, and `pose_spherical` by the reference's own
-    `pose_spherical_nograd` -- the published call `pose_spherical(angle, -30.0, 1.01)` raises on a python float
-    (LL:63), so render_poses cannot be produced by the reference as written."""
+    """Pinned against LL:97-163 itself on the same files: tests/golden/g27_linemod_reader.npz holds what the reference's
+    load_LINEMOD_data(basedir, False, 2) returned for the dataset _make_dataset writes (oracle/gen_linemod_golden.py).  Two
+    shims there, both outside the arithmetic under test: imageio (absent) was replaced by this package's PNG decoder, and
+    `pose_spherical` by the reference's own `pose_spherical_nograd` -- the published call `pose_spherical(angle, -30.0, 1.01)`
+    raises on a python float (LL:63), so render_poses cannot be produced by the reference as written."""
+    sys.path.insert(0, ROOT)
+    from neural_sim_nerf_amd import data
+    g = np.load(os.path.join(ROOT, "tests", "golden", "g27_linemod_reader.npz"))
+    assert bool(g["pose_spherical_raises"])
     _make_dataset(str(tmp_path))
-    code = r'''
-import sys, types, json, numpy as np
-sys.path.insert(0, %r)
-from neural_sim_nerf_amd import png, data
-for m in ("imageio", "cv2"):
-    sys.modules[m] = types.ModuleType(m)
-sys.modules["imageio"].imread = png.imread
-sys.path.insert(0, "/root/reference/optimization")
-import utils.load_LINEMOD_noscale as LL
-try:
-    LL.load_LINEMOD_data(%r, False, 2)
-    raised = False
-except AttributeError:
-    raised = True
-LL.pose_spherical = LL.pose_spherical_nograd
-ref = LL.load_LINEMOD_data(%r, False, 2)
-got = data.load_LINEMOD_data(%r, False, 2)
-ok = raised
-ok &= np.array_equal(ref[0], got[0]) and ref[0].dtype == got[0].dtype
-ok &= np.array_equal(ref[1], got[1]) and np.array_equal(ref[2].numpy(), got[2].numpy())
-ok &= list(ref[3]) == list(got[3]) and ref[4] == got[4]
-ok &= all(np.array_equal(a, b) for a, b in zip(ref[5], got[5])) and ref[6] == got[6] and ref[7] == got[7]
-print("ok" if ok else "mismatch", raised)
-''' % (ROOT, str(tmp_path), str(tmp_path), str(tmp_path))
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and out.stdout.strip().splitlines()[-1] == "ok True", (out.stdout, out.stderr[-2000:])
+    imgs, poses, render_poses, hwf, K, i_split, near, far = data.load_LINEMOD_data(str(tmp_path), False, 2)
+    assert np.array_equal(imgs, g["imgs"]) and imgs.dtype == g["imgs"].dtype
+    assert np.array_equal(poses, g["poses"]) and poses.dtype == g["poses"].dtype
+    assert np.array_equal(render_poses.numpy(), g["render_poses"])
+    assert list(hwf) == g["hwf"].tolist() and K == g["K"].tolist()
+    assert all(np.array_equal(a, g[k]) for a, k in zip(i_split, ("i_train", "i_val", "i_test")))
+    assert near == float(g["near"]) and far == float(g["far"])
 
 
 def test_imwrite_many_equals_imwrite(tmp_path):

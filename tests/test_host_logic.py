@@ -591,18 +591,26 @@ def test_nerf_module_has_reference_parameter_names(synth_nets):
     n.invalidate()                                       # explicit hook: no native handle yet, must be a no-op
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/optimization"), reason="needs the reference checkout")
-def test_dropin_import_shadows_only_the_render_modules():
+def test_dropin_import_shadows_only_the_render_modules(tmp_path):
     """`from utils.run_nerf_noscale import *` as neural_sim_main.py:35 does, with the drop-in directory ahead of
     the reference's optimization/ on sys.path: render symbols come from this package, pose sampling
-    (utils.load_LINEMOD_noscale, NM:36) still comes from the reference."""
+    (utils.load_LINEMOD_noscale, NM:36) still comes from the reference.  The reference's side is a stand-in with its
+    layout: `utils` a namespace package (no __init__.py) holding run_nerf_noscale / run_nerf_helpers (which fail if they
+    are ever imported), gumble and load_LINEMOD_noscale (which star-imports utils.gumble and imports imageio / cv2)."""
     import subprocess
     import sys
+    ref = tmp_path / "optimization"
+    (ref / "utils").mkdir(parents=True)
+    for name in ("run_nerf_noscale", "run_nerf_helpers"):
+        (ref / "utils" / (name + ".py")).write_text("raise ImportError('the reference\\'s utils.%s was imported')\n" % name)
+    (ref / "utils" / "gumble.py").write_text("def gumbel_softmax(logits, tau):\n    return logits\n")
+    (ref / "utils" / "load_LINEMOD_noscale.py").write_text(
+        "import imageio\nimport cv2\nfrom utils.gumble import *\n\n\ndef sample_pose_nograd(prob, n, std):\n    return None\n")
     code = r'''
 import sys, types
 for m in ("imageio", "cv2"):
     sys.modules[m] = types.ModuleType(m)
-sys.path[:0] = [%r, %r, "/root/reference/optimization"]
+sys.path[:0] = [%r, %r, %r]
 ns = {}
 exec("from utils.run_nerf_noscale import *\nfrom utils.load_LINEMOD_noscale import *", ns)
 assert ns["render_path"].__module__ == "neural_sim_nerf_amd.run_nerf_noscale", ns["render_path"].__module__
@@ -610,10 +618,13 @@ assert ns["create_nerf"].__module__ == "neural_sim_nerf_amd.run_nerf_noscale"
 for name in ("render", "render_path_grad", "to8b", "device"):
     assert name in ns, name
 assert ns["sample_pose_nograd"].__module__ == "utils.load_LINEMOD_noscale"
+assert ns["gumbel_softmax"].__module__ == "utils.gumble"
 import utils.load_LINEMOD_noscale as LL
-assert LL.__file__.startswith("/root/reference/")
+import utils.run_nerf_helpers as RH
+assert LL.__file__.startswith(%r)
+assert RH.__file__.startswith(%r)
 print("ok")
-''' % (ROOT, os.path.join(ROOT, "neural_sim_nerf_amd", "dropin"))
+''' % (ROOT, os.path.join(ROOT, "neural_sim_nerf_amd", "dropin"), str(ref), str(ref), os.path.join(ROOT, "neural_sim_nerf_amd", "dropin"))
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "ok" in out.stdout, out.stderr[-2000:]
 

@@ -12,7 +12,7 @@ O=$R/gpurun_out/prof
 rm -rf $O; mkdir -p $O
 cd $R && python -c "from neural_sim_nerf_amd import _lib; print(_lib.kernel_source_hash())" > $O/kernel_source_sha256.txt
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py --steps 3 --warmup 1 > $O/bench.json 2> $O/bench.err
+python $R/bench.py --full --steps 3 --warmup 1 > $O/bench.json 2> $O/bench.err
 for mlp in f16x2 fp32 bf16x3; do
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$mlp -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --mlp $mlp > $O/stats_$mlp.log 2>&1
   NSR_MLP=$mlp timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_vjp_$mlp -- python $R/tools/bench_vjp.py 400 2 > $O/stats_vjp_$mlp.log 2>&1
