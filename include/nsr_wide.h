@@ -119,8 +119,10 @@ size_t nsrw_network_floats(const NsrwNet* net);
  * ATen's values are not np.linspace's); n_fine may be 0.  SETUP call. */
 int nsrw_upload_tables(nsrw_handle h, const float* t_coarse, int n_coarse, const float* u_fine, int n_fine);
 
-/* Bytes of workspace ONE chunk of `rays` rays needs (with_grad: for nsrw_render_rays_vjp, which keeps every activation of the
- * fine network).  The launch calls accept any workspace that holds a chunk of at least 64 rays. */
+/* Bytes of workspace ONE chunk of `rays` rays needs (with_grad = 1: for nsrw_render_rays_vjp, which keeps every activation of the
+ * last network; with_grad = 2: for nsrw_render_rays_vjp_cot with a coarse cotangent and N_importance > 0, whose gradient
+ * buffers hold either network).  The launch calls accept any workspace that holds a chunk of at least 64 rays; the chunk
+ * size decides nothing but how many rays one f16x2 re-run covers. */
 int nsrw_workspace_bytes(nsrw_handle h, int64_t rays, int with_grad, size_t* bytes);
 
 /* render_rays (RN:390-501) over n_rays rays.  near / far: scalars, overridden per ray by ex->d_near / d_far. */
@@ -128,11 +130,35 @@ int nsrw_render_rays(nsrw_handle h, const float* d_rays_o, const float* d_rays_d
                      const NsrwExtras* ex, const NsrwOut* out, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* The same forward plus d(sum(rgb * grad_rgb)) / d(rays_o, rays_d) (RN:177; weights frozen, z_samples detached RN:475, so
- * the gradient flows through the LAST pass only): d_grad_o, d_grad_d [N,3]; d_grad_viewdirs [N,3] iff ex->d_viewdirs is given
- * (d_grad_d then holds no view-direction term).  out (nullable) receives the forward's results. */
+ * an rgb cotangent flows through the LAST pass only): d_grad_o, d_grad_d [N,3]; d_grad_viewdirs [N,3] iff ex->d_viewdirs is
+ * given (d_grad_d then holds no view-direction term).  out (nullable) receives the forward's results.
+ * = nsrw_render_rays_vjp_cot with {d_rgb = d_grad_rgb} and every other cotangent NULL. */
 int nsrw_render_rays_vjp(nsrw_handle h, const float* d_rays_o, const float* d_rays_d, int64_t n_rays, float near_, float far_,
                          const NsrwExtras* ex, const float* d_grad_rgb, const NsrwOut* out, float* d_grad_o, float* d_grad_d,
                          float* d_grad_viewdirs, void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* Cotangents of render_rays' differentiable outputs (RN:488-494; z_std is not one: z_samples is detached, RN:475), all nullable
+ * DEVICE pointers: rgb / rgb0 [N,3], disp / acc / disp0 / acc0 [N].  rgb / disp / acc are the LAST pass's; with N_importance = 0
+ * that is the coarse pass, and rgb0 / disp0 / acc0 must be NULL.  A NULL cotangent contributes nothing; a given one -- zeros
+ * included -- contributes as torch's autograd would, NaN included: a ray with acc == 0 has disp = NaN (RN:381), and a disp
+ * cotangent there makes its d_grad_d NaN (through dists |d|, RN:361) while relu's backward keeps its d_grad_o finite. */
+typedef struct NsrwCotangents {
+  const float* d_rgb;
+  const float* d_disp;
+  const float* d_acc;
+  const float* d_rgb0;
+  const float* d_disp0;
+  const float* d_acc0;
+} NsrwCotangents;
+
+/* The forward plus d(sum over the given outputs of output * cotangent) / d(rays_o, rays_d[, viewdirs]), as
+ * nsrw_render_rays_vjp.  A coarse cotangent (N_importance > 0) runs, after the last pass's backward, the coarse network's
+ * forward once more with its activations kept, its backward, and adds its share into the same gradients -- the fp32 sum of
+ * the two passes' fp32 gradients; the workspace for that is nsrw_workspace_bytes(.., with_grad = 2).  On f16x2 handles those
+ * network passes are counted and re-run on bf16x3 like every other (nsrw_range_status). */
+int nsrw_render_rays_vjp_cot(nsrw_handle h, const float* d_rays_o, const float* d_rays_d, int64_t n_rays, float near_, float far_,
+                             const NsrwExtras* ex, const NsrwCotangents* cot, const NsrwOut* out, float* d_grad_o, float* d_grad_d,
+                             float* d_grad_viewdirs, void* d_workspace, size_t workspace_bytes, void* stream);
 
 /* run_network (RN:26-40): d_pts [P,3], d_viewdirs [P,3] (unit length; ignored without view directions) -> d_raw [P, C],
  * C = 4 or output_ch.  Workspace: nsrw_workspace_bytes(h, ceil(P / max(N_samples + N_importance, 1)), 0) suffices. */

@@ -384,16 +384,23 @@ __global__ void __launch_bounds__(64) kw_sort(const float* __restrict__ z0, cons
   }
 }
 
-// Backward of the compositing (the last pass's raw2outputs) for the cotangent of rgb_map, one thread per ray, fp32 forward
+// Backward of one pass's raw2outputs for the cotangents of its rgb_map / disp_map / acc_map, one thread per ray, fp32 forward
 // quantities recomputed exactly as kw_composite computed them, derivative arithmetic in fp64:
 //   w_i = alpha_i T_i, T_k (k > i) carries the factor om_i = 1 - alpha_i + 1e-10 -> dL/dalpha_i = A_i T_i - (sum_{k>i} A_k w_k) / om_i
-//   with A_i = g . sigmoid(rgb_i) [- sum g with a white background]; alpha = 1 - exp(-relu(sigma) dz |d|).
+//   with A_i = dL/dw_i = g . sigmoid(rgb_i) [- sum g with a white background, RN:384-385] + g_acc + dL/d(depth) z_i + dL/d(acc)
+//   through disp; alpha = 1 - exp(-relu(sigma) dz |d|).  disp = 1 / max(1e-10, depth / acc) (RN:380-382) is differentiated as
+//   torch does it: reciprocal -g disp^2, torch.max's backward (the whole cotangent to the quotient above 1e-10 AND for a NaN
+//   quotient, half of it on a tie), then the quotient rule.  A ray with acc == 0 has disp = NaN, so every A_i -- hence dL/dalpha
+//   and dL/d|d| -- is NaN, while relu's backward masks the density row to 0 (threshold_backward) exactly as in the reference.
+//   Without g_disp / g_acc the arithmetic is the rgb-only one, operation for operation.
 // Writes dL/draw [P,32] (rgb logits, sigma, zero padding: the K extent of the first backward GEMM) and dL/d|d| per ray.
 struct CompositeBwdArgs {
   int R, S, flags;
   const float* rgb; int ld_rgb; const float* sigma; int ld_sigma;
   const float* z; const float* nrm; const float* noise;
-  const float* grad_rgb;              // [R,3]
+  const float* grad_rgb;              // nullable [R,3]
+  const float* grad_disp;             // nullable [R]
+  const float* grad_acc;              // nullable [R]
   float* draw;                        // [P,32]
   float* gnorm;                       // [R]
   float* scr_a; float* scr_t;         // scratch [R,S] each: alpha_i, T_i
@@ -421,6 +428,7 @@ __global__ void __launch_bounds__(256) kw_composite_bwd(const CompositeBwdArgs a
   float* al_s = a.scr_a + (long long)r * a.S;
   float* t_s = a.scr_t + (long long)r * a.S;
   double T = 1.0;
+  float depth = 0.f, acc = 0.f;       // the forward's sequential fp32 sums (RN:380, RN:382), for disp only
   for (int i = 0; i < a.S; ++i) {
     const long long p = (long long)r * a.S + i;
     float dist = (i < a.S - 1) ? (z[i + 1] - z[i]) : 1e10f;
@@ -430,10 +438,28 @@ __global__ void __launch_bounds__(256) kw_composite_bwd(const CompositeBwdArgs a
     const float al = 1.0f - expf(-relu_nan(sg) * dist);
     al_s[i] = al;
     t_s[i] = (float)T;
+    if (a.grad_disp) {
+      const float w = al * (float)T;
+      depth = depth + w * z[i];
+      acc = acc + w;
+    }
     T = T * (double)((1.0f - al) + 1e-10f);
   }
-  const double g0 = a.grad_rgb[r * 3 + 0], g1 = a.grad_rgb[r * 3 + 1], g2 = a.grad_rgb[r * 3 + 2];
+  const double g0 = a.grad_rgb ? a.grad_rgb[r * 3 + 0] : 0.0, g1 = a.grad_rgb ? a.grad_rgb[r * 3 + 1] : 0.0,
+               g2 = a.grad_rgb ? a.grad_rgb[r * 3 + 2] : 0.0;
   const double gsum = (a.flags & NSRW_FLAG_WHITE_BKGD) ? (g0 + g1 + g2) : 0.0;
+  // dL/dw_i beyond the rgb term: g_w + g_z z_i (acc_map and depth_map; disp through depth and acc)
+  const bool extra = a.grad_disp || a.grad_acc;
+  double g_w = a.grad_acc ? (double)a.grad_acc[r] : 0.0, g_z = 0.0;
+  if (a.grad_disp) {
+    const float qd = depth / acc;
+    const float disp = (qd != qd) ? qd : 1.0f / fmaxf(1e-10f, qd);
+    double dq = -(double)a.grad_disp[r] * ((double)disp * (double)disp);       // reciprocal
+    if (qd < 1e-10f) dq = 0.0;                                                // torch.max: the clamp binds
+    else if (qd == 1e-10f) dq = 0.5 * dq;                                     // ... a tie splits the cotangent
+    g_z = dq / (double)acc;
+    g_w += -dq * ((double)depth / (double)acc) / (double)acc;
+  }
   double suffix = 0.0, dn = 0.0;
   for (int i = a.S - 1; i >= 0; --i) {
     const long long p = (long long)r * a.S + i;
@@ -441,7 +467,8 @@ __global__ void __launch_bounds__(256) kw_composite_bwd(const CompositeBwdArgs a
     const double c0 = sigmoidf_(q[0]), c1 = sigmoidf_(q[1]), c2 = sigmoidf_(q[2]);
     const double al = al_s[i], Ti = t_s[i];
     const double w = (double)(al_s[i] * t_s[i]);
-    const double A = g0 * c0 + g1 * c1 + g2 * c2 - gsum;
+    double A = g0 * c0 + g1 * c1 + g2 * c2 - gsum;
+    if (extra) A += g_w + g_z * (double)z[i];
     const double om = (double)((1.0f - al_s[i]) + 1e-10f);
     const double d_alpha = A * Ti - suffix / om;
     suffix += A * w;
@@ -480,6 +507,7 @@ struct EmbedBwdArgs {
   const float* rays_o; const float* rays_d; const float* z; const float* vd; const float* nrm; const float* gnorm;
   const float* GE; int ldE; const float* GED; int ldED;       // dL/d encodings [P, Ci], [P, Cv] (GED nullable)
   int given_viewdirs;
+  int accumulate;                                             // 0: write the gradients; 1: add them to what is there (a second pass)
   float* grad_o; float* grad_d; float* grad_v;                // [R,3]; grad_v only with given view directions
   const float* gscale;                                        // nullable [P]: 1 / s of the point's normalised chain (kw_composite_bwd)
 };
@@ -533,20 +561,28 @@ __global__ void __launch_bounds__(64) kw_embed_bwd(const EmbedBwdArgs a) {
   double u[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) u[c] = d[c] / nrm;                       // d|d| / dd = d / |d|
+  float ro[3], rd[3], rv[3] = {0.f, 0.f, 0.f};
   if (a.given_viewdirs) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      a.grad_o[r * 3 + c] = (float)go[c];
-      a.grad_d[r * 3 + c] = (float)(gd[c] + gn * u[c]);
-      if (a.grad_v) a.grad_v[r * 3 + c] = (float)gv[c];
+      ro[c] = (float)go[c];
+      rd[c] = (float)(gd[c] + gn * u[c]);
+      rv[c] = (float)gv[c];
     }
   } else {
     const double dot = gv[0] * u[0] + gv[1] * u[1] + gv[2] * u[2];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      a.grad_o[r * 3 + c] = (float)go[c];
-      a.grad_d[r * 3 + c] = (float)(gd[c] + gn * u[c] + (gv[c] - u[c] * dot) / nrm);      // d(d / |d|)
+      ro[c] = (float)go[c];
+      rd[c] = (float)(gd[c] + gn * u[c] + (gv[c] - u[c] * dot) / nrm);      // d(d / |d|)
     }
+  }
+  // accumulate: the fp32 sum of the two passes' fp32 gradients, as autograd adds the two branches that reach the rays
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    a.grad_o[r * 3 + c] = a.accumulate ? a.grad_o[r * 3 + c] + ro[c] : ro[c];
+    a.grad_d[r * 3 + c] = a.accumulate ? a.grad_d[r * 3 + c] + rd[c] : rd[c];
+    if (a.given_viewdirs && a.grad_v) a.grad_v[r * 3 + c] = a.accumulate ? a.grad_v[r * 3 + c] + rv[c] : rv[c];
   }
 }
 
@@ -824,8 +860,9 @@ struct Chunk {
   float *DRAW, *GV, *G0, *G1, *GEP, *GED, *gscale;
 };
 
-// floats per point of the forward buffers of `n`
-void carve_chunk(const Handle& h, long long R, bool grad, Carve& c, Chunk& k) {
+// grad: 0 = forward only, 1 = + the last pass's backward (nsrw_render_rays_vjp), 2 = + the coarse pass's backward as well
+// (nsrw_render_rays_vjp_cot with coarse cotangents and N_importance > 0: the gradient buffers hold either network)
+void carve_chunk(const Handle& h, long long R, int grad, Carve& c, Chunk& k) {
   const int S0 = h.cfg.n_samples, NI = h.cfg.n_importance, S1 = NI > 0 ? S0 + NI : 0;
   const long long Smax = std::max(S0, S1), P = R * Smax;
   const Net& n0 = h.net[0];
@@ -837,10 +874,15 @@ void carve_chunk(const Handle& h, long long R, bool grad, Carve& c, Chunk& k) {
   k.E = c.f(P * mx(&Net::Ci)); k.ED = c.f(P * mx(&Net::Cv));
   k.FA = c.f(P * mx(&Net::ldfa)); k.HV = c.f(P * mx(&Net::W2p)); k.RAW = c.f(P * 32);
   const Net& last = NI > 0 ? n1 : n0;
-  const int nH = grad ? std::max(2, last.d.D) : 2;
+  const int nH = grad >= 2 ? std::max(2, std::max(n0.d.D, last.d.D)) : grad ? std::max(2, last.d.D) : 2;
   k.H.resize(nH);
   for (int i = 0; i < nH; ++i) k.H[i] = c.f(P * mx(&Net::Wp));
-  if (grad) {
+  if (grad >= 2) {
+    const long long Pg = R * (S1 > 0 ? S1 : S0);
+    k.scr_a = c.f(Pg); k.scr_t = c.f(Pg); k.gscale = c.f(Pg);
+    k.DRAW = c.f(Pg * 32); k.GV = c.f(Pg * mx(&Net::W2p)); k.G0 = c.f(Pg * mx(&Net::Wp)); k.G1 = c.f(Pg * mx(&Net::Wp));
+    k.GEP = c.f(Pg * mx(&Net::Ci)); k.GED = c.f(Pg * mx(&Net::Cv));
+  } else if (grad) {
     const long long Pg = R * (S1 > 0 ? S1 : S0);
     k.scr_a = c.f(Pg); k.scr_t = c.f(Pg); k.gscale = c.f(Pg);
     k.DRAW = c.f(Pg * 32); k.GV = c.f(Pg * last.W2p); k.G0 = c.f(Pg * last.Wp); k.G1 = c.f(Pg * last.Wp);
@@ -1065,7 +1107,7 @@ int check_common(Handle* h, const float* ro, const float* rd, long long n, const
   return 0;
 }
 
-long long chunk_rays(Handle* h, size_t bytes, bool grad, long long n) {
+long long chunk_rays(Handle* h, size_t bytes, int grad, long long n) {
   // largest R (multiple of 64, <= n rounded up) whose chunk fits `bytes`; 0 if not even 64 rays fit
   auto need = [&](long long R) { Carve c(nullptr); Chunk k; carve_chunk(*h, R, grad, c, k); return c.off; };
   if (need(64) > bytes) return 0;
@@ -1079,10 +1121,15 @@ long long chunk_rays(Handle* h, size_t bytes, bool grad, long long n) {
 }
 
 int render_impl(Handle* h, const float* ro, const float* rd, long long n, float near_, float far_, const NsrwExtras* ex,
-                const float* grad_rgb, const NsrwOut* out, float* grad_o, float* grad_d, float* grad_v, void* ws, size_t ws_bytes,
-                hipStream_t st) {
-  const bool grad = grad_rgb != nullptr;
+                const NsrwCotangents* cot, const NsrwOut* out, float* grad_o, float* grad_d, float* grad_v, void* ws,
+                size_t ws_bytes, hipStream_t st) {
   const int S0 = h->cfg.n_samples, NI = h->cfg.n_importance, S1 = NI > 0 ? S0 + NI : 0, SL = NI > 0 ? S1 : S0;
+  // the last pass's backward runs for a cotangent on rgb / disp / acc, the coarse pass's (N_importance > 0) for one on
+  // rgb0 / disp0 / acc0 -- after the last pass's, into the same gradients; no cotangent at all: zero gradients
+  const bool grad_last = cot && (cot->d_rgb || cot->d_disp || cot->d_acc);
+  const bool grad_c = cot && NI > 0 && (cot->d_rgb0 || cot->d_disp0 || cot->d_acc0);
+  const bool grad = grad_last || grad_c;
+  const int mode = grad_c ? 2 : grad ? 1 : 0;
   const Net& n0 = h->net[0];
   const Net& n1 = (NI > 0 && h->net[1].loaded) ? h->net[1] : h->net[0];
   const Net& last = NI > 0 ? n1 : n0;
@@ -1093,7 +1140,7 @@ int render_impl(Handle* h, const float* ro, const float* rd, long long n, float 
   if (n == 0) return 0;
   if (!ws) return fail("nsrw: null workspace");
   if ((reinterpret_cast<uintptr_t>(ws) & 255) != 0) return fail("nsrw: workspace must be 256-byte aligned");
-  const long long R = chunk_rays(h, ws_bytes, grad, n);
+  const long long R = chunk_rays(h, ws_bytes, mode, n);
   if (R == 0) return fail("nsrw: workspace too small for a chunk of 64 rays (nsrw_workspace_bytes)");
   if ((size_t)S1 * sizeof(float) > 64 * 1024) return fail("nsrw: too many samples per ray for the sort kernel");
   h->chunks = 0;
@@ -1103,7 +1150,7 @@ int render_impl(Handle* h, const float* ro, const float* rd, long long n, float 
     const int Rc = (int)std::min<long long>(R, n - r0);
     Carve c(ws);
     Chunk k;
-    carve_chunk(*h, R, grad, c, k);
+    carve_chunk(*h, R, mode, c, k);
     if (c.off > ws_bytes) return fail("nsrw: internal error: the chunk's carve exceeds the workspace");      // (chunk_rays sized it)
     const unsigned rb = (Rc + 255) / 256;
     RayArgs ra{};
@@ -1127,7 +1174,7 @@ int render_impl(Handle* h, const float* ro, const float* rd, long long n, float 
     // ---- coarse pass (RN:463-467) ----
     const float* sigma; int ld_sigma;
     encode(n0, k.z0, S0);
-    const bool grad_coarse = grad && NI == 0;
+    const bool grad_coarse = grad_last && NI == 0;
     if (net_forward(h->gemm_cfg, st, n0, k, (long long)Rc * S0, grad_coarse, &sigma, &ld_sigma)) return 1;
     CompositeArgs ca{};
     ca.R = Rc; ca.S = S0; ca.flags = h->cfg.flags; ca.rgb = k.RAW; ca.ld_rgb = n0.ldraw; ca.sigma = sigma; ca.ld_sigma = ld_sigma;
@@ -1159,7 +1206,7 @@ int render_impl(Handle* h, const float* ro, const float* rd, long long n, float 
         NSRW_HIP(hipMemcpyAsync(k.zf, e.d_z_fine + r0 * S1, (size_t)Rc * S1 * 4, hipMemcpyDeviceToDevice, st));
       // ---- fine pass (RN:478-485) ----
       encode(n1, k.zf, S1);
-      if (net_forward(h->gemm_cfg, st, n1, k, (long long)Rc * S1, grad, &sigma, &ld_sigma)) return 1;
+      if (net_forward(h->gemm_cfg, st, n1, k, (long long)Rc * S1, grad_last, &sigma, &ld_sigma)) return 1;
       CompositeArgs cf = ca;
       cf.S = S1; cf.ld_rgb = n1.ldraw; cf.sigma = sigma; cf.ld_sigma = ld_sigma; cf.z = k.zf; cf.noise = e.d_noise1 ? e.d_noise1 + r0 * S1 : nullptr;
       cf.weights = k.wf;
@@ -1176,22 +1223,40 @@ int render_impl(Handle* h, const float* ro, const float* rd, long long n, float 
       noise_last = cf.noise;
     }
     if (o.d_z_vals) NSRW_HIP(hipMemcpyAsync(o.d_z_vals + r0 * SL, z_last, (size_t)Rc * SL * 4, hipMemcpyDeviceToDevice, st));
-    if (grad) {
-      const long long P = (long long)Rc * SL;
+    // one pass's backward: raw2outputs (the pass's cotangents, offset to the chunk inside) -> network -> encodings and rays
+    auto backward = [&](const Net& nn, const float* z, int S, const float* noise, const float* sg, int ld_sg, const float* g_rgb,
+                        const float* g_disp, const float* g_acc, int accumulate) -> int {
+      const long long P = (long long)Rc * S;
       NSRW_HIP(hipMemsetAsync(k.DRAW, 0, (size_t)P * 32 * 4, st));
       CompositeBwdArgs cb{};
-      cb.R = Rc; cb.S = SL; cb.flags = h->cfg.flags; cb.rgb = k.RAW; cb.ld_rgb = last.ldraw; cb.sigma = sigma; cb.ld_sigma = ld_sigma;
-      cb.z = z_last; cb.nrm = k.nrm; cb.noise = noise_last; cb.grad_rgb = grad_rgb + r0 * 3; cb.draw = k.DRAW; cb.gnorm = k.gnorm;
+      cb.R = Rc; cb.S = S; cb.flags = h->cfg.flags; cb.rgb = k.RAW; cb.ld_rgb = nn.ldraw; cb.sigma = sg; cb.ld_sigma = ld_sg;
+      cb.z = z; cb.nrm = k.nrm; cb.noise = noise; cb.draw = k.DRAW; cb.gnorm = k.gnorm;
+      cb.grad_rgb = g_rgb ? g_rgb + r0 * 3 : nullptr; cb.grad_disp = g_disp ? g_disp + r0 : nullptr;
+      cb.grad_acc = g_acc ? g_acc + r0 : nullptr;
       cb.scr_a = k.scr_a; cb.scr_t = k.scr_t; cb.gscale = h->gemm_cfg.h2 ? k.gscale : nullptr;
       hipLaunchKernelGGL(kw_composite_bwd, dim3(rb), dim3(256), 0, st, cb);
-      if (net_backward(h->gemm_cfg, st, last, k, P)) return 1;
+      if (net_backward(h->gemm_cfg, st, nn, k, P)) return 1;
       EmbedBwdArgs eb{};
-      eb.R = Rc; eb.S = SL; eb.L = last.d.multires; eb.Lv = last.d.multires_views;
-      eb.rays_o = ra.rays_o; eb.rays_d = ra.rays_d; eb.z = z_last; eb.vd = k.vd; eb.nrm = k.nrm; eb.gnorm = k.gnorm;
-      eb.GE = k.GEP; eb.ldE = last.Ci; eb.GED = last.d.use_viewdirs ? k.GED : nullptr; eb.ldED = last.Cv;
-      eb.given_viewdirs = e.d_viewdirs != nullptr; eb.gscale = cb.gscale;
+      eb.R = Rc; eb.S = S; eb.L = nn.d.multires; eb.Lv = nn.d.multires_views;
+      eb.rays_o = ra.rays_o; eb.rays_d = ra.rays_d; eb.z = z; eb.vd = k.vd; eb.nrm = k.nrm; eb.gnorm = k.gnorm;
+      eb.GE = k.GEP; eb.ldE = nn.Ci; eb.GED = nn.d.use_viewdirs ? k.GED : nullptr; eb.ldED = nn.Cv;
+      eb.given_viewdirs = e.d_viewdirs != nullptr; eb.gscale = cb.gscale; eb.accumulate = accumulate;
       eb.grad_o = grad_o + r0 * 3; eb.grad_d = grad_d + r0 * 3; eb.grad_v = grad_v ? grad_v + r0 * 3 : nullptr;
       hipLaunchKernelGGL(kw_embed_bwd, dim3((unsigned)Rc), dim3(64), 0, st, eb);
+      return 0;
+    };
+    if (grad_last && backward(last, z_last, SL, noise_last, sigma, ld_sigma, cot->d_rgb, cot->d_disp, cot->d_acc, 0)) return 1;
+    if (grad_c) {
+      // ---- the coarse pass's backward (RN:463-467 with rgb0 / disp0 / acc0, RN:492-494): its forward again, activations kept
+      // (the buffers the last pass's backward is done with), then the same three stages, adding into the rays' gradients
+      encode(n0, k.z0, S0);
+      if (net_forward(h->gemm_cfg, st, n0, k, (long long)Rc * S0, true, &sigma, &ld_sigma)) return 1;
+      if (backward(n0, k.z0, S0, ca.noise, sigma, ld_sigma, cot->d_rgb0, cot->d_disp0, cot->d_acc0, grad_last ? 1 : 0)) return 1;
+    }
+    if (cot && !grad) {       // cotangents given, all NULL: the gradient of nothing
+      NSRW_HIP(hipMemsetAsync(grad_o + r0 * 3, 0, (size_t)Rc * 3 * 4, st));
+      NSRW_HIP(hipMemsetAsync(grad_d + r0 * 3, 0, (size_t)Rc * 3 * 4, st));
+      if (grad_v) NSRW_HIP(hipMemsetAsync(grad_v + r0 * 3, 0, (size_t)Rc * 3 * 4, st));
     }
     ++h->chunks;
   }
@@ -1493,7 +1558,7 @@ int nsrw_workspace_bytes(nsrw_handle hh, int64_t rays, int with_grad, size_t* by
   const long long R = (rays + 63) / 64 * 64;
   Carve c(nullptr);
   Chunk k;
-  carve_chunk(*h, R, with_grad != 0, c, k);
+  carve_chunk(*h, R, with_grad >= 2 ? 2 : with_grad != 0 ? 1 : 0, c, k);
   *bytes = c.off;
   return 0;
 }
@@ -1515,7 +1580,24 @@ int nsrw_render_rays_vjp(nsrw_handle hh, const float* d_rays_o, const float* d_r
   if (n_rays > 0 && (!d_grad_rgb || !d_grad_o || !d_grad_d)) return fail("nsrw_render_rays_vjp: null gradient buffer");
   if (d_grad_viewdirs && !(ex && ex->d_viewdirs)) return fail("nsrw_render_rays_vjp: grad_viewdirs without given view directions");
   NSRW_DEVICE(h);
-  return render_impl(h, d_rays_o, d_rays_d, n_rays, near_, far_, ex, d_grad_rgb, out, d_grad_o, d_grad_d, d_grad_viewdirs, ws,
+  NsrwCotangents cot{};
+  cot.d_rgb = d_grad_rgb;
+  return render_impl(h, d_rays_o, d_rays_d, n_rays, near_, far_, ex, &cot, out, d_grad_o, d_grad_d, d_grad_viewdirs, ws,
+                     ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+int nsrw_render_rays_vjp_cot(nsrw_handle hh, const float* d_rays_o, const float* d_rays_d, int64_t n_rays, float near_, float far_,
+                             const NsrwExtras* ex, const NsrwCotangents* cot, const NsrwOut* out, float* d_grad_o, float* d_grad_d,
+                             float* d_grad_viewdirs, void* ws, size_t ws_bytes, void* stream) {
+  Handle* h = reinterpret_cast<Handle*>(hh);
+  if (check_common(h, d_rays_o, d_rays_d, n_rays, ex)) return 1;
+  if (!cot) return fail("nsrw_render_rays_vjp_cot: null cotangents");
+  if (n_rays > 0 && (!d_grad_o || !d_grad_d)) return fail("nsrw_render_rays_vjp_cot: null gradient buffer");
+  if (h->cfg.n_importance == 0 && (cot->d_rgb0 || cot->d_disp0 || cot->d_acc0))
+    return fail("nsrw_render_rays_vjp_cot: rgb0 / disp0 / acc0 cotangents without N_importance (the coarse pass IS the last one)");
+  if (d_grad_viewdirs && !(ex && ex->d_viewdirs)) return fail("nsrw_render_rays_vjp_cot: grad_viewdirs without given view directions");
+  NSRW_DEVICE(h);
+  return render_impl(h, d_rays_o, d_rays_d, n_rays, near_, far_, ex, cot, out, d_grad_o, d_grad_d, d_grad_viewdirs, ws,
                      ws_bytes, static_cast<hipStream_t>(stream));
 }
 

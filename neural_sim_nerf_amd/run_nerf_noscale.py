@@ -106,6 +106,13 @@ def _model_for(network_fn, network_fine, n_importance, kw=None, trust=False):
                 cache["model"] = NsrModel(_native_sd(network_fn), _native_sd(network_fine) if network_fine is not None
                                           else None, device=dev, n_importance=n_importance, white_bkgd=white,
                                           lindisp=lindisp, mlp=forced, n_samples=n_samples)
+                # the layered TWIN of this handle (_twin): the same networks in the modules' own layout, the same options and
+                # arithmetic, built on the first backward that the fused VJP kernels do not serve (_vjp_route)
+                own = lambda net: {k: v.detach() for k, v in net.state_dict().items()}
+                cache["model"].twin_spec = dict(
+                    sd_coarse=own(network_fn), sd_fine=own(network_fine) if network_fine is not None else None, device=dev,
+                    n_importance=n_importance, white_bkgd=white, lindisp=lindisp, n_samples=n_samples,
+                    mlp=cache["model"].mlp if cache["model"].mlp in ("f16x2", "bf16x3", "fp32") else "fp32")
             cache["model"].weights_version = ident
         cache["key"] = key
         cache["fp"] = fp
@@ -225,28 +232,108 @@ def _get_rays_autograd(H, W, K, c2w):
     return _util_model(c2w.device).get_rays(int(H), int(W), K, c2w)
 
 
+DIFFERENTIABLE = ("rgb_map", "disp_map", "acc_map", "rgb0", "disp0", "acc0")     # RN:488-494 (z_std: RN:475 detaches z_samples)
+
+
+def _vjp_route(model, cotangent_keys):
+    """Which renderer differentiates a backward of render() whose cotangents are on `cotangent_keys` (outputs present in the
+    graph): "fused" -- the fused VJP kernels of the handle itself, for rgb_map alone on a coarse+fine handle (their input-gradient
+    kernels differentiate the fine pass's rgb only); "twin" -- every other backward on a fused handle, on its layered twin
+    (_twin: the same networks and arithmetic); "layered" -- a layered handle differentiates everything itself.  None: nothing
+    to differentiate."""
+    keys = set(cotangent_keys)
+    if not keys:
+        return None
+    if str(getattr(model, "mlp", "")).startswith("layered-"):
+        return "layered"
+    if keys == {"rgb_map"} and model.n_importance > 0:
+        return "fused"
+    return "twin"
+
+
+def _twin(model):
+    """The layered handle (wide.WideModel) of a fused handle's networks, options and arithmetic, built once per fused handle
+    from _model_for's twin_spec and kept with it (it shares the layered renderer's workspace of its stream)."""
+    t = getattr(model, "_twin", None)
+    if t is None:
+        spec = getattr(model, "twin_spec", None)
+        if spec is None:
+            raise NotImplementedError("this handle was not made by the drop-in API (_model_for): it has no layered twin for the "
+                                      "gradient of disp / acc / the coarse outputs")
+        from .wide import WideModel
+        t = model._twin = WideModel(**spec)
+        t.weights_version = getattr(model, "weights_version", None)
+    return t
+
+
+def _twin_extras(model, twin, ex):
+    """The per-ray extras of a fused handle's forward in the layered renderer's layout: the resampling uniforms as the
+    n_importance draws themselves (the fused kernels read rows of 128: padded, or repeated 128 / n times -- _draws)."""
+    if not ex or ex.get("u") is None or ex["u"].shape[-1] == twin.n_importance:
+        out = ex
+    else:
+        u, ni = ex["u"], twin.n_importance
+        out = dict(ex, u=(u[:, :ni] if model.ni_kernel == ni else u[:, ::u.shape[-1] // ni]).contiguous())
+    if out and out.get("noise1") is not None and out["noise1"].shape[-1] != twin.nf_kernel:
+        raise NotImplementedError("the gradient of disp / acc / the coarse outputs with raw_noise_std > 0 and N_importance=%d on the "
+                                  "fused kernels (their fine noise covers duplicated samples); NSR_LAYERED=1 serves it" % twin.n_importance)
+    return out
+
+
+def _render_vjp(model, rays_o, rays_d, near, far, cot, extras=None):
+    """(grad_o, grad_d[, grad_viewdirs]) for the cotangents `cot` {output: tensor} on the route _vjp_route names (recorded in
+    model.last_vjp_route).  rgb_map alone goes to the handle's own render_rays_vjp exactly as before."""
+    route = _vjp_route(model, cot)
+    model.last_vjp_route = route
+    ex = {} if extras is None else {"extras": extras}
+    if route == "fused" or (route == "layered" and set(cot) == {"rgb_map"}):
+        return model.render_rays_vjp(rays_o, rays_d, near, far, cot["rgb_map"], **ex)
+    m = model
+    if route == "twin":
+        m = _twin(model)
+        if extras is not None:
+            ex = {"extras": _twin_extras(model, m, extras)}
+    if set(cot) == {"rgb_map"}:
+        return m.render_rays_vjp(rays_o, rays_d, near, far, cot["rgb_map"], **ex)
+    return m.render_rays_vjp(rays_o, rays_d, near, far, cotangents=cot, **ex)
+
+
+def _outputs(ctx, out, model, want_raw):
+    """render_rays' returns in render()'s order; z_std and raw carry no gradient (RN:475; a cotangent on raw is not served)."""
+    fine = model.n_importance > 0
+    keys = ["rgb_map", "disp_map", "acc_map"] + (["rgb0", "disp0", "acc0", "z_std"] if fine else [])
+    if want_raw:
+        keys.append("raw" if fine else "raw0")
+    ctx.keys = keys
+    ctx.set_materialize_grads(False)        # an output absent from the graph contributes nothing (None), not a zero cotangent
+    ctx.mark_non_differentiable(*[out[k] for k in keys if k not in DIFFERENTIABLE])
+    return tuple(out[k] for k in keys)
+
+
+def _cotangents(ctx, grads):
+    return {k: g for k, g in zip(ctx.keys, grads) if g is not None and k in DIFFERENTIABLE}
+
+
 class _RenderRays(torch.autograd.Function):
-    """render(rays=...) with the input-side VJP the bilevel loop needs (RN:177: d rgb / d rays; network weights
-    are frozen and z_samples is detached, RN:475, so nothing else carries gradient)."""
+    """render(rays=...) with the input-side VJP (RN:177: d outputs / d rays; network weights are frozen and z_samples is
+    detached, RN:475): rgb_map, disp_map, acc_map and the coarse rgb0 / disp0 / acc0 are differentiable, as in the reference;
+    _vjp_route says which renderer runs the backward."""
 
     @staticmethod
     def forward(ctx, rays_o, rays_d, model, near, far, want_raw):
         out = model.render_rays(rays_o.detach(), rays_d.detach(), near, far, debug=want_raw)
         ctx.save_for_backward(rays_o.detach(), rays_d.detach())
         ctx.cfg = (model, near, far)
-        fine = model.n_importance > 0
-        keys = ["rgb_map", "disp_map", "acc_map"] + (["rgb0", "disp0", "acc0", "z_std"] if fine else [])
-        if want_raw:
-            keys.append("raw" if fine else "raw0")
-        ctx.n_out = len(keys)
-        ctx.mark_non_differentiable(*[out[k] for k in keys[1:]])
-        return tuple(out[k] for k in keys)
+        return _outputs(ctx, out, model, want_raw)
 
     @staticmethod
-    def backward(ctx, g_rgb, *others):
+    def backward(ctx, *grads):
         model, near, far = ctx.cfg
         rays_o, rays_d = ctx.saved_tensors
-        go, gd = model.render_rays_vjp(rays_o, rays_d, near, far, g_rgb)
+        cot = _cotangents(ctx, grads)
+        if not cot:
+            return None, None, None, None, None, None
+        go, gd = _render_vjp(model, rays_o, rays_d, near, far, cot)
         return go, gd, None, None, None, None
 
 
@@ -263,18 +350,16 @@ class _RenderRaysEx(torch.autograd.Function):
         out = model.render_rays(rays_o.detach(), rays_d.detach(), near, far, debug=want_raw, extras=ex)
         ctx.save_for_backward(rays_o.detach(), rays_d.detach())
         ctx.cfg = (model, near, far, ex)
-        fine = model.n_importance > 0
-        keys = ["rgb_map", "disp_map", "acc_map"] + (["rgb0", "disp0", "acc0", "z_std"] if fine else [])
-        if want_raw:
-            keys.append("raw" if fine else "raw0")
-        ctx.mark_non_differentiable(*[out[k] for k in keys[1:]])
-        return tuple(out[k] for k in keys)
+        return _outputs(ctx, out, model, want_raw)
 
     @staticmethod
-    def backward(ctx, g_rgb, *others):
+    def backward(ctx, *grads):
         model, near, far, ex = ctx.cfg
         rays_o, rays_d = ctx.saved_tensors
-        res = model.render_rays_vjp(rays_o, rays_d, near, far, g_rgb, extras=ex)
+        cot = _cotangents(ctx, grads)
+        if not cot:
+            return (None,) * 8
+        res = _render_vjp(model, rays_o, rays_d, near, far, cot, extras=ex)
         gv = res[2] if "viewdirs" in ex else None
         return res[0], res[1], gv, None, None, None, None, None
 
@@ -535,7 +620,7 @@ def _scaled_hw(hwf, render_factor):
     return int(H), int(W), focal
 
 
-def _path_setup(name, hwf, render_factor, render_kwargs, need_fine=False):
+def _path_setup(name, hwf, render_factor, render_kwargs):
     """-> (H, W, near, far, handle, general).  general: ndc=True / perturb > 0 / raw_noise_std > 0 are in the kwargs -- the
     reference forwards **render_kwargs to render() unchanged (RN:233, RN:168), so render_kwargs_train works there; here
     such a call goes through render() too (per pose), the deterministic one through the batched launches."""
@@ -547,9 +632,6 @@ def _path_setup(name, hwf, render_factor, render_kwargs, need_fine=False):
     _check_kwargs(kw)
     n_imp = kw.get("N_importance", 0)
     model = _model_for(kw["network_fn"], kw.get("network_fine", None) if n_imp > 0 else None, n_imp, kw)
-    if need_fine and n_imp == 0 and not getattr(model, "mlp", "").startswith("layered-"):
-        raise NotImplementedError("%s needs the coarse+fine configuration (N_importance > 0) on the fused kernels (their "
-                                  "input-gradient kernels differentiate the fine pass; NSR_LAYERED=1 serves coarse-only)" % name)
     return H, W, near, far, model, general
 
 
@@ -610,7 +692,10 @@ def _pose_patch_grads(model, c2w, cot, H, W, K, near, far, N_rand, render_kwargs
             g_pose = model.pose_grad(g[0].contiguous(), g[1].contiguous(), H, W, K, N_rand)
         return rgb.detach().reshape(H, W, 3), g_pose
     with torch.no_grad():
-        go, gd, out = model.render_rays_vjp(ro.reshape(-1, 3), rd.reshape(-1, 3), near, far, cot, with_forward=True)
+        # (a coarse-only fused handle: its fused VJP kernels differentiate the fine pass only -- the layered twin does, _vjp_route)
+        model.last_vjp_route = route = _vjp_route(model, ["rgb_map"])
+        vjp = _twin(model) if route == "twin" else model
+        go, gd, out = vjp.render_rays_vjp(ro.reshape(-1, 3), rd.reshape(-1, 3), near, far, cot, with_forward=True)
         g_pose = model.pose_grad(go, gd, H, W, K, N_rand)
     return out["rgb_map"].reshape(H, W, 3), g_pose
 
@@ -629,7 +714,7 @@ def render_path_grad(categorical_prob, render_poses, hwf, K, chunk, grad_E, rend
     are all-gathered, so every rank returns the reference's full (rgbs, dLdpsis) in pose-major order and NM:184-191
     run unchanged (the mean over the stacked list equals dist.mean_psi_grad's all-reduce)."""
     from . import dist as D
-    H, W, near, far, model, general = _path_setup("render_path_grad", hwf, render_factor, render_kwargs, need_fine=True)
+    H, W, near, far, model, general = _path_setup("render_path_grad", hwf, render_factor, render_kwargs)
     n_rays = H * W
     N_rand = int(chunk)
     n_patches = (n_rays + N_rand - 1) // N_rand

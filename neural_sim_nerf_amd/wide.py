@@ -39,6 +39,17 @@ class NsrwOut(C.Structure):
                 ("d_raw0", C.c_void_p)]
 
 
+class NsrwCotangents(C.Structure):
+    _fields_ = [("d_rgb", C.c_void_p), ("d_disp", C.c_void_p), ("d_acc", C.c_void_p), ("d_rgb0", C.c_void_p),
+                ("d_disp0", C.c_void_p), ("d_acc0", C.c_void_p)]
+
+
+# render()'s differentiable outputs (RN:488-494) -> the field of NsrwCotangents and the shape of one ray's cotangent
+COTANGENTS = {"rgb_map": ("d_rgb", 3), "disp_map": ("d_disp", 1), "acc_map": ("d_acc", 1),
+              "rgb0": ("d_rgb0", 3), "disp0": ("d_disp0", 1), "acc0": ("d_acc0", 1)}
+COARSE_COTANGENTS = ("rgb0", "disp0", "acc0")
+
+
 # name -> (restype, argtypes); every symbol include/nsr_wide.h declares
 SIGNATURES = {
     "nsrw_last_error": (C.c_char_p, []),
@@ -53,6 +64,9 @@ SIGNATURES = {
     "nsrw_render_rays_vjp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
                                        C.POINTER(NsrwExtras), C.c_void_p, C.POINTER(NsrwOut), C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_size_t, C.c_void_p]),
+    "nsrw_render_rays_vjp_cot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float,
+                                           C.POINTER(NsrwExtras), C.POINTER(NsrwCotangents), C.POINTER(NsrwOut), C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "nsrw_run_network": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
                                    C.c_void_p]),
     "nsrw_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
@@ -279,12 +293,13 @@ class WideModel:
         return torch.empty(shape, dtype=dtype, device=self.device)
 
     def _need(self, n_rays, grad):
-        """bytes one chunk of n_rays rays needs (cached per handle: the bilevel loop asks for the same 512 rays 313 times a pose)"""
-        key = (int(n_rays), bool(grad))
+        """bytes one chunk of n_rays rays needs (cached per handle: the bilevel loop asks for the same 512 rays 313 times a pose).
+        grad: 0 / False, 1 / True (the last pass's backward), 2 (the coarse pass's as well: nsrw_workspace_bytes)"""
+        key = (int(n_rays), int(grad))
         v = self._ws_need.get(key)
         if v is None:
             need = C.c_size_t()
-            check(self.lib.nsrw_workspace_bytes(self.h, key[0], 1 if grad else 0, C.byref(need)))
+            check(self.lib.nsrw_workspace_bytes(self.h, key[0], key[1], C.byref(need)))
             v = self._ws_need[key] = int(need.value)
         return v
 
@@ -371,9 +386,14 @@ class WideModel:
         ro, rd = self.util.get_rays_views(int(H), int(W), K, self._f32(c2w))
         return self.render_rays(ro, rd, near, far, debug=debug)
 
-    def render_rays_vjp(self, rays_o, rays_d, near, far, grad_rgb, with_forward=False, z_fine=None, extras=None, debug=False):
+    def render_rays_vjp(self, rays_o, rays_d, near, far, grad_rgb=None, with_forward=False, z_fine=None, extras=None, debug=False,
+                        cotangents=None):
         """Forward + input-side VJP (RN:168-178): grad_rgb [N,3] -> (grad_rays_o, grad_rays_d) [N,3] each (+ grad_viewdirs with
-        extras["viewdirs"], + the forward's rgb / disp / acc with with_forward)."""
+        extras["viewdirs"], + the forward's rgb / disp / acc with with_forward).
+        cotangents: {output name: cotangent} for any of render()'s differentiable outputs (COTANGENTS: rgb_map / disp_map / acc_map
+        of the last pass, rgb0 / disp0 / acc0 of the coarse one when N_importance > 0) instead of -- or, for rgb_map, besides --
+        grad_rgb: the gradient of the sum of their contractions (nsrw_render_rays_vjp_cot).  A missing or None entry contributes
+        nothing; a given one follows torch's autograd of the reference, NaN included."""
         if debug:
             raise NotImplementedError("the layered renderer has no relu taps")
         if z_fine is not None:                      # given depths for the fine pass (constants of the gradient, RN:475)
@@ -381,7 +401,22 @@ class WideModel:
         rays_o, rays_d = self._f32(rays_o, (-1, 3)), self._f32(rays_d, (-1, 3))
         n = rays_o.shape[0]
         self.rays_launched += n
-        g = self._f32(grad_rgb, (n, 3))
+        cot = None
+        if cotangents is not None:
+            cot = {k: v for k, v in dict(cotangents).items() if v is not None}
+            unknown = set(cot) - set(COTANGENTS)
+            if unknown:
+                raise ValueError("cotangents: not differentiable outputs of render(): %s (z_std and raw are not: RN:475)" % sorted(unknown))
+            if grad_rgb is not None:
+                if "rgb_map" in cot:
+                    raise ValueError("grad_rgb and cotangents['rgb_map'] both given")
+                cot["rgb_map"] = grad_rgb
+            if self.n_importance == 0 and any(k in cot for k in COARSE_COTANGENTS):
+                raise ValueError("cotangents %s: a coarse-only handle's outputs are rgb_map / disp_map / acc_map"
+                                 % sorted(k for k in cot if k in COARSE_COTANGENTS))
+            cot = {k: self._f32(v, (n, COTANGENTS[k][1]) if COTANGENTS[k][1] > 1 else (n,)) for k, v in cot.items()}
+        elif grad_rgb is None:
+            raise ValueError("render_rays_vjp: grad_rgb or cotangents")
         go, gd = self._new(n, 3), self._new(n, 3)
         fwd, out = None, None
         if with_forward:
@@ -389,10 +424,19 @@ class WideModel:
             out = NsrwOut(_dev(fwd["rgb_map"]), _dev(fwd["disp_map"]), _dev(fwd["acc_map"]))
         ex, keep = self._extras(extras, n)
         gv = self._new(n, 3) if (keep and "viewdirs" in keep) else None
-        ws, nbytes = self._workspace(n, True)
-        check(self.lib.nsrw_render_rays_vjp(self.h, _dev(rays_o), _dev(rays_d), n, float(near), float(far),
-                                            C.byref(ex) if ex else None, _dev(g), C.byref(out) if out else None, _dev(go), _dev(gd),
-                                            _dev(gv), _dev(ws), nbytes, _stream_ptr(self.device)))
+        if cot is None:
+            g = self._f32(grad_rgb, (n, 3))
+            ws, nbytes = self._workspace(n, True)
+            check(self.lib.nsrw_render_rays_vjp(self.h, _dev(rays_o), _dev(rays_d), n, float(near), float(far),
+                                                C.byref(ex) if ex else None, _dev(g), C.byref(out) if out else None, _dev(go),
+                                                _dev(gd), _dev(gv), _dev(ws), nbytes, _stream_ptr(self.device)))
+        else:
+            ct = NsrwCotangents(*[_dev(cot.get(k)) for k in COTANGENTS])
+            coarse = self.n_importance > 0 and any(k in cot for k in COARSE_COTANGENTS)
+            ws, nbytes = self._workspace(n, 2 if coarse else 1)
+            check(self.lib.nsrw_render_rays_vjp_cot(self.h, _dev(rays_o), _dev(rays_d), n, float(near), float(far),
+                                                    C.byref(ex) if ex else None, C.byref(ct), C.byref(out) if out else None,
+                                                    _dev(go), _dev(gd), _dev(gv), _dev(ws), nbytes, _stream_ptr(self.device)))
         res = (go, gd) if gv is None else (go, gd, gv)
         return res + (fwd,) if with_forward else res
 
