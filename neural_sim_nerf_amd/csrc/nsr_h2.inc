@@ -236,6 +236,108 @@ __device__ __forceinline__ void step_h2(Ring& rg, f32x4 (&Acur)[4], f32x4 (&Anxt
 #undef NSR_H2_FRAG
 }
 
+// ---- the tail of a layer GEMM: the LAST k16 block with the layer's epilogue in its MFMA gaps ----------------------------
+// Between two layer GEMMs sit the epilogue in = clamp(acc) (the accumulators live in AGPRs: one v_accvgpr_read and one
+// v_max_i32 per value, 256 instructions) and the next layer's bias load (32 ds_read_b128).  With one wave per SIMD nothing
+// covers them: the matrix pipe idles for every one of their issue cycles, while the gaps between the last 24 MFMAs of the
+// GEMM are empty (the last block has no next block to split).  So the last block of an 8-output-block GEMM -- always one
+// whole slab, steps g = 0..3 -- gets an order of its own in which accumulators become FINAL one after another,
+//     MFMA  0  1  2  3  4  5  6* 7* 8* 9 10 11 12 13 14 15* 16* 17 18 19 20 21* 22* 23*        (* = last MFMA of that
+//     acc   0  1  2  0  1  2  0  1  2  3  4  5  3  4  6  3   4   7  5  6  7  5   6   7          accumulator)
+// and whatever is final is clamped into in[] (dead by now: the last block was split during the one before) and re-loaded
+// with the next layer's bias in the gaps that follow.  What the order keeps:
+//   * per accumulator the three MFMAs of the block come in the order they have in step_h2 (even pairs: hi.bl, hi.bh, lo.bh;
+//     odd pairs: lo.bh, hi.bl, hi.bh) -- the fp32 accumulation order, hence every bit of the result;
+//   * an accumulator recurs no sooner than three MFMAs later (which is also why no order retires much earlier: any three
+//     consecutive MFMAs go to three different accumulators, so the last three end at 21, 22, 23 whatever one does);
+//   * the slab's chunk layout (chunk c of the slab = step c / 4, fragment c % 4 of step_h2) -- only the read order differs;
+//   * the slab-change duties of step G = 3 at the MFMAs they had: one LDS-DMA piece after MFMA 4, 10, 16, 18, the counted
+//     wait + barrier after MFMA 19 (every read of this slab has been issued by then: the chunks of the last four MFMAs
+//     sit in A1), the next slab's first fragments into A0 after MFMA 20..23;
+//   * a gap carries a fragment read or a DMA piece or bias reads, never two of them.
+// The accumulators 0..4 are clamped inside the block (160 instructions) and 0 and half of 1 re-loaded; accumulators 5, 6, 7
+// retire with the last three MFMAs: their 96 clamp instructions and the 26 bias reads that are left stay behind the last MFMA
+// (137 instructions with the ring's scalar bookkeeping) and the split of the next layer's first block before the next first
+// MFMA (35) -- 172 per layer where 482 stood (tools/isa_mix.py; measured -2.6 % kernel time, profiles/r07/ab_epilogue.txt).
+struct H2Tail {
+  f32x16 (&acc)[8];
+  f32x16 (&in)[8];
+  int thr;                 // clamp_bits16 threshold of this layer: 0 = relu, INT_MIN = none
+  unsigned bias;           // LDS byte address of this lane's half of the NEXT layer's bias (aux layout, load_bias)
+  __device__ __forceinline__ void clamp(int k, int q) const {           // a quarter of accumulator k
+#pragma unroll
+    for (int r = 4 * q; r < 4 * q + 4; ++r) in[k][r] = __int_as_float(max(__float_as_int(acc[k][r]), thr));
+  }
+  __device__ __forceinline__ void load(int k, int rq) const {            // a quarter of the next bias into accumulator k
+    const f32x4 v = *(const __attribute__((address_space(3))) f32x4*)(bias + (k * 4 + rq) * 32);
+    acc[k][rq * 4 + 0] = v[0];
+    acc[k][rq * 4 + 1] = v[1];
+    acc[k][rq * 4 + 2] = v[2];
+    acc[k][rq * 4 + 3] = v[3];
+  }
+};
+// the LDS address of p + h4 as ONE opaque per-lane register: every access through it is base + immediate offset (the aux
+// block sits above 64 KiB, beyond the reach of a ds offset from the LDS base: without this each read gets a v_add of its own)
+__device__ __forceinline__ unsigned h2_lds_base(const float* p, int h4) {
+  return (unsigned)opaque_v((int)(unsigned)(size_t)(const __attribute__((address_space(3))) float*)(p + h4));
+}
+
+template <int NS, typename Tail>
+__device__ __forceinline__ void tail_h2(Ring& rg, f32x4 (&A0)[4], f32x4 (&A1)[4], const H2& b, f32x16 (&acc)[8], int lane,
+                                        const Tail& t) {
+  const char* p = rg.smem + rg.cslot * kSlabBytes + lane * 16;          // A0 holds chunks 0..3 of this slab
+#define NSR_T_MFMA(k, frag, bop) NSR_PIN(); acc[k] = mfma_h2(frag, b.bop, acc[k]); NSR_PIN()
+#define NSR_T_READ(dst, c) dst = *(const f32x4*)(p + (c) * 1024)
+  // chunks: 0 hi0, 1 hi1, 2 lo2, 3 lo3 | 4 hi2, 5 hi3, 6 lo0, 7 lo1 | 8 hi4, 9 hi5, 10 lo6, 11 lo7 | 12 hi6, 13 hi7, 14 lo4, 15 lo5
+  NSR_T_MFMA(0, A0[0], lo); NSR_T_READ(A1[0], 4);
+  NSR_T_MFMA(1, A0[1], lo); NSR_T_READ(A1[1], 6);
+  NSR_T_MFMA(2, A0[2], hi); NSR_T_READ(A1[2], 7);
+  NSR_T_MFMA(0, A0[0], hi); NSR_T_READ(A1[3], 8);
+  NSR_T_MFMA(1, A0[1], hi); ring_issue_dma1<0>(rg);
+  NSR_T_MFMA(2, A1[0], lo); NSR_T_READ(A0[2], 9);
+  NSR_T_MFMA(0, A1[1], hi); NSR_T_READ(A0[0], 5);                                     // 0 final
+  NSR_T_MFMA(1, A1[2], hi); NSR_T_READ(A0[1], 10);                                    // 1 final
+  NSR_T_MFMA(2, A1[0], hi); NSR_T_READ(A1[1], 14); t.clamp(0, 0); t.clamp(0, 1);      // 2 final
+  NSR_T_MFMA(3, A0[3], hi); NSR_T_READ(A1[2], 11); t.clamp(0, 2); t.clamp(0, 3);
+  NSR_T_MFMA(4, A1[3], lo); ring_issue_dma1<1>(rg); t.clamp(1, 0); t.clamp(1, 1);
+  NSR_T_MFMA(5, A0[2], lo); NSR_T_READ(A1[0], 12); t.clamp(1, 2); t.clamp(1, 3);
+  NSR_T_MFMA(3, A0[0], lo); t.clamp(2, 0); t.clamp(2, 1); t.load(0, 0); t.load(0, 1);
+  NSR_T_MFMA(4, A1[3], hi); t.clamp(2, 2); t.clamp(2, 3); t.load(0, 2); t.load(0, 3);
+  NSR_T_MFMA(6, A0[1], hi); t.load(1, 0); t.load(1, 1);
+  NSR_T_MFMA(3, A0[0], hi); NSR_T_READ(A1[3], 13);                                    // 3 final
+  NSR_T_MFMA(4, A1[1], hi); ring_issue_dma1<2>(rg);                                   // 4 final
+  NSR_T_MFMA(7, A1[2], hi); NSR_T_READ(A1[1], 15); t.clamp(3, 0); t.clamp(3, 1);
+  NSR_T_MFMA(5, A0[2], hi); ring_issue_dma1<3>(rg); t.clamp(3, 2); t.clamp(3, 3);
+  NSR_T_MFMA(6, A1[0], lo);
+  // as in step_h2, G == 3: every read of this slab is complete, my share of the next slab has landed, for the whole workgroup
+#ifdef NSR_EXP_NOVMWAIT
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#else
+  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(4 * (NS - 2)) : "memory");
+#endif
+#ifndef NSR_EXP_NOBARRIER
+  __builtin_amdgcn_s_barrier();
+#endif
+  rg.cslot = (rg.cslot + 1 == NS) ? 0 : rg.cslot + 1;
+  p = rg.smem + rg.cslot * kSlabBytes + lane * 16;
+  NSR_T_MFMA(7, A1[3], lo); NSR_T_READ(A0[0], 0); t.clamp(4, 0); t.clamp(4, 1);
+  NSR_T_MFMA(5, A1[1], hi); NSR_T_READ(A0[1], 1); t.clamp(4, 2); t.clamp(4, 3);      // 5 final
+  NSR_T_MFMA(6, A1[0], hi); NSR_T_READ(A0[2], 2);                                     // 6 final
+  const bool wrapped = ring_issue_advance_a<NS, kStreamSlabs, kStreamSlabsH2Bwd>(rg);
+  NSR_T_MFMA(7, A1[3], hi); NSR_T_READ(A0[3], 3);                                     // 7 final
+  ring_issue_advance_b(rg, wrapped);
+  NSR_PIN();
+  // what does not fit: the rest of the bias of 1, the bias of 2, 3, 4 and all of 5, 6, 7
+  t.load(1, 2); t.load(1, 3);
+#pragma unroll
+  for (int k = 2; k < 8; ++k) {
+    if (k >= 5) { t.clamp(k, 0); t.clamp(k, 1); t.clamp(k, 2); t.clamp(k, 3); }
+    t.load(k, 0); t.load(k, 1); t.load(k, 2); t.load(k, 3);
+  }
+#undef NSR_T_READ
+#undef NSR_T_MFMA
+}
+
 // The power of two a k16 block's values are multiplied with before the split: m[0] for blocks < split, m[1] from there on
 // (the views layer reads 16 blocks of scaled registers and 2 of unscaled direction encoding); split >= NKB: one scale.
 struct H2Scale {
@@ -303,6 +405,39 @@ __device__ __forceinline__ void gemm_h2(Ring& rg, f32x4 (&A0)[4], f32x4 (&A1)[4]
     }
     if (more) b = bn;
   }
+  NSR_PIN();
+  amax = __builtin_fmaxf(amax, __builtin_fmaxf(am[0] * scale.m[0], am[1] * scale.m[1]));
+}
+
+// gemm_h2 for an 8-output-block layer whose LAST k16 block runs as tail_h2: the layer's epilogue and the next layer's bias
+// load in its MFMA gaps (tail: H2Tail).  A function of its own, so that gemm_h2 -- the input-gradient kernels use nothing
+// else -- stays the text it was.  Every k16 block is one whole slab (steps g = 0..3); the accumulators come with their bias.
+template <int NKB, typename Src, typename Tail>
+__device__ __forceinline__ void gemm_h2_tail(Ring& rg, f32x4 (&A0)[4], f32x4 (&A1)[4], Src src, const H2Scale scale,
+                                             f32x16 (&acc)[8], int lane, float& amax, const Tail tail) {
+  static_assert(NKB > 1, "the last block is not the first");
+  float am[2] = {0.0f, 0.0f};                      // per scale class, unscaled
+  H2 b;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) split_pair_h2(src(0, 2 * j), src(0, 2 * j + 1), scale(0), j, b, am[0 >= scale.split]);
+#pragma unroll
+  for (int kb = 0; kb + 1 < NKB; ++kb) {
+    H2 bn;
+    const int cls = kb + 1 >= scale.split;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      H2Job job[1] = {H2Job{src(kb + 1, 2 * s), src(kb + 1, 2 * s + 1), scale(kb + 1), 0u, 0.0f, 0.0f}};
+      const int hb = 2 * s, lb = 2 * (s ^ 1);
+#define NSR_H2_STEP(GG, AC, AN) step_h2<kRingSlots, GG, 1, true, false, false>(rg, AC, AN, b, acc, hb, lb, lane, job, s, bn, am[cls])
+      if (s == 0) NSR_H2_STEP(0, A0, A1);
+      if (s == 1) NSR_H2_STEP(1, A1, A0);
+      if (s == 2) NSR_H2_STEP(2, A0, A1);
+      if (s == 3) NSR_H2_STEP(3, A1, A0);
+#undef NSR_H2_STEP
+    }
+    b = bn;
+  }
+  tail_h2<kRingSlots>(rg, A0, A1, b, acc, lane, tail);
   NSR_PIN();
   amax = __builtin_fmaxf(amax, __builtin_fmaxf(am[0] * scale.m[0], am[1] * scale.m[1]));
 }

@@ -429,22 +429,37 @@ __device__ __forceinline__ void mlp_pass(Ring& rg, const float* aux, f32x4 (&A0)
   constexpr bool H2M = MODE == kMlpH2;
   float amax = 0.0f;                       // kMlpH2: largest |scaled activation| this lane has split so far
   const float* h2s = aux + kAuxH2Scale;
+  // kMlpH2 forward kernels: the epilogue of a layer (in = clamp(acc)) and the bias load of the NEXT layer run in the MFMA
+  // gaps of the layer's last k16 block (tail_h2, nsr_h2.inc) -- acc arrives at every GEMM with its bias already in it.
+  // Not with CAPTURE: relu_mask reads acc before the clamp, and k_render_vjp_h2 has no register to spare (512 of 512).
+  // (tail_h2 issues the LDS-DMA pieces where step schedule 3 does and knows none of step_h2's timing-experiment switches:
+  // the r03 / r04 A/B schedule and the NSR_EXP_H2_* ablation builds keep the plain epilogue, every block follows the switch.)
+#if NSR_H2_SCHED == 3 && !defined(NSR_EXP_H2_NOFRAG) && !defined(NSR_EXP_H2_HALFBARRIER) && !defined(NSR_EXP_H2_NOSPLIT)
+  constexpr bool TAIL = H2M && !CAPTURE;
+#else
+  constexpr bool TAIL = false;
+#endif
+  static_assert(kAuxBiasV == kAuxBias + 9 * 256, "the views layer's bias follows feature_linear's: 'bias of layer L + 1' for L = 8");
   NSR_TP(0);
   load_bias<8>(aux + kAuxBias, h4, acc);
   NSR_TP(2);
   if constexpr (B3) gemm_b3<8, 2>(rg, A0, A1, enc_src, acc, lane);
+  else if constexpr (TAIL)
+    gemm_h2_tail<4>(rg, A0, A1, enc_src, H2Scale{{h2s[0], 0.0f}, 4}, acc, lane, amax, H2Tail{acc, in, 0, h2_lds_base(aux + kAuxBias + 256, h4)});
   else if constexpr (H2M) gemm_h2<8, 4>(rg, A0, A1, enc_src, H2Scale{{h2s[0], 0.0f}, 4}, acc, lane, amax);
   else seg<8, 8>(rg, A0, A1, BArr<32>{e}, acc, lane);
   NSR_TP(1);
   if (CAPTURE) mask_dst[mask_tid] = relu_mask<8>(acc);
+  if constexpr (!TAIL) {
 #pragma unroll
-  for (int mo = 0; mo < 8; ++mo) in[mo] = relu16(acc[mo]);
+    for (int mo = 0; mo < 8; ++mo) in[mo] = relu16(acc[mo]);
+  }
 
   float alpha_part = 0.0f;
   // layers 1..7 (ReLU) and 8 = feature_linear (no activation)
 #pragma unroll 1
   for (int L = 1; L <= 8; ++L) {
-    load_bias<8>(aux + kAuxBias + L * 256, h4, acc);
+    if constexpr (!TAIL) load_bias<8>(aux + kAuxBias + L * 256, h4, acc);
     NSR_TP(2);
     if (L == 5) {                                                // skip: cat([input_pts, h]) -> input columns first (RH:105)
       if constexpr (B3) gemm_b3<8, 2>(rg, A0, A1, enc_src, acc, lane);
@@ -464,18 +479,28 @@ __device__ __forceinline__ void mlp_pass(Ring& rg, const float* aux, f32x4 (&A0)
       }
     }
     if constexpr (B3) gemm_b3<8, 8>(rg, A0, A1, in_src, acc, lane);
+    else if constexpr (TAIL)     // (after L = 8 the views layer's bias goes into acc[0..3]; acc[4..7] get the 128 floats that follow it, unused)
+      gemm_h2_tail<16>(rg, A0, A1, in_src, H2Scale{{h2s[L], 0.0f}, 16}, acc, lane, amax,
+                       H2Tail{acc, in, (L == 8) ? (int)0x80000000 : 0, h2_lds_base(aux + kAuxBias + (L + 1) * 256, h4)});
     else if constexpr (H2M) gemm_h2<8, 16>(rg, A0, A1, in_src, H2Scale{{h2s[L], 0.0f}, 16}, acc, lane, amax);
     else seg<8, 32>(rg, A0, A1, BRegs16<8>{in}, acc, lane);
     NSR_TP(1);
     if (CAPTURE && L < 8) mask_dst[L * 256 + mask_tid] = relu_mask<8>(acc);
-    const int thr = (L == 8) ? (int)0x80000000 : 0;      // feature_linear has no activation
+    if constexpr (!TAIL) {
+      const int thr = (L == 8) ? (int)0x80000000 : 0;      // feature_linear has no activation
 #pragma unroll
-    for (int mo = 0; mo < 8; ++mo) in[mo] = clamp_bits16(acc[mo], thr);
+      for (int mo = 0; mo < 8; ++mo) in[mo] = clamp_bits16(acc[mo], thr);
+    }
   }
 
   // views_linears.0 (RH:111-115): cat([feature, input_views]) -> 128, ReLU
   f32x16 av[4];
-  load_bias<4>(aux + kAuxBiasV, h4, av);
+  if constexpr (TAIL) {
+#pragma unroll
+    for (int mo = 0; mo < 4; ++mo) av[mo] = acc[mo];
+  } else {
+    load_bias<4>(aux + kAuxBiasV, h4, av);
+  }
   NSR_TP(2);
   if constexpr (B3) {        // 16 blocks of features, 2 of direction encoding, 2 of padding (a group is 4 blocks)
     auto v_src = [&](int kb, int i) {
