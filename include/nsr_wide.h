@@ -46,7 +46,7 @@ enum { NSRW_FLAG_WHITE_BKGD = 1,     /* RN:384-385 */
 
 typedef struct NsrwConfig {
   int32_t device;
-  int32_t n_samples;                 /* N_samples >= 2 (RN:439) */
+  int32_t n_samples;                 /* N_samples (RN:439): 3 .. NSRW_MAX_SAMPLES -- sample_pdf needs an interior weight; nsrw_create refuses less */
   int32_t n_importance;              /* N_importance >= 0 (RN:474); 0 = coarse only */
   int32_t flags;
   int32_t reserved[4];

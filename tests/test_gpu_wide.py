@@ -696,7 +696,8 @@ def test_layered_debug_bounds_build_is_clean(tmp_path):
     """`make debug` compiles nsr_wide.hip with -DNSR_DEBUG_BOUNDS too (r06): every global / LDS index of the GEMM body (kw_gemm_h2 /
     _b3 / _f32) and of the per-ray kernels is checked against its extent.  A fresh process runs, on ALL THREE arithmetics, the edge shapes (W = 34,
     3 + 512 samples, 61 rays), ragged run_network calls, NaN / zero / infinite rays, a 64-ray-chunk workspace and the
-    gradient; no check may trip, and every output equals the release build's."""
+    gradient -- and, on 128-row tiles (NSRW_B3_WM=2), the W = 34 case and the 10 x 384 network; no check may trip, and every output
+    equals the release build's."""
     import subprocess
     dbg = os.path.join(ROOT, "neural_sim_nerf_amd", "csrc", "libnsr_debug.so")
     if not os.path.exists(dbg):
@@ -719,16 +720,25 @@ for mlp in ("bf16x3", "fp32", "f16x2"):
     for tag in "bcd":
         c, f, ns, ni = wide_case(O, g, tag)
         cases.append((c, f if ni else None, ns, ni, g["rays_o"], g["rays_d"]))
-    for i, (c, f, ns, ni, o, d) in enumerate(cases):
-        for gb in ("16", "0.0001"):
-            os.environ["NSR_WIDE_WORKSPACE_GB"] = gb
+    runs = [(i, case, gb, None) for i, case in enumerate(cases) for gb in ("16", "0.0001")]
+    # ... and on 128-row tiles (NSRW_B3_WM=2, read by nsrw_create): the W = 34 case (kw_gemm_* <1,2>) and the 10 x 384 network of
+    # g25 a, whose 384 and 192 columns are cut into 256 + 128 and 128 + 64 there (<4,2>, <2,2>) -- same process, same build
+    c, f, ns, ni = wide_case(O, g, "a")
+    runs += [(0, cases[0], "16", "2"), (4, (c, f, ns, ni, g["rays_o"], g["rays_d"]), "16", "2")]
+    for i, (c, f, ns, ni, o, d), gb, wm in runs:
+        os.environ["NSR_WIDE_WORKSPACE_GB"] = gb
+        if wm:
+            os.environ["NSRW_B3_WM"] = wm
+        try:
             m = WideModel(c, f, n_samples=ns, n_importance=ni, mlp=mlp)
-            r = m.render_rays(o, d, O.YCBV_NEAR, O.YCBV_FAR, debug=True)
-            go, gd = m.render_rays_vjp(o, d, O.YCBV_NEAR, O.YCBV_FAR, np.ones((len(o), 3), np.float32))
-            rn = m.run_network(np.zeros((129, 3), np.float32) + 0.01, np.tile(np.float32([0, 0, 1]), (129, 1)), 0)
-            res += [r["rgb_map"].cpu().numpy(), r["z_fine" if ni else "z_coarse"].cpu().numpy(), go.cpu().numpy(), gd.cpu().numpy(), rn.cpu().numpy()]
-            out["%%s_%%d_%%s" %% (mlp, i, gb)] = m.debug_bounds_status()
-            m.close()
+        finally:
+            os.environ.pop("NSRW_B3_WM", None)
+        r = m.render_rays(o, d, O.YCBV_NEAR, O.YCBV_FAR, debug=True)
+        go, gd = m.render_rays_vjp(o, d, O.YCBV_NEAR, O.YCBV_FAR, np.ones((len(o), 3), np.float32))
+        rn = m.run_network(np.zeros((129, 3), np.float32) + 0.01, np.tile(np.float32([0, 0, 1]), (129, 1)), 0)
+        res += [r["rgb_map"].cpu().numpy(), r["z_fine" if ni else "z_coarse"].cpu().numpy(), go.cpu().numpy(), gd.cpu().numpy(), rn.cpu().numpy()]
+        out["%%s_%%d_%%s%%s" %% (mlp, i, gb, "_wm" + wm if wm else "")] = m.debug_bounds_status()
+        m.close()
 np.savez(sys.argv[1] + "/res.npz", *res)
 print(out)
 ''' % (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden", "g25_wide_networks.npz"))
@@ -740,9 +750,9 @@ print(out)
                            timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         res[name] = eval(r.stdout.strip().splitlines()[-1])
-    assert len(res["debug"]) == 24 and all(v == (True, 0) for v in res["debug"].values()), res["debug"]
+    assert len(res["debug"]) == 30 and all(v == (True, 0) for v in res["debug"].values()), res["debug"]
     assert all(v == (False, 0) for v in res["release"].values()), res["release"]
     a, b = np.load(tmp_path / "debug" / "res.npz"), np.load(tmp_path / "release" / "res.npz")
-    assert len(a.files) == len(b.files) == 120
+    assert len(a.files) == len(b.files) == 150
     for k in a.files:
         assert np.array_equal(a[k], b[k], equal_nan=True), k
