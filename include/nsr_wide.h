@@ -36,7 +36,7 @@ typedef struct NsrwHandle_* nsrw_handle;
 enum { NSRW_FLAG_WHITE_BKGD = 1,     /* RN:384-385 */
        NSRW_FLAG_LINDISP = 2,        /* RN:443 */
        NSRW_FLAG_MLP_BF16X3 = 4,     /* r06: the layer GEMMs on bf16 MFMAs, every fp32 operand split exactly into three bf16 pieces, six
-                                      * piece products per product, fp32 accumulate (csrc/nsr_wide_b3.inc): fp32-grade results, fp32's
+                                      * piece products per product, fp32 accumulate (csrc/nsr_wide_gemm.inc): fp32-grade results, fp32's
                                       * exponent range, 2.67x the matrix-pipe rate of the fp32 MFMAs.  Without a flag: fp32 MFMAs. */
        NSRW_FLAG_MLP_F16X2 = 8 };    /* r06: the layer GEMMs on fp16 MFMAs, every fp32 operand as two fp16 pieces, three piece products
                                       * (the arithmetic of the fused default kernel, csrc/nsr_h2.inc: |error| <= 2^-22 per product;
@@ -183,9 +183,21 @@ int nsrw_range_status(nsrw_handle h, unsigned long long* passes, unsigned long l
 /* Device time of the last launch call (ms; synchronises on its closing event) and the number of chunks it ran. */
 int nsrw_last_ms(nsrw_handle h, float* ms, int* chunks);
 
+/* DIAGNOSTIC; needs no device and no handle.  The launches one layer GEMM is cut into along N: for a matrix packed with
+ * n_packed_rows rows (a multiple of 32 in the library's own use; its weight image is padded to an even count of 32-column blocks) of
+ * which the caller stores n_stored_columns columns, on a handle whose 256-column tiles have tile_wm = 4 (256 rows, the default) or 2
+ * (128 rows: NSRW_B3_WM=2) wave rows.  A part is `tiles` tiles of 64 nj columns from 32-column block col_block on, run by the kernel
+ * form <nj, wm>; a part that would start behind the last stored column is not launched and not listed.  Writes the first max_parts
+ * parts and returns how many there are (at most 3); -1 for an argument out of range.  The tests hold their own statement of the rule
+ * to this one. */
+typedef struct NsrwGemmPart {
+  int32_t nj, wm, tiles, col_block;
+} NsrwGemmPart;
+int nsrw_gemm_plan(int n_packed_rows, int n_stored_columns, int tile_wm, NsrwGemmPart* parts_out, int max_parts);
+
 /* libnsr_debug.so (-DNSR_DEBUG_BOUNDS) checks every global / LDS index of this unit's kernels against its extent; a violation is
  * recorded, not trapped.  built_with_checks: 1 in that build, 0 in the product library; first_bad_line: 0 = clean, else the source
- * line of the (highest) failed check -- nsr_wide.hip's line, or 100000 + the line of nsr_wide_b3.inc.  Synchronises the device. */
+ * line of the (highest) failed check -- nsr_wide.hip's line, or 100000 + the line of nsr_wide_gemm.inc.  Synchronises the device. */
 int nsrw_debug_bounds_status(int* built_with_checks, unsigned* first_bad_line);
 
 #ifdef __cplusplus

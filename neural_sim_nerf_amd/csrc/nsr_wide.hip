@@ -8,9 +8,9 @@
 // with every activation matrix [points, width] resident in the caller's workspace (HBM), and for the gradient
 //   composite_bwd -> the same GEMM kernel on the transposed weights, relu masks read from the stored activations
 //   -> encode_bwd + the per-ray reductions.
-// The GEMM (kw_gemm) is fp32 in, fp32 MFMA (v_mfma_f32_32x32x2_f32), fp32 out: the reference's arithmetic, no operand
-// splitting, no range to manage.  Every K and N extent is padded to a multiple of 32 with zero weights, so no kernel carries a
-// K tail; M (points) is arbitrary.
+// The GEMM (nsr_wide_gemm.inc) is fp32 in HBM on both sides and runs on fp16 MFMAs with two-piece operands (f16x2, the default),
+// on bf16 MFMAs with three-piece operands (bf16x3) or on fp32 MFMAs (the strict mode): fp32-grade results in every case.  Every K
+// and N extent is padded to a multiple of 32 with zero weights, so no kernel carries a K tail; M (points) is arbitrary.
 //
 // (RN = optimization/utils/run_nerf_noscale.py, RH = optimization/utils/run_nerf_helpers.py of the reference.)
 #include <hip/hip_runtime.h>
@@ -43,12 +43,12 @@ __device__ unsigned g_wide_violation = 0u;
 #else
 #define NSRW_CHECK(cond) do { } while (0)
 #endif
-#define NSRW_FILE_TAG 0            /* nsr_wide.hip: the line itself; nsr_wide_b3.inc: 100000 + line */
+#define NSRW_FILE_TAG 0            /* nsr_wide.hip: the line itself; nsr_wide_gemm.inc: 100000 + line (it sets its own tag) */
 
 // ------------------------------------------------------------------------------------------------------------------------
 // GEMM: C[m][n] = epi( sum_k A[m][k] * Wt[n][k] + bias[n] ), A = [A1 | A2] (two row-major segments: the skip concatenation
 // cat[input_pts, h] RH:105-106 and cat[feature, input_views] RH:113 without materialising them), both K extents multiples of 32.
-// ONE kernel body for the three arithmetics (nsr_wide_b3.inc: gemm_split_body -> kw_gemm_h2 / kw_gemm_b3 / kw_gemm_f32): weights as an
+// ONE kernel body for the three arithmetics (nsr_wide_gemm.inc: gemm_split_body -> kw_gemm_h2 / kw_gemm_b3 / kw_gemm_f32): weights as an
 // LDS image moved by LDS-DMA, activations staged through registers, 256 x 256 tiles in 512-thread workgroups, persistent tiles with
 // the next tile's first stages in flight, XCD-aware tile order (the N-tiles of one M-block go to ONE XCD back to back: an A tile
 // is read from HBM once and then from that XCD's L2).  MFMA operand roles: A-operand = activations, B-operand = weights, so a
@@ -58,7 +58,7 @@ __device__ unsigned g_wide_violation = 0u;
 // ------------------------------------------------------------------------------------------------------------------------
 enum { kRelu = 1, kAccum = 2, kMaskEpi = 4 };
 
-#include "nsr_wide_b3.inc"
+#include "nsr_wide_gemm.inc"
 #undef NSRW_FILE_TAG
 #define NSRW_FILE_TAG 0
 
@@ -651,14 +651,26 @@ struct DeviceGuard {
 
 inline int pad32(int x) { return (x + 31) / 32 * 32; }
 
-struct Mat {                 // one packed matrix [Np][K1p + K2p] and its (nullable) bias, as offsets into Net::dW
-  size_t w = 0, b = (size_t)-1;
+// The arithmetic of a GEMM launch: the pieces per operand, gemm_split_body's NP.  A handle has ONE (nsrw_create); a chain of
+// launches runs on one -- an f16x2 handle's on kH2 and then, conditionally, on kB3 (net_forward, net_backward).
+enum Arith { kF32 = 1, kH2 = 2, kB3 = 3 };
+constexpr Arith kAriths[] = {kF32, kH2, kB3};
+constexpr int kArithSlots = 4;                                                    // arrays indexed by an Arith
+constexpr int frag_bytes(Arith a) { return a == kB3 ? 3072 : 2048; }              // one (col-block, k16 block) of a weight image
+constexpr const char* arith_name(Arith a) { return a == kB3 ? "bf16x3" : a == kH2 ? "f16x2" : "fp32"; }
+// the weight images a handle of arithmetic `handle` uploads: its own, and bf16x3 for the re-runs of an f16x2 handle
+constexpr bool has_image(Arith handle, Arith a) { return a == handle || (handle == kH2 && a == kB3); }
+
+// col-blocks of the weight image of a matrix with Np packed rows: Np / 32 rounded up to an even count (the padding holds zero weights)
+inline int col_blocks(int Np) { return ((Np + 31) / 32 + 1) / 2 * 2; }
+
+struct Mat {                 // one packed matrix [Np][K1p + K2p] and its (nullable) bias
+  size_t w = 0;              // offset of the plain fp32 packing in the host vector the images are made from (nsrw_upload_network)
+  size_t b = (size_t)-1;     // offset of the bias in Net::dBias
   int Np = 0, K1p = 0, K2p = 0;
-  size_t wb = 0;             // bf16x3 handles: byte offset of the split image [col-block][k16 block][piece][64][8 bf16] in Net::dWb
-  int ncb = 0;               // ... and its col-blocks (Np / 32 rounded up to an even count; the padding holds zero weights)
-  size_t wh = 0;             // f16x2 handles: byte offset of the two-piece fp16 image (same layout, 2 KiB per block) in Net::dWh
-  float cscale = 1.0f;       // ... and 2^-sw, which undoes the image's weight scale in the epilogue
-  size_t wf = 0;             // fp32 handles: byte offset of the fp32 image [col-block][k16 block][2][64 lanes][4 floats] in Net::dWf
+  int ncb = 0;               // col_blocks(Np)
+  size_t img[kArithSlots] = {};      // per arithmetic: byte offset of the weight image in Net::dImg (pack_image)
+  float cscale = 1.0f;       // 2^-sw, which undoes the f16x2 image's weight scale in the epilogue
 };
 
 struct Net {
@@ -667,18 +679,33 @@ struct Net {
   int in_ch = 0, in_v = 0, Ci = 0, Cv = 0, Wp = 0, W2 = 0, W2p = 0, ldfa = 0, raw_ch = 4;
   int ldraw = 32;                     // row length of the raw outputs: 4 = [r g b sigma] dense (view directions), else 32
   std::vector<char> skip_in;          // skip_in[i]: layer i takes cat[input_pts, h]  (i - 1 in skips)
-  float* dW = nullptr;
-  char* dWb = nullptr;                // bf16x3 handles: the split images of every matrix (nsr_wide_b3.inc)
-  size_t wb_bytes = 0;
-  char* dWh = nullptr;                // f16x2 handles: the scaled two-piece fp16 images of every matrix (kw_gemm_h2)
-  size_t wh_bytes = 0;
-  char* dWf = nullptr;                // fp32 handles: the fp32 images in the same LDS-image layout (kw_gemm_f32)
-  size_t wf_bytes = 0;
+  float* dBias = nullptr;             // device: every bias, padded (all the device reads in fp32 form)
+  char* dImg[kArithSlots] = {};       // device, per arithmetic the handle has an image of: the weight images of every matrix
+  size_t img_bytes[kArithSlots] = {};
   std::vector<Mat> fwd;               // pts_linears
   Mat fa, al, hv, rgb, out;           // feature_linear, alpha_linear, views_linears.0, rgb_linear / output_linear
   std::vector<Mat> bwd_h, bwd_e;      // per pts layer: G W_i[:, hidden part] (i >= 1), G W_i[:, encoding part] (layer 0, skip layers)
   Mat b_rgb, b_feat, b_ed, b_head;
 };
+
+// every matrix of a network (the unused ones have Np == 0)
+template <typename F>
+void for_each_mat(Net& n, F f) {
+  for (Mat& m : n.fwd) f(m);
+  for (Mat& m : n.bwd_h) f(m);
+  for (Mat& m : n.bwd_e) f(m);
+  for (Mat* m : {&n.fa, &n.al, &n.hv, &n.rgb, &n.out, &n.b_rgb, &n.b_feat, &n.b_ed, &n.b_head}) f(*m);
+}
+
+void free_net(Net& n) {      // (the caller has selected the handle's device)
+  if (n.dBias) (void)hipFree(n.dBias);
+  n.dBias = nullptr;
+  for (Arith a : kAriths) {
+    if (n.dImg[a]) (void)hipFree(n.dImg[a]);
+    n.dImg[a] = nullptr;
+  }
+  n.loaded = false;
+}
 
 std::string check_net(const NsrwNet& n) {
   char buf[160];
@@ -711,16 +738,18 @@ size_t net_floats(const NsrwNet& n) {
 
 // How the GEMM kernels are launched: fixed per handle by nsrw_create (a setup call; launch calls read no environment).
 struct GemmCfg {
-  int cus = 256;       // compute units of the handle's device
-  bool b3 = false;     // NSRW_FLAG_MLP_BF16X3: every GEMM on bf16 MFMAs with three-way split operands (kw_gemm_b3)
-  int b3_wm = 4;       // ... 256-column tiles with 256 rows / 512 threads (4) or 128 rows / 256 threads (2: NSRW_B3_WM = 2)
-  // NSRW_FLAG_MLP_F16X2 (b3 is set as well: it is the re-run arithmetic and the backward's).  A forward network pass runs on
-  // kw_gemm_h2 (two fp16 pieces, three products); an activation that leaves fp16's range sets d_range[0], and the same pass
-  // follows on kw_gemm_b3 in launches that return at once unless the flag is set (net_forward).
-  bool h2 = false;
-  unsigned* d_range = nullptr;          // device: [0] flag of the pass in flight, [1] passes run, [2] passes re-run on bf16x3
-  bool use_h2 = false;                  // (per call, net_forward) this chain runs on kw_gemm_h2
-  const unsigned* run_if = nullptr;     // (per call, net_forward) this chain's launches are conditional on *run_if
+  int cus = 256;                        // compute units of the handle's device
+  Arith arith = kF32;                   // NsrwConfig::flags: NSRW_FLAG_MLP_F16X2 -> kH2, NSRW_FLAG_MLP_BF16X3 -> kB3, neither -> kF32
+  int tile_wm = 4;                      // 256-column tiles with 256 rows / 512 threads (4) or 128 rows / 256 threads (2: NSRW_B3_WM = 2)
+  unsigned* d_range = nullptr;          // device: [0] flag of the f16x2 pass in flight, [1] passes run, [2] passes re-run on bf16x3
+};
+
+// One chain of GEMM launches (a network pass): the arithmetic it runs on and, nullable, the device word its launches are conditional
+// on.  An f16x2 pass is the chain {kH2, nullptr} -- an activation that leaves fp16's range sets d_range[0] -- and then the same chain
+// {kB3, d_range}, whose launches return at once unless the flag is set.
+struct Run {
+  Arith arith;
+  const unsigned* run_if;
 };
 
 struct Handle {
@@ -766,80 +795,57 @@ inline float bf16_f(uint16_t h) {
   return f;
 }
 
-// appends the bf16x3 image of the packed fp32 matrix src [Np][Kp] (Kp a multiple of 16): [col-block][k16 block][piece][lane][8],
-// lane l <-> (column 32 cb + l % 32, k = 16 kb + 8 (l / 32) .. + 7): what one LDS-DMA instruction of kw_gemm_b3 moves is one
-// B fragment of v_mfma_f32_32x32x16_bf16.  Returns the byte offset; *ncb = col-blocks, rounded up to an even count.
-size_t pack_b3(std::vector<uint16_t>& imgb, const float* src, int Np, int Kp, int* ncb) {
-  const int cbs = ((Np + 31) / 32 + 1) / 2 * 2, KB = Kp / 16;
-  const size_t off = imgb.size();
-  imgb.resize(off + (size_t)cbs * KB * 3 * 512, 0);
+// Appends the weight image of the packed fp32 matrix src [Np][Kp] (Kp a multiple of 16) for arithmetic `a` and returns its byte offset.
+// Every image is [col-block][k16 block][frag_bytes(a)] over col_blocks(Np) col-blocks (zero weights behind row Np), and within a block
+// lane l <-> (column 32 cb + l % 32, k = 16 kb + 8 (l / 32) + e, e = 0..7): a block IS the LDS image of the B fragments that the
+// kernel's LDS-DMA moves.  The arithmetics differ in what they write for one weight, put(block, l, e, w):
+//   bf16x3  [piece 3][64 lanes][8 bf16]: the three round-to-nearest bf16 pieces, which sum to w exactly;
+//   f16x2   [piece 2][64 lanes][8 fp16]: w 2^sw as two round-to-nearest fp16 pieces -- sw the power of two that puts the matrix's
+//           largest |entry| into [2^14, 2^15), 0 for a zero matrix; *cscale = 2^-sw undoes it in the epilogue;
+//   fp32    [chunk 2][64 lanes][4 floats]: w itself, k = .. + 4 chunk + 0..3.
+template <typename Put>
+size_t pack_blocks(std::vector<char>& img, Arith a, const float* src, int Np, int Kp, Put put) {
+  const int cbs = col_blocks(Np), KB = Kp / 16, fb = frag_bytes(a);
+  const size_t off = img.size();
+  img.resize(off + (size_t)cbs * KB * fb, 0);
   for (int cb = 0; cb < cbs; ++cb)
     for (int kb = 0; kb < KB; ++kb) {
-      uint16_t* blk = imgb.data() + off + ((size_t)cb * KB + kb) * 3 * 512;
+      char* blk = img.data() + off + ((size_t)cb * KB + kb) * fb;
       for (int l = 0; l < 64; ++l) {
         const int n = 32 * cb + (l & 31);
         if (n >= Np) continue;
-        for (int e = 0; e < 8; ++e) {
-          const float w = src[(size_t)n * Kp + 16 * kb + 8 * (l >> 5) + e];
-          const uint16_t p0 = bf16_rn(w);
-          const float r1 = w - bf16_f(p0);
-          const uint16_t p1 = bf16_rn(r1);
-          const uint16_t p2 = bf16_rn(r1 - bf16_f(p1));
-          blk[0 * 512 + l * 8 + e] = p0; blk[1 * 512 + l * 8 + e] = p1; blk[2 * 512 + l * 8 + e] = p2;
-        }
+        for (int e = 0; e < 8; ++e) put(blk, l, e, src[(size_t)n * Kp + 16 * kb + 8 * (l >> 5) + e]);
       }
     }
-  *ncb = cbs;
-  return off * sizeof(uint16_t);
+  return off;
 }
 
-// f16x2: the image of src scaled by 2^sw -- sw the power of two that puts the largest |entry| into [2^14, 2^15), 0 for a zero
-// matrix -- as two round-to-nearest fp16 pieces in pack_b3's layout (2 KiB per (col-block, k16 block)).  *cscale = 2^-sw.
-size_t pack_h2(std::vector<uint16_t>& imgh, const float* src, int Np, int Kp, float* cscale) {
-  const int cbs = ((Np + 31) / 32 + 1) / 2 * 2, KB = Kp / 16;
-  float amax = 0.0f;
-  for (size_t i = 0; i < (size_t)Np * Kp; ++i) if (std::isfinite(src[i])) amax = std::max(amax, std::fabs(src[i]));
-  int sw = 0;
-  if (amax > 0.0f) { int e; (void)std::frexp(amax, &e); sw = 15 - e; }        // amax = f 2^e, f in [0.5, 1): amax 2^sw in [2^14, 2^15)
-  sw = std::max(-100, std::min(100, sw));
-  const float up = std::ldexp(1.0f, sw);
-  *cscale = std::ldexp(1.0f, -sw);
-  const size_t off = imgh.size();
-  imgh.resize(off + (size_t)cbs * KB * 2 * 512, 0);
-  auto bits = [](_Float16 v) { uint16_t u; memcpy(&u, &v, 2); return u; };
-  for (int cb = 0; cb < cbs; ++cb)
-    for (int kb = 0; kb < KB; ++kb) {
-      uint16_t* blk = imgh.data() + off + ((size_t)cb * KB + kb) * 2 * 512;
-      for (int l = 0; l < 64; ++l) {
-        const int n = 32 * cb + (l & 31);
-        if (n >= Np) continue;
-        for (int e = 0; e < 8; ++e) {
-          const float w = src[(size_t)n * Kp + 16 * kb + 8 * (l >> 5) + e] * up;       // exact (a non-finite weight stays non-finite)
-          const _Float16 p0 = (_Float16)w;
-          const _Float16 p1 = (_Float16)(w - (float)p0);
-          blk[0 * 512 + l * 8 + e] = bits(p0); blk[1 * 512 + l * 8 + e] = bits(p1);
-        }
-      }
-    }
-  return off * sizeof(uint16_t);
-}
-
-// fp32 handles: the matrix as it is, in the LDS-image layout of kw_gemm_f32 -- [col-block][k16 block][chunk 2][64 lanes][4 floats],
-// lane l <-> (column 32 cb + l % 32, k = 16 kb + 8 (l / 32) + 4 chunk .. + 3)
-size_t pack_f32img(std::vector<float>& imgf, const float* src, int Np, int Kp) {
-  const int cbs = ((Np + 31) / 32 + 1) / 2 * 2, KB = Kp / 16;
-  const size_t off = imgf.size();
-  imgf.resize(off + (size_t)cbs * KB * 512, 0.0f);
-  for (int cb = 0; cb < cbs; ++cb)
-    for (int kb = 0; kb < KB; ++kb) {
-      float* blk = imgf.data() + off + ((size_t)cb * KB + kb) * 512;
-      for (int l = 0; l < 64; ++l) {
-        const int n = 32 * cb + (l & 31);
-        if (n >= Np) continue;
-        for (int e = 0; e < 8; ++e) blk[(e >> 2) * 256 + l * 4 + (e & 3)] = src[(size_t)n * Kp + 16 * kb + 8 * (l >> 5) + e];
-      }
-    }
-  return off * sizeof(float);
+size_t pack_image(std::vector<char>& img, Arith a, const float* src, int Np, int Kp, float* cscale) {
+  auto put16 = [](char* blk, int piece, int l, int e, const void* v) { memcpy(blk + 2 * (piece * 512 + l * 8 + e), v, 2); };
+  if (a == kB3)
+    return pack_blocks(img, a, src, Np, Kp, [&](char* blk, int l, int e, float w) {
+      const uint16_t p0 = bf16_rn(w);
+      const float r1 = w - bf16_f(p0);
+      const uint16_t p1 = bf16_rn(r1);
+      const uint16_t p2 = bf16_rn(r1 - bf16_f(p1));
+      put16(blk, 0, l, e, &p0); put16(blk, 1, l, e, &p1); put16(blk, 2, l, e, &p2);
+    });
+  if (a == kH2) {
+    float amax = 0.0f;
+    for (size_t i = 0; i < (size_t)Np * Kp; ++i) if (std::isfinite(src[i])) amax = std::max(amax, std::fabs(src[i]));
+    int sw = 0;
+    if (amax > 0.0f) { int e; (void)std::frexp(amax, &e); sw = 15 - e; }        // amax = f 2^e, f in [0.5, 1): amax 2^sw in [2^14, 2^15)
+    sw = std::max(-100, std::min(100, sw));
+    const float up = std::ldexp(1.0f, sw);
+    *cscale = std::ldexp(1.0f, -sw);
+    return pack_blocks(img, a, src, Np, Kp, [&](char* blk, int l, int e, float w0) {
+      const float w = w0 * up;                                                   // exact (a non-finite weight stays non-finite)
+      const _Float16 p0 = (_Float16)w;
+      const _Float16 p1 = (_Float16)(w - (float)p0);
+      put16(blk, 0, l, e, &p0); put16(blk, 1, l, e, &p1);
+    });
+  }
+  return pack_blocks(img, a, src, Np, Kp, [](char* blk, int l, int e, float w) { memcpy(blk + 4 * ((e >> 2) * 256 + l * 4 + (e & 3)), &w, 4); });
 }
 
 // Chunk workspace: the same carve runs with base = nullptr to size it.
@@ -892,91 +898,21 @@ void carve_chunk(const Handle& h, long long R, int grad, Carve& c, Chunk& k) {
   }
 }
 
-template <int NJ, int WM>
-void launch_gemm_b3(hipStream_t st, unsigned grid, const GemmB3Args& g, int epi) {
-  switch (epi) {
-    case kRelu: hipLaunchKernelGGL((kw_gemm_b3<NJ, kRelu, WM>), dim3(grid), dim3(128 * WM), 0, st, g); break;
-    case kMaskEpi: hipLaunchKernelGGL((kw_gemm_b3<NJ, kMaskEpi, WM>), dim3(grid), dim3(128 * WM), 0, st, g); break;
-    case kAccum: hipLaunchKernelGGL((kw_gemm_b3<NJ, kAccum, WM>), dim3(grid), dim3(128 * WM), 0, st, g); break;
-    default: hipLaunchKernelGGL((kw_gemm_b3<NJ, 0, WM>), dim3(grid), dim3(128 * WM), 0, st, g); break;
-  }
-}
-
-template <int NJ, int WM>
-void launch_gemm_h2(hipStream_t st, unsigned grid, const GemmB3Args& g, int epi) {
-  switch (epi) {
-    case kRelu: hipLaunchKernelGGL((kw_gemm_h2<NJ, kRelu, WM>), dim3(grid), dim3(128 * WM), 0, st, g); break;
-    case kMaskEpi: hipLaunchKernelGGL((kw_gemm_h2<NJ, kMaskEpi, WM>), dim3(grid), dim3(128 * WM), 0, st, g); break;
-    case kAccum: hipLaunchKernelGGL((kw_gemm_h2<NJ, kAccum, WM>), dim3(grid), dim3(128 * WM), 0, st, g); break;
-    default: hipLaunchKernelGGL((kw_gemm_h2<NJ, 0, WM>), dim3(grid), dim3(128 * WM), 0, st, g); break;
-  }
-}
-
-template <int NJ, int WM>
-void launch_gemm_f32(hipStream_t st, unsigned grid, const GemmB3Args& g, int epi) {
-  switch (epi) {
-    case kRelu: hipLaunchKernelGGL((kw_gemm_f32<NJ, kRelu, WM>), dim3(grid), dim3(128 * WM), 0, st, g); break;
-    case kMaskEpi: hipLaunchKernelGGL((kw_gemm_f32<NJ, kMaskEpi, WM>), dim3(grid), dim3(128 * WM), 0, st, g); break;
-    case kAccum: hipLaunchKernelGGL((kw_gemm_f32<NJ, kAccum, WM>), dim3(grid), dim3(128 * WM), 0, st, g); break;
-    default: hipLaunchKernelGGL((kw_gemm_f32<NJ, 0, WM>), dim3(grid), dim3(128 * WM), 0, st, g); break;
-  }
-}
-
-// bf16x3 handles: the N extent is cut into tiles of 256 columns, then one of 128 and one of 64 for what is left (the image is
-// padded to an even number of 32-column blocks with zero weights; columns >= N are never stored)
-int gemm_b3(const GemmCfg& cfg, hipStream_t st, const Net& net, const Mat& m, const float* bias, const float* A1, int lda1,
-            const float* A2, int lda2, float* C, int ldc, int N, long long M, int epi, const float* mask, int ldm) {
-  GemmB3Args g{};
-  g.A1 = A1; g.A2 = m.K2p ? A2 : nullptr; g.lda1 = lda1; g.lda2 = lda2; g.K1 = m.K1p; g.K2 = m.K2p;
-  g.M = M; g.ldc = ldc; g.ldm = ldm;
-  const bool h2 = cfg.use_h2, f32 = !cfg.b3;
-  const int kfrag = (h2 || f32) ? 2048 : 3072;                      // bytes of one (col-block, k16 block) of the image
-  g.cscale = h2 ? m.cscale : 1.0f; g.range_flag = cfg.d_range; g.run_if = cfg.run_if;
-  const int KB = (m.K1p + m.K2p) / 16;
-  int cb = 0;
+// The launch plan of one GEMM -- pure host arithmetic, no HIP call (nsrw_gemm_plan exposes it).  The N extent of a matrix whose image
+// has ncb col-blocks, in units of 64 columns: tiles of 256 where they divide it; else tiles of 192 where THEY do (r06: 384 = 2 x 192 and
+// 192 itself are ONE launch -- as 256 + 128 resp. 128 + 64 the second launch read the whole A matrix from HBM again); else 256s and one
+// remainder tile of 192, or of 128 and / or 64.  The 192-column form exists with 256-row tiles only (tile_wm == 4); a 64-column
+// remainder keeps 128 rows.  The image is padded to an even number of col-blocks with zero weights and columns >= N are never
+// stored: a part that starts at or behind column N is not launched.  Returns the number of parts (<= kMaxGemmParts).
+constexpr int kMaxGemmParts = 3;
+int gemm_plan(int ncb, int N, int tile_wm, NsrwGemmPart* parts) {
+  int count = 0, cb = 0;
   auto part = [&](int nj, int tiles) {
-    // 256-row tiles (one 512-thread workgroup per CU) for the 256-column tiles; the narrow remainders keep 128 rows
-    const bool tall = nj >= 2 && cfg.b3_wm == 4;
-    const int tm = tall ? 256 : 128;
-    const long long mblocks = (M + tm - 1) / tm, mgroups = (mblocks + 7) / 8;
-    GemmB3Args t = g;
-    const size_t boff = (size_t)cb * KB * kfrag;
-    t.Wb = (h2 ? net.dWh + m.wh : f32 ? net.dWf + m.wf : net.dWb + m.wb) + boff;
-    t.wb_bytes = (unsigned)((size_t)m.ncb * KB * kfrag - boff);
-    t.bias = bias ? bias + cb * 32 : nullptr;
-    t.C = C + cb * 32; t.N = N - cb * 32;
-    t.mask = mask ? mask + cb * 32 : nullptr;
-    t.n_tiles = tiles;
-    if (t.N > 0) {
-      const long long all = mgroups * 8 * tiles;
-      const int per_cu = tall ? (nj >= 3 ? 1 : 2) : nj == 4 ? 2 : nj == 2 ? 3 : 4;
-      const unsigned grid = (unsigned)std::max<long long>(8, std::min<long long>(all, (long long)cfg.cus * per_cu / 8 * 8));
-      if (f32) {
-        if (tall && nj == 4) launch_gemm_f32<4, 4>(st, grid, t, epi);
-        else if (tall && nj == 3) launch_gemm_f32<3, 4>(st, grid, t, epi);
-        else if (tall) launch_gemm_f32<2, 4>(st, grid, t, epi);
-        else if (nj == 4) launch_gemm_f32<4, 2>(st, grid, t, epi);
-        else if (nj == 2) launch_gemm_f32<2, 2>(st, grid, t, epi);
-        else launch_gemm_f32<1, 2>(st, grid, t, epi);
-      } else if (h2) {
-        if (tall && nj == 4) launch_gemm_h2<4, 4>(st, grid, t, epi);
-        else if (tall && nj == 3) launch_gemm_h2<3, 4>(st, grid, t, epi);
-        else if (tall) launch_gemm_h2<2, 4>(st, grid, t, epi);
-        else if (nj == 4) launch_gemm_h2<4, 2>(st, grid, t, epi);
-        else if (nj == 2) launch_gemm_h2<2, 2>(st, grid, t, epi);
-        else launch_gemm_h2<1, 2>(st, grid, t, epi);
-      } else if (tall && nj == 4) launch_gemm_b3<4, 4>(st, grid, t, epi);
-      else if (tall && nj == 3) launch_gemm_b3<3, 4>(st, grid, t, epi);
-      else if (tall) launch_gemm_b3<2, 4>(st, grid, t, epi);
-      else if (nj == 4) launch_gemm_b3<4, 2>(st, grid, t, epi);
-      else if (nj == 2) launch_gemm_b3<2, 2>(st, grid, t, epi);
-      else launch_gemm_b3<1, 2>(st, grid, t, epi);
-    }
+    if (N - cb * 32 > 0) parts[count++] = NsrwGemmPart{nj, (nj >= 2 && tile_wm == 4) ? 4 : 2, tiles, cb};
     cb += tiles * nj * 2;
   };
-  // N in units of 64 columns: tiles of 256 where they divide it; else tiles of 192 where THEY do (r06: 384 = 2 x 192 and 192 itself are ONE
-  // launch -- as 256 + 128 resp. 128 + 64 the second launch read the whole A matrix from HBM again); else 256s and one remainder tile
-  const int u = m.ncb / 2, three = cfg.b3_wm == 4;
+  const int u = ncb / 2;
+  const bool three = tile_wm == 4;
   if (u % 4 != 0 && u % 3 == 0 && three) {
     part(3, u / 3);
   } else {
@@ -988,41 +924,104 @@ int gemm_b3(const GemmCfg& cfg, hipStream_t st, const Net& net, const Mat& m, co
       if (r & 1) part(1, 1);
     }
   }
-  return 0;
+  return count;
 }
 
-int gemm(const GemmCfg& cfg, hipStream_t st, const Net& net, const Mat& m, const float* A1, int lda1, const float* A2, int lda2,
-         float* C, int ldc, int N, long long M, int flags, const float* mask = nullptr, int ldm = 0, bool with_bias = true) {
+// The 72 GEMM kernels, by (arithmetic, tile form <NJ, WM>, epilogue): the forms below are the ones gemm_plan produces.
+typedef void (*GemmKernel)(GemmArgs);
+struct GemmForm {
+  int nj, wm, wgs_per_cu;               // wgs_per_cu: the kernel's own __launch_bounds__ figure
+  GemmKernel epi[5];                    // indexed by the epilogue: 0, kRelu, kAccum, (3: none), kMaskEpi
+};
+template <int NP, int NJ, int EPI, int WM>
+GemmKernel gemm_kernel() {
+  if constexpr (NP == kB3) return kw_gemm_b3<NJ, EPI, WM>;
+  else if constexpr (NP == kH2) return kw_gemm_h2<NJ, EPI, WM>;
+  else return kw_gemm_f32<NJ, EPI, WM>;
+}
+template <int NP, int NJ, int WM>
+GemmForm gemm_form() {
+  GemmForm f{NJ, WM, wgs_per_cu<NJ, WM>(), {}};
+  // (in this order, and f32 / h2 / b3 in find_form: the order of instantiation is the order of the kernels in the code object)
+  f.epi[kRelu] = gemm_kernel<NP, NJ, kRelu, WM>();
+  f.epi[kMaskEpi] = gemm_kernel<NP, NJ, kMaskEpi, WM>();
+  f.epi[kAccum] = gemm_kernel<NP, NJ, kAccum, WM>();
+  f.epi[0] = gemm_kernel<NP, NJ, 0, WM>();
+  return f;
+}
+constexpr int kGemmForms = 6;
+template <int NP>
+const GemmForm* gemm_forms() {
+  static const GemmForm forms[kGemmForms] = {gemm_form<NP, 4, 4>(), gemm_form<NP, 3, 4>(), gemm_form<NP, 2, 4>(),
+                                             gemm_form<NP, 4, 2>(), gemm_form<NP, 2, 2>(), gemm_form<NP, 1, 2>()};
+  return forms;
+}
+const GemmForm* find_form(Arith a, int nj, int wm) {
+  const GemmForm* forms = a == kF32 ? gemm_forms<kF32>() : a == kH2 ? gemm_forms<kH2>() : gemm_forms<kB3>();
+  for (int i = 0; i < kGemmForms; ++i)
+    if (forms[i].nj == nj && forms[i].wm == wm) return &forms[i];
+  return nullptr;
+}
+
+// C = epi(A W^T + bias) for one matrix of `net` on the arithmetic of `run`: one launch per part of the plan
+int gemm(const GemmCfg& cfg, Run run, hipStream_t st, const Net& net, const Mat& m, const float* A1, int lda1, const float* A2, int lda2,
+         float* C, int ldc, int N, long long M, int flags, const float* mask = nullptr, int ldm = 0) {
   if (M <= 0) return 0;
   const int epi = mask ? kMaskEpi : (flags & kAccum) ? kAccum : (flags & kRelu) ? kRelu : 0;     // (never combined: net_*)
-  return gemm_b3(cfg, st, net, m, (with_bias && m.b != (size_t)-1) ? net.dW + m.b : nullptr, A1, lda1, A2, lda2, C, ldc, N, M, epi, mask, ldm);
+  const float* bias = m.b != (size_t)-1 ? net.dBias + m.b : nullptr;
+  GemmArgs g{};
+  g.A1 = A1; g.A2 = m.K2p ? A2 : nullptr; g.lda1 = lda1; g.lda2 = lda2; g.K1 = m.K1p; g.K2 = m.K2p;
+  g.M = M; g.ldc = ldc; g.ldm = ldm;
+  g.cscale = run.arith == kH2 ? m.cscale : 1.0f; g.range_flag = cfg.d_range; g.run_if = run.run_if;
+  const int kfrag = frag_bytes(run.arith), KB = (m.K1p + m.K2p) / 16;
+  NsrwGemmPart parts[kMaxGemmParts];
+  const int n_parts = gemm_plan(m.ncb, N, cfg.tile_wm, parts);
+  for (int i = 0; i < n_parts; ++i) {
+    const NsrwGemmPart& p = parts[i];
+    const GemmForm* form = find_form(run.arith, p.nj, p.wm);
+    if (!form) return fail("nsrw: internal error: the launch plan names a tile form that is not compiled");
+    const int tm = 64 * p.wm, cb = p.col_block;
+    const long long mblocks = (M + tm - 1) / tm, mgroups = (mblocks + 7) / 8;
+    GemmArgs t = g;
+    const size_t boff = (size_t)cb * KB * kfrag;
+    t.Wb = net.dImg[run.arith] + m.img[run.arith] + boff;
+    t.wb_bytes = (unsigned)((size_t)m.ncb * KB * kfrag - boff);
+    t.bias = bias ? bias + cb * 32 : nullptr;
+    t.C = C + cb * 32; t.N = N - cb * 32;
+    t.mask = mask ? mask + cb * 32 : nullptr;
+    t.n_tiles = p.tiles;
+    const long long all = mgroups * 8 * p.tiles;
+    const unsigned grid = (unsigned)std::max<long long>(8, std::min<long long>(all, (long long)cfg.cus * form->wgs_per_cu / 8 * 8));
+    hipLaunchKernelGGL(form->epi[epi], dim3(grid), dim3(128 * p.wm), 0, st, t);
+  }
+  return 0;
 }
 
 // RH:99-122 over P points whose encodings are in k.E / k.ED: leaves the rgb logits in k.RAW (ld 32; all output_linear rows
 // without view directions) and the density at sigma / ld_sigma.  keep: every pts layer's activation stays (k.H[i]).
-int net_forward_chain(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P, bool keep, const float** sigma,
+int net_forward_chain(const GemmCfg& cfg, Run run, hipStream_t st, const Net& n, const Chunk& k, long long P, bool keep, const float** sigma,
                       int* ld_sigma) {
   const float* h = nullptr;
   for (int i = 0; i < n.d.D; ++i) {
     float* out = k.H[keep ? i : (i & 1)];
     int rc;
-    if (i == 0) rc = gemm(cfg, st, n, n.fwd[0], k.E, n.Ci, nullptr, 0, out, n.Wp, n.Wp, P, kRelu);
-    else if (n.skip_in[i]) rc = gemm(cfg, st, n, n.fwd[i], k.E, n.Ci, h, n.Wp, out, n.Wp, n.Wp, P, kRelu);
-    else rc = gemm(cfg, st, n, n.fwd[i], h, n.Wp, nullptr, 0, out, n.Wp, n.Wp, P, kRelu);
+    if (i == 0) rc = gemm(cfg, run, st, n, n.fwd[0], k.E, n.Ci, nullptr, 0, out, n.Wp, n.Wp, P, kRelu);
+    else if (n.skip_in[i]) rc = gemm(cfg, run, st, n, n.fwd[i], k.E, n.Ci, h, n.Wp, out, n.Wp, n.Wp, P, kRelu);
+    else rc = gemm(cfg, run, st, n, n.fwd[i], h, n.Wp, nullptr, 0, out, n.Wp, n.Wp, P, kRelu);
     if (rc) return rc;
     h = out;
   }
   if (!n.d.use_viewdirs) {
-    if (gemm(cfg, st, n, n.out, h, n.Wp, nullptr, 0, k.RAW, 32, n.d.output_ch, P, 0)) return 1;
+    if (gemm(cfg, run, st, n, n.out, h, n.Wp, nullptr, 0, k.RAW, 32, n.d.output_ch, P, 0)) return 1;
     *sigma = k.RAW + 3; *ld_sigma = 32;
     return 0;
   }
   // the raw outputs of a point are FOUR dense floats [r g b sigma] (r06: rows of 32 with 3 + 1 useful values made every per-ray
   // kernel fetch two 128-byte lines per point): alpha_linear writes column 3, rgb_linear columns 0..2
-  if (gemm(cfg, st, n, n.fa, h, n.Wp, nullptr, 0, k.FA, n.ldfa, n.ldfa, P, 0)) return 1;
-  if (gemm(cfg, st, n, n.al, h, n.Wp, nullptr, 0, k.RAW + 3, n.ldraw, 1, P, 0)) return 1;
-  if (gemm(cfg, st, n, n.hv, k.FA, n.ldfa, k.ED, n.Cv, k.HV, n.W2p, n.W2p, P, kRelu)) return 1;
-  if (gemm(cfg, st, n, n.rgb, k.HV, n.W2p, nullptr, 0, k.RAW, n.ldraw, 3, P, 0)) return 1;
+  if (gemm(cfg, run, st, n, n.fa, h, n.Wp, nullptr, 0, k.FA, n.ldfa, n.ldfa, P, 0)) return 1;
+  if (gemm(cfg, run, st, n, n.al, h, n.Wp, nullptr, 0, k.RAW + 3, n.ldraw, 1, P, 0)) return 1;
+  if (gemm(cfg, run, st, n, n.hv, k.FA, n.ldfa, k.ED, n.Cv, k.HV, n.W2p, n.W2p, P, kRelu)) return 1;
+  if (gemm(cfg, run, st, n, n.rgb, k.HV, n.W2p, nullptr, 0, k.RAW, n.ldraw, 3, P, 0)) return 1;
   *sigma = k.RAW + 3; *ld_sigma = n.ldraw;
   return 0;
 }
@@ -1037,39 +1036,36 @@ __global__ void kw_range_tally(unsigned* r) {
 
 int net_forward(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P, bool keep, const float** sigma,
                 int* ld_sigma) {
-  if (!cfg.h2 || P <= 0) return net_forward_chain(cfg, st, n, k, P, keep, sigma, ld_sigma);
+  if (cfg.arith != kH2 || P <= 0) return net_forward_chain(cfg, Run{cfg.arith, nullptr}, st, n, k, P, keep, sigma, ld_sigma);
   // f16x2: the pass on fp16 MFMAs; then the same pass on bf16x3 in launches that are empty unless an activation left fp16's
   // range (its inputs -- the encodings -- are untouched, every buffer it writes is written again); then the tally
-  GemmCfg c = cfg;
-  c.use_h2 = true;
-  if (net_forward_chain(c, st, n, k, P, keep, sigma, ld_sigma)) return 1;
-  c.use_h2 = false; c.run_if = cfg.d_range;
-  if (net_forward_chain(c, st, n, k, P, keep, sigma, ld_sigma)) return 1;
+  if (net_forward_chain(cfg, Run{kH2, nullptr}, st, n, k, P, keep, sigma, ld_sigma)) return 1;
+  if (net_forward_chain(cfg, Run{kB3, cfg.d_range}, st, n, k, P, keep, sigma, ld_sigma)) return 1;
   hipLaunchKernelGGL(kw_range_tally, dim3(1), dim3(64), 0, st, cfg.d_range);
   return 0;
 }
 
 // Input-side backward of net_forward (activations kept): k.DRAW [P,32] = dL/d(rgb logits, sigma) -> k.GEP [P,Ci], k.GED [P,Cv].
-int net_backward_chain(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P) {
+int net_backward_chain(const GemmCfg& cfg, Run run, hipStream_t st, const Net& n, const Chunk& k, long long P) {
   float* g = k.G0;
   float* g2 = k.G1;
   const int D = n.d.D;
   if (n.d.use_viewdirs) {
-    if (gemm(cfg, st, n, n.b_rgb, k.DRAW, 32, nullptr, 0, k.GV, n.W2p, n.W2p, P, 0, k.HV, n.W2p)) return 1;   // (g W_rgb) relu'(views)
-    if (gemm(cfg, st, n, n.b_feat, k.GV, n.W2p, nullptr, 0, g2, n.Wp, n.Wp, P, 0)) return 1;                  // dL/d feature
-    if (gemm(cfg, st, n, n.b_ed, k.GV, n.W2p, nullptr, 0, k.GED, n.Cv, n.Cv, P, 0)) return 1;                 // dL/d direction encoding
-    if (gemm(cfg, st, n, n.b_head, g2, n.Wp, k.DRAW, 32, g, n.Wp, n.Wp, P, 0, k.H[D - 1], n.Wp)) return 1;    // feature, alpha -> h_{D-1}
+    if (gemm(cfg, run, st, n, n.b_rgb, k.DRAW, 32, nullptr, 0, k.GV, n.W2p, n.W2p, P, 0, k.HV, n.W2p)) return 1;   // (g W_rgb) relu'(views)
+    if (gemm(cfg, run, st, n, n.b_feat, k.GV, n.W2p, nullptr, 0, g2, n.Wp, n.Wp, P, 0)) return 1;                  // dL/d feature
+    if (gemm(cfg, run, st, n, n.b_ed, k.GV, n.W2p, nullptr, 0, k.GED, n.Cv, n.Cv, P, 0)) return 1;                 // dL/d direction encoding
+    if (gemm(cfg, run, st, n, n.b_head, g2, n.Wp, k.DRAW, 32, g, n.Wp, n.Wp, P, 0, k.H[D - 1], n.Wp)) return 1;    // feature, alpha -> h_{D-1}
   } else {
-    if (gemm(cfg, st, n, n.b_head, k.DRAW, 32, nullptr, 0, g, n.Wp, n.Wp, P, 0, k.H[D - 1], n.Wp)) return 1;
+    if (gemm(cfg, run, st, n, n.b_head, k.DRAW, 32, nullptr, 0, g, n.Wp, n.Wp, P, 0, k.H[D - 1], n.Wp)) return 1;
   }
   bool first_e = true;
   for (int i = D - 1; i >= 0; --i) {          // g = dL/d pre-activation of layer i
     if (i == 0 || n.skip_in[i]) {
-      if (gemm(cfg, st, n, n.bwd_e[i], g, n.Wp, nullptr, 0, k.GEP, n.Ci, n.Ci, P, first_e ? 0 : kAccum)) return 1;
+      if (gemm(cfg, run, st, n, n.bwd_e[i], g, n.Wp, nullptr, 0, k.GEP, n.Ci, n.Ci, P, first_e ? 0 : kAccum)) return 1;
       first_e = false;
     }
     if (i > 0) {
-      if (gemm(cfg, st, n, n.bwd_h[i], g, n.Wp, nullptr, 0, g2, n.Wp, n.Wp, P, 0, k.H[i - 1], n.Wp)) return 1;
+      if (gemm(cfg, run, st, n, n.bwd_h[i], g, n.Wp, nullptr, 0, g2, n.Wp, n.Wp, P, 0, k.H[i - 1], n.Wp)) return 1;
       std::swap(g, g2);
     }
   }
@@ -1080,12 +1076,9 @@ int net_backward_chain(const GemmCfg& cfg, hipStream_t st, const Net& n, const C
 // unless a gradient left fp16's range -- once more on bf16x3 from the same inputs (k.DRAW and the stored activations are read
 // only; the first write of k.GEP does not accumulate), then the tally
 int net_backward(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P) {
-  if (!cfg.h2 || P <= 0) return net_backward_chain(cfg, st, n, k, P);
-  GemmCfg c = cfg;
-  c.use_h2 = true;
-  if (net_backward_chain(c, st, n, k, P)) return 1;
-  c.use_h2 = false; c.run_if = cfg.d_range;
-  if (net_backward_chain(c, st, n, k, P)) return 1;
+  if (cfg.arith != kH2 || P <= 0) return net_backward_chain(cfg, Run{cfg.arith, nullptr}, st, n, k, P);
+  if (net_backward_chain(cfg, Run{kH2, nullptr}, st, n, k, P)) return 1;
+  if (net_backward_chain(cfg, Run{kB3, cfg.d_range}, st, n, k, P)) return 1;
   hipLaunchKernelGGL(kw_range_tally, dim3(1), dim3(64), 0, st, cfg.d_range);
   return 0;
 }
@@ -1233,7 +1226,7 @@ int render_impl(Handle* h, const float* ro, const float* rd, long long n, float 
       cb.z = z; cb.nrm = k.nrm; cb.noise = noise; cb.draw = k.DRAW; cb.gnorm = k.gnorm;
       cb.grad_rgb = g_rgb ? g_rgb + r0 * 3 : nullptr; cb.grad_disp = g_disp ? g_disp + r0 : nullptr;
       cb.grad_acc = g_acc ? g_acc + r0 : nullptr;
-      cb.scr_a = k.scr_a; cb.scr_t = k.scr_t; cb.gscale = h->gemm_cfg.h2 ? k.gscale : nullptr;
+      cb.scr_a = k.scr_a; cb.scr_t = k.scr_t; cb.gscale = h->gemm_cfg.arith == kH2 ? k.gscale : nullptr;
       hipLaunchKernelGGL(kw_composite_bwd, dim3(rb), dim3(256), 0, st, cb);
       if (net_backward(h->gemm_cfg, st, nn, k, P)) return 1;
       EmbedBwdArgs eb{};
@@ -1294,9 +1287,8 @@ int nsrw_create(const NsrwConfig* cfg, nsrw_handle* out) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess && prop.multiProcessorCount > 0) gc.cus = prop.multiProcessorCount;
   }
-  gc.h2 = (cfg->flags & NSRW_FLAG_MLP_F16X2) != 0;
-  gc.b3 = gc.h2 || (cfg->flags & NSRW_FLAG_MLP_BF16X3) != 0;
-  if (const char* wm = getenv("NSRW_B3_WM")) gc.b3_wm = atoi(wm) == 2 ? 2 : 4;
+  gc.arith = (cfg->flags & NSRW_FLAG_MLP_F16X2) ? kH2 : (cfg->flags & NSRW_FLAG_MLP_BF16X3) ? kB3 : kF32;
+  if (const char* wm = getenv("NSRW_B3_WM")) gc.tile_wm = atoi(wm) == 2 ? 2 : 4;
   Handle* h = new Handle();
   h->cfg = *cfg;
   h->gemm_cfg = gc;
@@ -1332,12 +1324,7 @@ int nsrw_destroy(nsrw_handle hh) {
   Handle* h = reinterpret_cast<Handle*>(hh);
   if (!h) return 0;
   DeviceGuard guard(h->cfg.device);
-  for (Net& n : h->net) {
-    if (n.dW) (void)hipFree(n.dW);
-    if (n.dWb) (void)hipFree(n.dWb);
-    if (n.dWh) (void)hipFree(n.dWh);
-    if (n.dWf) (void)hipFree(n.dWf);
-  }
+  for (Net& n : h->net) free_net(n);
   if (h->d_tab) (void)hipFree(h->d_tab);
   if (h->d_range) (void)hipFree(h->d_range);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1395,7 +1382,7 @@ int nsrw_upload_network(nsrw_handle hh, int net_id, const NsrwNet* desc, const f
   } else {
     Wo = p; p += (size_t)desc->output_ch * W; Bo = p; p += desc->output_ch;
   }
-  std::vector<float> img;
+  std::vector<float> img, bias;        // the plain fp32 packing of every matrix (host only: input of the images) and the biases
   n.fwd.resize(D); n.bwd_h.resize(D); n.bwd_e.resize(D);
   const int in_ch = n.in_ch, Ci = n.Ci, Wp = n.Wp;
   for (int i = 0; i < D; ++i) {
@@ -1418,7 +1405,7 @@ int nsrw_upload_network(nsrw_handle hh, int net_id, const NsrwNet* desc, const f
       m.K1p = Wp;
       m.w = pack(img, Wp, Wp, [&](int nn, int kk) { return (nn < W && kk < W) ? w[(size_t)nn * K + kk] : 0.0f; });
     }
-    m.b = pack_bias(img, Wp, Bl[i], W);
+    m.b = pack_bias(bias, Wp, Bl[i], W);
     // transposed pieces for the backward: out[n'] = sum_k g[k] W_i[k][col(n')]
     const int hoff = (i > 0 && n.skip_in[i]) ? in_ch : 0;
     if (i > 0) {
@@ -1437,10 +1424,10 @@ int nsrw_upload_network(nsrw_handle hh, int net_id, const NsrwNet* desc, const f
     // feature_linear, and alpha_linear as a matrix of its own (row 0; its one output column goes to the raw block, net_forward)
     n.fa.Np = Wp; n.fa.K1p = Wp;
     n.fa.w = pack(img, Wp, Wp, [&](int nn, int kk) { return (nn < W && kk < W) ? Wf[(size_t)nn * W + kk] : 0.0f; });
-    n.fa.b = pack_bias(img, Wp, Bf, W);
+    n.fa.b = pack_bias(bias, Wp, Bf, W);
     n.al.Np = 32; n.al.K1p = Wp;
     n.al.w = pack(img, 32, Wp, [&](int nn, int kk) { return (nn == 0 && kk < W) ? Wa[kk] : 0.0f; });
-    n.al.b = pack_bias(img, 32, Ba, 1);
+    n.al.b = pack_bias(bias, 32, Ba, 1);
     // views_linears.0 on cat[feature, input_views] (RH:113): A1 = FA's feature columns, A2 = direction encoding
     n.hv.Np = W2p; n.hv.K1p = Wp; n.hv.K2p = Cv;
     n.hv.w = pack(img, W2p, Wp + Cv, [&](int nn, int kk) {
@@ -1449,10 +1436,10 @@ int nsrw_upload_network(nsrw_handle hh, int net_id, const NsrwNet* desc, const f
       const int c = kk - Wp;
       return c < in_v ? Wv[(size_t)nn * Kv + W + c] : 0.0f;
     });
-    n.hv.b = pack_bias(img, W2p, Bv, W2);
+    n.hv.b = pack_bias(bias, W2p, Bv, W2);
     n.rgb.Np = 32; n.rgb.K1p = W2p;
     n.rgb.w = pack(img, 32, W2p, [&](int nn, int kk) { return (nn < 3 && kk < W2) ? Wr[(size_t)nn * W2 + kk] : 0.0f; });
-    n.rgb.b = pack_bias(img, 32, Br, 3);
+    n.rgb.b = pack_bias(bias, 32, Br, 3);
     // backward heads
     n.b_rgb.Np = W2p; n.b_rgb.K1p = 32;
     n.b_rgb.w = pack(img, W2p, 32, [&](int nn, int kk) { return (nn < W2 && kk < 3) ? Wr[(size_t)kk * W2 + nn] : 0.0f; });
@@ -1470,81 +1457,38 @@ int nsrw_upload_network(nsrw_handle hh, int net_id, const NsrwNet* desc, const f
     const int oc = desc->output_ch;
     n.out.Np = 32; n.out.K1p = Wp;
     n.out.w = pack(img, 32, Wp, [&](int nn, int kk) { return (nn < oc && kk < W) ? Wo[(size_t)nn * W + kk] : 0.0f; });
-    n.out.b = pack_bias(img, 32, Bo, oc);
+    n.out.b = pack_bias(bias, 32, Bo, oc);
     n.b_head.Np = Wp; n.b_head.K1p = 32;                            // render_rays reads rows 0..3 of output_linear (RN:363-374)
     n.b_head.w = pack(img, Wp, 32, [&](int nn, int kk) { return (nn < W && kk < 4) ? Wo[(size_t)kk * W + nn] : 0.0f; });
   }
-  // bf16x3 handles: every matrix once more as three bf16 pieces in the layout kw_gemm_b3's LDS-DMA reads (6 bytes per weight)
-  std::vector<uint16_t> imgb;
-  if (h->gemm_cfg.b3) {
-    std::vector<Mat*> all;
-    for (Mat& m : n.fwd) all.push_back(&m);
-    for (Mat& m : n.bwd_h) all.push_back(&m);
-    for (Mat& m : n.bwd_e) all.push_back(&m);
-    for (Mat* m : {&n.fa, &n.al, &n.hv, &n.rgb, &n.out, &n.b_rgb, &n.b_feat, &n.b_ed, &n.b_head}) all.push_back(m);
-    for (Mat* m : all)
-      if (m->Np > 0) m->wb = pack_b3(imgb, img.data() + m->w, m->Np, m->K1p + m->K2p, &m->ncb);
-    if (imgb.size() * sizeof(uint16_t) >= 0x7fffffffull) return fail("nsrw_upload_network: network too large for the bf16x3 image");
-  }
-  // f16x2 handles: ... and as scaled two-piece fp16 images (4 bytes per weight) for kw_gemm_h2
-  std::vector<uint16_t> imgh;
-  if (h->gemm_cfg.h2) {
-    std::vector<Mat*> all;
-    for (Mat& m : n.fwd) all.push_back(&m);
-    for (Mat& m : n.bwd_h) all.push_back(&m);
-    for (Mat& m : n.bwd_e) all.push_back(&m);
-    for (Mat* m : {&n.fa, &n.al, &n.hv, &n.rgb, &n.out, &n.b_rgb, &n.b_feat, &n.b_ed, &n.b_head}) all.push_back(m);
-    for (Mat* m : all)
-      if (m->Np > 0) m->wh = pack_h2(imgh, img.data() + m->w, m->Np, m->K1p + m->K2p, &m->cscale);
-    if (imgh.size() * sizeof(uint16_t) >= 0x7fffffffull) return fail("nsrw_upload_network: network too large for the f16x2 image");
-  }
-  // fp32 handles: the matrices in the LDS-image layout of kw_gemm_f32 (4 bytes per weight; dW keeps the biases)
-  std::vector<float> imgf;
-  if (!h->gemm_cfg.b3) {
-    std::vector<Mat*> all;
-    for (Mat& m : n.fwd) all.push_back(&m);
-    for (Mat& m : n.bwd_h) all.push_back(&m);
-    for (Mat& m : n.bwd_e) all.push_back(&m);
-    for (Mat* m : {&n.fa, &n.al, &n.hv, &n.rgb, &n.out, &n.b_rgb, &n.b_feat, &n.b_ed, &n.b_head}) all.push_back(m);
-    for (Mat* m : all)
-      if (m->Np > 0) {
-        m->wf = pack_f32img(imgf, img.data() + m->w, m->Np, m->K1p + m->K2p);
-        m->ncb = ((m->Np + 31) / 32 + 1) / 2 * 2;
-      }
-    if (imgf.size() * sizeof(float) >= 0x7fffffffull) return fail("nsrw_upload_network: network too large for the fp32 image");
+  // the weight images: per arithmetic the handle launches, every matrix in the layout that arithmetic's kernel moves into LDS
+  std::vector<char> image[kArithSlots];
+  for (Arith a : kAriths) {
+    if (!has_image(h->gemm_cfg.arith, a)) continue;
+    for_each_mat(n, [&](Mat& m) {
+      if (m.Np <= 0) return;
+      m.ncb = col_blocks(m.Np);
+      m.img[a] = pack_image(image[a], a, img.data() + m.w, m.Np, m.K1p + m.K2p, &m.cscale);
+    });
+    if (image[a].size() >= 0x7fffffffull) return fail(std::string("nsrw_upload_network: network too large for the ") + arith_name(a) + " image");
   }
   NSRW_DEVICE(h);
   // (every failure path below frees what this call allocated: ADVICE r05)
-  hipError_t e = hipMalloc(&n.dW, img.size() * sizeof(float));
-  if (e == hipSuccess) e = hipMemcpy(n.dW, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess && !imgb.empty()) {
-    n.wb_bytes = imgb.size() * sizeof(uint16_t);
-    e = hipMalloc(&n.dWb, n.wb_bytes);
-    if (e == hipSuccess) e = hipMemcpy(n.dWb, imgb.data(), n.wb_bytes, hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess && !imgh.empty()) {
-    n.wh_bytes = imgh.size() * sizeof(uint16_t);
-    e = hipMalloc(&n.dWh, n.wh_bytes);
-    if (e == hipSuccess) e = hipMemcpy(n.dWh, imgh.data(), n.wh_bytes, hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess && !imgf.empty()) {
-    n.wf_bytes = imgf.size() * sizeof(float);
-    e = hipMalloc(&n.dWf, n.wf_bytes);
-    if (e == hipSuccess) e = hipMemcpy(n.dWf, imgf.data(), n.wf_bytes, hipMemcpyHostToDevice);
+  hipError_t e = hipMalloc(&n.dBias, bias.size() * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(n.dBias, bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice);
+  for (Arith a : kAriths) {
+    if (e != hipSuccess || image[a].empty()) continue;
+    n.img_bytes[a] = image[a].size();
+    e = hipMalloc(&n.dImg[a], n.img_bytes[a]);
+    if (e == hipSuccess) e = hipMemcpy(n.dImg[a], image[a].data(), n.img_bytes[a], hipMemcpyHostToDevice);
   }
   Net& slot = h->net[net_id];
-  if (e == hipSuccess && (slot.dW || slot.dWb)) e = hipDeviceSynchronize();      // a launch may still read the images being replaced
+  if (e == hipSuccess && slot.loaded) e = hipDeviceSynchronize();      // a launch may still read the images being replaced
   if (e != hipSuccess) {
-    if (n.dW) (void)hipFree(n.dW);
-    if (n.dWb) (void)hipFree(n.dWb);
-    if (n.dWh) (void)hipFree(n.dWh);
-    if (n.dWf) (void)hipFree(n.dWf);
+    free_net(n);
     return fail(std::string("nsrw_upload_network: ") + hipGetErrorString(e));
   }
-  if (slot.dW) (void)hipFree(slot.dW);
-  if (slot.dWb) (void)hipFree(slot.dWb);
-  if (slot.dWh) (void)hipFree(slot.dWh);
-  if (slot.dWf) (void)hipFree(slot.dWf);
+  free_net(slot);
   slot = n;
   slot.loaded = true;
   return 0;
@@ -1647,6 +1591,17 @@ int nsrw_run_network(nsrw_handle hh, int net_id, const float* d_pts, const float
   h->timed = !cap;
   NSRW_HIP(hipGetLastError());
   return 0;
+}
+
+int nsrw_gemm_plan(int n_packed_rows, int n_stored_columns, int tile_wm, NsrwGemmPart* parts_out, int max_parts) {
+  if (n_packed_rows < 1 || n_packed_rows > NSRW_MAX_WIDTH || (tile_wm != 2 && tile_wm != 4) || max_parts < 0 || (max_parts > 0 && !parts_out)) {
+    fail("nsrw_gemm_plan: 1..NSRW_MAX_WIDTH packed rows, tile_wm 2 or 4, max_parts >= 0 with a buffer");
+    return -1;
+  }
+  NsrwGemmPart parts[kMaxGemmParts];
+  const int count = gemm_plan(col_blocks(n_packed_rows), n_stored_columns, tile_wm, parts);
+  for (int i = 0; i < std::min(count, max_parts); ++i) parts_out[i] = parts[i];
+  return count;
 }
 
 int nsrw_debug_bounds_status(int* built_with_checks, unsigned* first_bad_line) {

@@ -1,7 +1,9 @@
-// nsr_wide_b3.inc -- the layered renderer's GEMM on bf16 MFMAs with fp32 operands split three ways ("bf16x3", r06).
-// Included inside namespace nsrw (nsr_wide.hip), after GemmArgs / the epilogue enums.
+// nsr_wide_gemm.inc -- the layered renderer's GEMM: ONE kernel body, gemm_split_body<NJ, EPI, WM, NP>, for its three arithmetics
+// -- kw_gemm_b3 (NP = 3, "bf16x3"), kw_gemm_h2 (NP = 2, "f16x2") and kw_gemm_f32 (NP = 1, strict fp32).  Included inside namespace
+// nsrw (nsr_wide.hip), after the epilogue enums.  The bf16x3 form came first and is described first; what the other two change is
+// said where they are defined below.
 //
-// C[m][n] = epi( sum_k A[m][k] W[n][k] + bias[n] ) as kw_gemm computes it, fp32 in HBM on both sides, but the products run
+// C[m][n] = epi( sum_k A[m][k] W[n][k] + bias[n] ), fp32 in HBM on both sides.  bf16x3: the products run
 // on v_mfma_f32_32x32x16_bf16: every fp32 value is the exact sum of three bf16 pieces x = x0 + x1 + x2; of the nine piece
 // products of a * w the six of weight >= 2^-16 are kept (a0w0 a0w1 a0w2 a1w0 a1w1 a2w0, each exact in the MFMA's product
 // stage, fp32 accumulate) and the three below 2^-24 |a||w| are dropped -- the arithmetic of csrc/nsr_b3.inc, whose error
@@ -21,15 +23,18 @@
 //   * tile 128 (M) x 64 NJ (N), NJ = 4 | 2 | 1; 256 threads = 4 waves as 2 x 2, a wave owns 64 x 32 NJ = 2 x NJ accumulator
 //     blocks (128 registers at NJ = 4); K advances one k16 block per stage through double-buffered LDS (36 KiB per stage at
 //     NJ = 4: two workgroups per CU, two waves per SIMD), ONE barrier per stage = per 12 NJ MFMAs of a wave.  Per stage a wave
-//     reads 6 + 3 NJ fragments for 12 NJ MFMAs (384 B per MFMA at NJ = 4; the fp32 kernel: 512 B per MFMA of half the FLOP);
-//   * the tile walk, the two-segment K ([A1 | A2], the skip concatenations), the clamped ragged-M rows and the epilogues are
-//     kw_gemm's.
+//     reads 6 + 3 NJ fragments for 12 NJ MFMAs (384 B per MFMA at NJ = 4);
+//   * persistent workgroups walk the tiles in an XCD-aware order (the N-tiles of one M-block go to ONE XCD back to back), K runs
+//     over two segments ([A1 | A2], the skip concatenations), the rows of a ragged last M-block are clamped on the way in and
+//     never stored.
+#undef NSRW_FILE_TAG
+#define NSRW_FILE_TAG 100000        /* a failed NSRW_CHECK of this file reports 100000 + its line (nsrw_debug_bounds_status) */
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-struct GemmB3Args {
+struct GemmArgs {
   const float* A1; const float* A2;
-  const char* Wb;                          // b3 image, first col-block of this launch
+  const char* Wb;                          // weight image of the launch's arithmetic, from the first col-block of this launch on
   const float* bias; float* C; const float* mask;
   long long M;
   int lda1, lda2, K1, K2;                  // K extents, multiples of 32 (so of 16)
@@ -101,7 +106,7 @@ __device__ __forceinline__ f32x16 mfma_h2w(u32x4 a, u32x4 b, f32x16 c) {
 // WM: wave rows of a workgroup.  2: 256 threads, tile 128 x 64 NJ, two (NJ = 4) to four workgroups per CU.  4: 512 threads, tile
 // 256 x 64 NJ, ONE workgroup per CU (the same two waves per SIMD) -- the weights' L2 -> LDS traffic per FLOP halves, which is
 // what the ablations of profiles/r06/extra/ab_wide.txt price highest (this kernel runs at the board's power limit; time is energy).
-template <int NJ, int WM> constexpr int b3_wgs_per_cu() { return WM == 4 ? (NJ >= 3 ? 1 : 2) : NJ == 4 ? 2 : NJ == 2 ? 3 : 4; }
+template <int NJ, int WM> constexpr int wgs_per_cu() { return WM == 4 ? (NJ >= 3 ? 1 : 2) : NJ == 4 ? 2 : NJ == 2 ? 3 : 4; }
 
 // NP: pieces per operand -- 3: bf16x3 (six products), 2: f16x2 (three products), 1: the STRICT fp32 mode (r06: v_mfma_f32_32x32x2_f32 on
 // the same tiles, staging, prefetch and epilogues -- a fragment is then the lane's 8 consecutive fp32 k of a k16 block in two 16-byte
@@ -111,9 +116,9 @@ template <int NP> constexpr int split_chunks() { return NP == 1 ? 2 : NP; }
 template <int NJ, int WM, int NP> constexpr int split_lds_bytes() { return 2 * (2 * WM + 2 * NJ) * split_chunks<NP>() * 1024; }
 
 template <int NJ, int EPI, int WM, int NP>
-__device__ __forceinline__ void gemm_split_body(const GemmB3Args& g, char* const smem) {
+__device__ __forceinline__ void gemm_split_body(const GemmArgs& g, char* const smem) {
   constexpr int TN = 64 * NJ, NCB = 2 * NJ;                        // columns / col-blocks of a tile
-  constexpr int kTM = 64 * WM, NW = 2 * WM;                        // rows of a tile (shadows the fp32 kernel's 128) / waves
+  constexpr int kTM = 64 * WM, NW = 2 * WM;                        // rows of a tile / waves
   constexpr int NPC = split_chunks<NP>();
   constexpr int kFrag = NPC * 1024;                                // bytes of one fragment's pieces
   constexpr int kABytes = NW * kFrag, kBBytes = NCB * kFrag, kStage = kABytes + kBBytes;
@@ -127,7 +132,7 @@ __device__ __forceinline__ void gemm_split_body(const GemmB3Args& g, char* const
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)g.Wb, 0, (int)g.wb_bytes, 0x00020000);
 
   struct Tile { long long m0; int n0; const float* a1p; const float* a2p; int wsrc; };
-  auto coords = [&](long long t, Tile& tl) -> bool {               // kw_gemm's XCD-aware walk
+  auto coords = [&](long long t, Tile& tl) -> bool {               // the XCD-aware walk
     const int xcd = (int)(t & 7);
     const long long j = t >> 3;
     const long long mb = (j / g.n_tiles) * 8 + xcd;
@@ -423,19 +428,19 @@ __device__ __forceinline__ void gemm_split_body(const GemmB3Args& g, char* const
 }
 
 template <int NJ, int EPI, int WM>
-__global__ void __launch_bounds__(128 * WM, (b3_wgs_per_cu<NJ, WM>())) kw_gemm_b3(const GemmB3Args g) {
+__global__ void __launch_bounds__(128 * WM, (wgs_per_cu<NJ, WM>())) kw_gemm_b3(const GemmArgs g) {
   __shared__ __attribute__((aligned(1024))) char smem[split_lds_bytes<NJ, WM, 3>()];
   gemm_split_body<NJ, EPI, WM, 3>(g, smem);
 }
 
 template <int NJ, int EPI, int WM>
-__global__ void __launch_bounds__(128 * WM, (b3_wgs_per_cu<NJ, WM>())) kw_gemm_f32(const GemmB3Args g) {
+__global__ void __launch_bounds__(128 * WM, (wgs_per_cu<NJ, WM>())) kw_gemm_f32(const GemmArgs g) {
   __shared__ __attribute__((aligned(1024))) char smem[split_lds_bytes<NJ, WM, 1>()];
   gemm_split_body<NJ, EPI, WM, 1>(g, smem);
 }
 
 template <int NJ, int EPI, int WM>
-__global__ void __launch_bounds__(128 * WM, (b3_wgs_per_cu<NJ, WM>())) kw_gemm_h2(const GemmB3Args g) {
+__global__ void __launch_bounds__(128 * WM, (wgs_per_cu<NJ, WM>())) kw_gemm_h2(const GemmArgs g) {
   __shared__ __attribute__((aligned(1024))) char smem[split_lds_bytes<NJ, WM, 2>()];
   gemm_split_body<NJ, EPI, WM, 2>(g, smem);
 }

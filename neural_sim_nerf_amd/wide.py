@@ -3,7 +3,7 @@ input-side VJP (RN:168-178) for what the fused kernels are not built for: a NeRF
 list, any N_samples / N_importance (RN:439, RN:474).  Same interface as engine.NsrModel where the drop-in API
 (run_nerf_noscale.py) touches it, so `_model_for` can hand out either.
 
-One fp32-MFMA GEMM kernel per layer over a chunk of rays, activations resident in HBM between the layers; torch owns the
+One MFMA GEMM kernel per layer over a chunk of rays (f16x2, bf16x3 or fp32 MFMAs: `mlp`), activations resident in HBM between the layers; torch owns the
 buffers (including the workspace) and the stream, nothing else.  No fallback: without the library or a GPU every call raises."""
 import ctypes as C
 import os
@@ -44,6 +44,10 @@ class NsrwCotangents(C.Structure):
                 ("d_disp0", C.c_void_p), ("d_acc0", C.c_void_p)]
 
 
+class NsrwGemmPart(C.Structure):
+    _fields_ = [("nj", C.c_int32), ("wm", C.c_int32), ("tiles", C.c_int32), ("col_block", C.c_int32)]
+
+
 # render()'s differentiable outputs (RN:488-494) -> the field of NsrwCotangents and the shape of one ray's cotangent
 COTANGENTS = {"rgb_map": ("d_rgb", 3), "disp_map": ("d_disp", 1), "acc_map": ("d_acc", 1),
               "rgb0": ("d_rgb0", 3), "disp0": ("d_disp0", 1), "acc0": ("d_acc0", 1)}
@@ -70,6 +74,7 @@ SIGNATURES = {
     "nsrw_run_network": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
                                    C.c_void_p]),
     "nsrw_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "nsrw_gemm_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(NsrwGemmPart), C.c_int]),
     "nsrw_debug_bounds_status": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
     "nsrw_range_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "nsrw_sample_pdf": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -105,6 +110,17 @@ def load():
 def check(rc):
     if rc != 0:
         raise _lib.NsrError(load().nsrw_last_error().decode("utf-8", "replace"))
+
+
+def gemm_plan(n_packed_rows, n_stored_columns, tile_wm=4):
+    """nsrw_gemm_plan (diagnostic; no device, no handle): the launches of one layer GEMM along N, as
+    [(NJ, WM of the kernel form, tiles, first column)]; tile_wm = 2 is what NSRW_B3_WM=2 selects."""
+    lib = load()
+    parts = (NsrwGemmPart * 8)()
+    count = lib.nsrw_gemm_plan(int(n_packed_rows), int(n_stored_columns), int(tile_wm), parts, len(parts))
+    if not 0 <= count <= len(parts):
+        raise _lib.NsrError(lib.nsrw_last_error().decode("utf-8", "replace"))
+    return [(p.nj, p.wm, p.tiles, 32 * p.col_block) for p in parts[:count]]
 
 
 def _np(v):
@@ -223,7 +239,7 @@ class WideModel:
     def __init__(self, sd_coarse, sd_fine=None, device=None, n_importance=128, white_bkgd=False, lindisp=False, n_samples=64,
                  mlp=None):
         """mlp: the arithmetic of the layer GEMMs -- "bf16x3" (bf16 MFMAs on three-way split fp32 operands, fp32-grade results at
-        2.67x the matrix-pipe rate: csrc/nsr_wide_b3.inc), "fp32" (fp32 MFMAs, the strict mode) or "f16x2" (fp16 MFMAs with
+        2.67x the matrix-pipe rate: csrc/nsr_wide_gemm.inc), "fp32" (fp32 MFMAs, the strict mode) or "f16x2" (fp16 MFMAs with
         two-piece operands -- the fused default kernel's arithmetic; a network pass that leaves fp16's range is re-run on bf16x3
         inside the call); default $NSR_WIDE_MLP, else DEFAULT_MLP."""
         mlp = mlp or os.environ.get("NSR_WIDE_MLP") or DEFAULT_MLP

@@ -692,6 +692,34 @@ def test_two_layered_handles_on_two_streams(oracle):
         m.close()
 
 
+@pytest.mark.parametrize("mlp", MLPS3)
+def test_uploading_into_an_occupied_slot_equals_a_fresh_handle(mlp, oracle):
+    """nsrw_upload_network into slots that hold a network (the replaced images are freed behind a synchronise): 3 x 40 with view
+    directions at (3, 2) samples on 64 rays -- networks A uploaded and rendered, B (A's two networks swapped) uploaded into the same
+    slots of the live handle and rendered: every tap and the rgb input gradient equal a fresh handle's with B, bit for bit."""
+    from test_gpu_wide_tiles import TAPS, _nets, _rays
+    a_c, a_f = _nets(oracle, 40)
+    b_c, b_f = a_f, a_c
+    ns, ni, n = 3, 2, 64
+    near, far = oracle.YCBV_NEAR, oracle.YCBV_FAR
+    ro, rd = _rays(oracle, n, 24)
+    cot = np.random.RandomState(25).standard_normal((n, 3)).astype(np.float32)
+    m = _wide(mlp)(a_c, a_f, n_samples=ns, n_importance=ni)
+    with_a = cpu(m.render_rays(ro, rd, near, far, debug=True)["rgb_map"])
+    m.upload(b_c, b_f)
+    fresh = _wide(mlp)(b_c, b_f, n_samples=ns, n_importance=ni)
+    r1, r2 = (h.render_rays(ro, rd, near, far, debug=True) for h in (m, fresh))
+    g1, g2 = (h.render_rays_vjp(ro, rd, near, far, cot) for h in (m, fresh))
+    for k in TAPS:
+        assert np.array_equal(cpu(r1[k]), cpu(r2[k]), equal_nan=True), k
+    for x, y, what in zip(g1, g2, ("grad_o", "grad_d")):
+        assert np.array_equal(cpu(x), cpu(y), equal_nan=True), what
+    assert np.isfinite(cpu(r1["rgb_map"])).all() and np.isfinite(cpu(g1[0])).all() and np.abs(cpu(g1[0])).max() > 0
+    assert not np.array_equal(with_a, cpu(r1["rgb_map"]))                    # (B is another network: the upload took effect)
+    for h in (m, fresh):
+        h.close()
+
+
 def test_layered_debug_bounds_build_is_clean(tmp_path):
     """`make debug` compiles nsr_wide.hip with -DNSR_DEBUG_BOUNDS too (r06): every global / LDS index of the GEMM body (kw_gemm_h2 /
     _b3 / _f32) and of the per-ray kernels is checked against its extent.  A fresh process runs, on ALL THREE arithmetics, the edge shapes (W = 34,

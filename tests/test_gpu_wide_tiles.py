@@ -1,5 +1,5 @@
-"""GPU tests of EVERY tile form of the layered renderer's GEMM (gemm_split_body in csrc/nsr_wide_b3.inc; run with -m gpu on an
-MI355X).  gemm_b3 launches the body as <NJ, WM> = <4,4> <3,4> <2,4> <1,2> on a default handle and as <4,2> <2,2> <1,2> on one made
+"""GPU tests of EVERY tile form of the layered renderer's GEMM (gemm_split_body in csrc/nsr_wide_gemm.inc; run with -m gpu on an
+MI355X).  gemm launches the body as <NJ, WM> = <4,4> <3,4> <2,4> <1,2> on a default handle and as <4,2> <2,2> <1,2> on one made
 with NSRW_B3_WM=2 (128-row tiles), each with four epilogues on three arithmetics.  An output element's accumulator starts at 0 and
 takes the k16 blocks in ascending order and its MFMAs in a fixed order per block, and the epilogue is one expression: nothing in
 that depends on NJ, WM, the tile a row lands in, the grid or the rows that share the launch.  So the two tile heights agree BIT FOR

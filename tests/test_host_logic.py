@@ -105,7 +105,7 @@ def test_shipped_kernels_target_gfx950_only_and_do_not_spill():
     assert "kw_composite" in layered and "kw_sort" in layered and "kw_embed" in layered
     for k in layered:
         assert res[k]["vgpr_spill_count"] == 0 and res[k]["private_segment_fixed_size"] == 0, (k, res[k])
-    # r06: ONE GEMM body for the three arithmetics (csrc/nsr_wide_b3.inc) -- r05's separate fp32 kernel kw_gemm<...> is gone; the
+    # r06: ONE GEMM body for the three arithmetics (csrc/nsr_wide_gemm.inc) -- r05's separate fp32 kernel kw_gemm<...> is gone; the
     # strict fp32 mode is the same body on fp32 MFMAs with the f16x2 form's LDS footprint
     assert not [k for k in layered if k.startswith("kw_gemm<")]
     f32 = [k for k in layered if k.startswith("kw_gemm_f32<")]
@@ -113,7 +113,7 @@ def test_shipped_kernels_target_gfx950_only_and_do_not_spill():
     for e in (0, 1, 2, 4):
         r = res["kw_gemm_f32<4, %d, 4>" % e]
         assert r["vgpr_count"] <= 256 and r["group_segment_fixed_size"] == 65536, r
-    # r06: the bf16x3 GEMM (csrc/nsr_wide_b3.inc).  Its 256 x 256 tile (512 threads, two waves per SIMD) lives on <= 256 registers
+    # r06: the bf16x3 GEMM (csrc/nsr_wide_gemm.inc).  Its 256 x 256 tile (512 threads, two waves per SIMD) lives on <= 256 registers
     # and 96 KiB of LDS -- one workgroup per CU; the 128-row form on 72 KiB, two per CU
     b3 = [k for k in layered if k.startswith("kw_gemm_b3<")]
     assert {"kw_gemm_b3<%d, %d, %d>" % (nj, e, wm) for nj, wm in ((4, 4), (3, 4), (2, 4), (4, 2), (2, 2), (1, 2)) for e in (0, 1, 2, 4)} <= set(b3), b3

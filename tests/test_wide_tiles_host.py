@@ -1,6 +1,12 @@
-"""The N partition of the layered renderer's GEMM (gemm_b3 in csrc/nsr_wide.hip) restated in plain Python, and the guard that
+"""The N partition of the layered renderer's GEMM (gemm_plan in csrc/nsr_wide.hip) restated in plain Python, the guard that
 the widths tests/test_gpu_wide_tiles.py runs reach every tile form the library compiles: kw_gemm_* <NJ, WM> with NJ column units of
-64 and WM wave rows -- <4,4> <3,4> <2,4> <1,2> at the default tile height, <4,2> <2,2> <1,2> with NSRW_B3_WM=2.  No GPU needed."""
+64 and WM wave rows -- <4,4> <3,4> <2,4> <1,2> at the default tile height, <4,2> <2,2> <1,2> with NSRW_B3_WM=2 -- and the check that
+the restatement IS what the built library launches (nsrw_gemm_plan).  No GPU needed."""
+import os
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # network widths of the tile tests: the padded column count u = ncb / 2 (units of 64 columns) is 1 2 3 4 5 7 9 10
 WIDTHS = (40, 100, 136, 200, 264, 392, 520, 600)
@@ -13,13 +19,13 @@ def pad32(x):
 
 
 def units(n_padded):
-    """u of a packed matrix with n_padded rows: its 32-column blocks rounded up to an even count (pack_b3), in pairs"""
+    """u of a packed matrix with n_padded rows: its 32-column blocks rounded up to an even count (col_blocks), in pairs"""
     return ((n_padded + 31) // 32 + 1) // 2
 
 
 def partition(n_padded, n, wm):
-    """[(NJ, WM of the kernel, tiles, first column)] of the launches gemm_b3 makes for a matrix packed with n_padded rows of which the
-    caller stores n columns, on a handle with b3_wm = wm.  A part whose first column is not below n is not launched."""
+    """[(NJ, WM of the kernel, tiles, first column)] of the launches gemm makes for a matrix packed with n_padded rows of which the
+    caller stores n columns, on a handle with tile_wm = wm.  A part whose first column is not below n is not launched."""
     u, three = units(n_padded), wm == 4
     parts, cb = [], 0
 
@@ -95,3 +101,16 @@ def test_tile_test_widths_reach_every_form():
     assert trunk[600] == [[(4, 2), (2, 1)]] * 2                                # u = 10: 2 x 256 + 128
     for W in WIDTHS:
         print("W %3d u %2d: default %s   NSRW_B3_WM=2 %s" % (W, units(pad32(W)), sorted(forms(W, 4)), sorted(forms(W, 2))))
+
+
+def test_python_partition_is_the_librarys_launch_plan():
+    """partition() above against nsrw_gemm_plan of the built library -- the function gemm iterates over when it launches -- for every
+    padded width up to 1024 with the stored columns at the edges of the last block, and for every matrix of the tile tests' networks."""
+    if not os.path.exists(os.path.join(ROOT, "neural_sim_nerf_amd", "csrc", "libnsr.so")):
+        pytest.skip("needs the built library (python -c 'import __graft_entry__ as g; g.build()')")
+    from neural_sim_nerf_amd import wide
+    cases = {(npad, max(n, 1)) for npad in range(32, 1025, 32) for n in (1, 3, npad - 31, npad)}
+    cases |= {m for W in WIDTHS for m in network_matrices(W).values()}
+    for npad, n in sorted(cases):
+        for wm in (4, 2):
+            assert wide.gemm_plan(npad, n, wm) == partition(npad, n, wm), (npad, n, wm)

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Timing ablations of the layered renderer's bf16x3 GEMM (csrc/nsr_wide_b3.inc, -DNSRW_EXP_<X>: results are WRONG, only the time
+# Timing ablations of the layered renderer's GEMM (csrc/nsr_wide_gemm.inc, -DNSRW_EXP_<X>: results are WRONG, only the time
 # and the clock mean something): tools/ab_wide.sh <outfile> [case] -- one forward view per build, interleaved twice.
 R=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$1; CASE=${2:-w512}

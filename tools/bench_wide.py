@@ -1,6 +1,7 @@
 """Timing of the layered renderer (include/nsr_wide.h) on one 400x400 view: ms per view forward and forward + input gradient,
 algorithmic fp32 TFLOP/s of the network evaluations against the fp32-MFMA peak (157.3 TFLOP/s, MI355X_MICROARCH.md) -- the
-roofline of its GEMM kernel (kw_gemm: fp32 in, v_mfma_f32_32x32x2_f32, fp32 out).
+roofline of its strict mode (kw_gemm_f32: v_mfma_f32_32x32x2_f32) and the yardstick the split arithmetics (kw_gemm_h2, kw_gemm_b3: --mlp) are
+quoted against; for those the issued fraction of the fp16 / bf16 peak is reported as well.
 
     python tools/bench_wide.py [--hw 400] [--cases ycbv,w512,d10w384,small] [--steps 3]
 """

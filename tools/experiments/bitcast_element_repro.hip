@@ -1,7 +1,7 @@
 // hipcc 7.2 (gfx950, -O3): __builtin_bit_cast(float, v[e]) of ONE element of an ext_vector_type(4) of unsigned takes element 0 for
 // every e of an unrolled loop -- all four MFMAs below read v16 / v18 (hipcc --offload-arch=gfx950 -O3 -c -save-temps=obj, then grep
 // v_mfma in the .s).  Casting the whole vector first (__builtin_bit_cast(f32x4, v)[e]) compiles to v16..v19 / v20..v23 as it should.
-// Found on the first run of kw_gemm_f32 (csrc/nsr_wide_b3.inc); the stage-wise parity tests caught it.
+// Found on the first run of kw_gemm_f32 (csrc/nsr_wide_gemm.inc); the stage-wise parity tests caught it.
 #include <hip/hip_runtime.h>
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));

@@ -43,7 +43,7 @@ def kernel_resources(lib):
             continue
         m = re.match(r"_ZN3nsr\d+(\w+?)E", name.group(1))
         key = m.group(1) if m else name.group(1)
-        if key.startswith("_ZN4nsrw"):              # the layered renderer's kernels (templates): kw_gemm<128, 1, 16> etc.
+        if key.startswith("_ZN4nsrw"):              # the layered renderer's kernels (templates): kw_gemm_h2<4, 1, 4> etc.
             mm = re.match(r"_ZN4nsrw(\d+)", key)
             base = key[len(mm.group(0)):][:int(mm.group(1))]
             targs = re.match(r"I((?:Li\d+E)+)E", key[len(mm.group(0)) + int(mm.group(1)):])

@@ -1,5 +1,5 @@
 #!/bin/bash
-# PMC passes over the layered renderer's GEMM kernel (kw_gemm): tools/pmc_wide.sh <outdir> [case] [hw]
+# PMC passes over the layered renderer's GEMM kernels (kw_gemm_h2 / _b3 / _f32): tools/pmc_wide.sh <outdir> [case] [hw]
 # separate rocprofv3 --pmc passes with --kernel-trace only (MI355X_MICROARCH.md); summarised by tools/pmc_wide.py
 R=${GRAFT_REPO_ROOT:-$PWD}
 O=$1; CASE=${2:-w512}; HW=${3:-200}
