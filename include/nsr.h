@@ -17,6 +17,7 @@
  *     allocation -- with ONE exception outside stream capture: an f16x2 handle's render / input-gradient launch that is
  *     larger than every launch before it first grows the range safety net's list (nsr_reserve_range).  They can be
  *     captured into a hipGraph and replayed (tests/test_gpu_parity.py);
+ *     nsr_launch_plan (diagnostic) touches neither a handle nor the device: it answers what a launch call would launch;
  *   - return value: 0 = OK, non-zero = error, message via nsr_last_error() (thread-local);
  *   - one handle per (model, stream): a handle owns one argument block, one work-queue head and its scratch
  *     buffers, so launches are ordered by the stream they are issued on; a launch on a DIFFERENT stream while the
@@ -403,6 +404,38 @@ int nsr_reserve_range(nsr_handle h, int64_t n_rays);
  * is clamped and its source line recorded.  *built_with_checks = 0 for the release library (then *first_bad_line = 0).
  * Synchronises the device. */
 int nsr_debug_bounds_status(nsr_handle h, int* built_with_checks, unsigned* first_bad_line);
+
+/* Diagnostic, no device and no handle needed: the launch plan of one nsr_render_rays* / nsr_render_views (NSR_PLAN_RENDER) or
+ * nsr_render_rays_vjp* (NSR_PLAN_VJP) call -- the function those calls launch from -- on a handle of configuration *cfg (what
+ * nsr_create accepts) on a GPU of n_cu compute units.  uploaded_bits: bit 3 * NSR_IMAGE_x + slot for every weight image the
+ * handle holds (slot 0 / 1 = net_id of nsr_upload_weights<x>, slot 2 = nsr_upload_weights_bwd<x>), NSR_UPLOADED_TABLES for
+ * nsr_upload_tables.  call_bits: NSR_CALL_EXTRAS = the call passes per-ray extras, NSR_CALL_TAPS = NsrVjpDebugOut taps,
+ * NSR_CALL_Z_FINE = d_z_fine (the last two: NSR_PLAN_VJP only).  Returns non-zero where the launch call refuses, with the
+ * launch call's own message in nsr_last_error.  Kernel names are those of namespace nsr in csrc/nsr_kernels.hip. */
+#define NSR_IMAGE_X32 0   /* nsr_upload_weights / _bwd         */
+#define NSR_IMAGE_X16 1   /* nsr_upload_weights16 / _bwd16     */
+#define NSR_IMAGE_B3  2   /* nsr_upload_weights_b3 / _bwd_b3   */
+#define NSR_IMAGE_H2  3   /* nsr_upload_weights_h2 / _bwd_h2   */
+#define NSR_UPLOADED_TABLES (1u << 12)
+#define NSR_PLAN_RENDER 0
+#define NSR_PLAN_VJP    1
+#define NSR_CALL_EXTRAS 1u
+#define NSR_CALL_TAPS   2u
+#define NSR_CALL_Z_FINE 4u
+typedef struct NsrLaunchPlan {
+  const char* kernel;          /* the kernel the call launches ...                                                        */
+  const char* fallback;        /* ... and the f16x2 range safety net's second launch over the reported items; NULL = none */
+  int32_t image;               /* NSR_IMAGE_* the kernel reads                                                            */
+  int32_t fallback_image;      /* ... and the fallback, -1 = none                                                         */
+  int32_t grid;                /* workgroups (of 256 threads) of both launches                                            */
+  int32_t lds_bytes;           /* dynamic LDS of the kernel = the limit nsr_create sets for it                            */
+  int32_t fallback_lds_bytes;
+  int32_t chunk;               /* x16 forward kernels: rays per chunk of the work queue (else 0)                          */
+  int32_t phases;              /* 1 = global-phases schedule (k_render16p / k_render_vjp16p)                              */
+  int32_t ovf_armed;           /* f16x2: 1 = reported items are listed for the fallback, 0 = dropped (NaN, counted)       */
+} NsrLaunchPlan;
+int nsr_launch_plan(const NsrConfig* cfg, int n_cu, unsigned uploaded_bits, int direction, unsigned call_bits, int64_t n_rays,
+                    NsrLaunchPlan* out);
 
 /* Timing helper for bench.py: HIP-event time in ms of the last EAGER nsr_render_* launch on this handle
  * (events recorded on the launch stream; this call synchronises on the stop event).  Launches made while the

@@ -35,6 +35,12 @@ class NsrVjpDebugOut(C.Structure):
     _fields_ = [("d_relu_masks", C.c_void_p), ("d_grad_raw", C.c_void_p), ("d_grad_pts", C.c_void_p)]
 
 
+class NsrLaunchPlan(C.Structure):
+    _fields_ = [("kernel", C.c_char_p), ("fallback", C.c_char_p), ("image", C.c_int32), ("fallback_image", C.c_int32),
+                ("grid", C.c_int32), ("lds_bytes", C.c_int32), ("fallback_lds_bytes", C.c_int32), ("chunk", C.c_int32),
+                ("phases", C.c_int32), ("ovf_armed", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/nsr.h declares
 SIGNATURES = {
     "nsr_last_error": (C.c_char_p, []),
@@ -98,6 +104,7 @@ SIGNATURES = {
     "nsr_schedule_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint)]),
     "nsr_debug_bounds_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
     "nsr_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "nsr_launch_plan": (C.c_int, [C.POINTER(NsrConfig), C.c_int, C.c_uint, C.c_int, C.c_uint, C.c_int64, C.POINTER(NsrLaunchPlan)]),
 }
 
 _lib = None

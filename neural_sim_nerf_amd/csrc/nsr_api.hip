@@ -12,7 +12,9 @@ extern "C" int nsr_unit_bounds_x16(unsigned* line);
 #include "nsr_handoff.hip"
 #include "nsr_pose.hip"
 
+#include <algorithm>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include <cstdio>
 #include <cstdlib>
@@ -58,37 +60,197 @@ struct DeviceGuard {
 constexpr unsigned kOvfCap = 1u << 17;      // items (2 rays each) the safety net's list holds at first: 1 MiB per handle; every launch
                                             // call grows it to its own size first (ensure_range), so no item is ever dropped
 constexpr long long kMaxRaysH2 = 2 * 0xFFFFFFFFll;   // f16x2 handles: the launch's item count is a 32-bit device word
-static int kSuperLg = 12;              // k_render16p: 4096 rays per super-chunk (8 rounds of the 512-workgroup grid)
 
+// ---- the weight images: one row per family.  A handle keeps a family in one buffer of three slots -- coarse | fine | fine
+// transposed -- `stride` floats apart (the transposed stream is the longest of the three in the bf16x3 and f16x2 layouts)
+enum Image { kX32, kX16, kB3, kH2, kImages };
+constexpr int kEveryHandle = -1;
+struct ImageRow {
+  size_t stride;          // floats between two slots
+  size_t fwd_stream;      // floats of a forward stream: where the slot's aux block starts
+  size_t fwd_floats;      // floats of a forward image (stream + aux block)
+  size_t bwd_stream;      // floats of the transposed stream
+  int upload_flags;       // NsrConfig::flags of the handles that take this family (kEveryHandle: all)
+  int create_flags;       // ... of those whose buffer nsr_create allocates; the others allocate it at their first upload, so that a
+                          // handle whose kernels never read a family does not pay for it
+  const char* suffix;     // nsr_upload_weights<suffix> / nsr_upload_weights_bwd<suffix>
+  const char* refusal;    // what the upload of another handle is told
+};
+constexpr size_t kStream = (size_t)NSR_STREAM_SLABS * NSR_SLAB_FLOATS;
+constexpr size_t kB3Stride = (size_t)NSR_STREAM_SLABS_B3_BWD * NSR_SLAB_FLOATS + NSR_AUX_FLOATS;
+constexpr size_t kH2Stride = (size_t)NSR_STREAM_SLABS_H2_BWD * NSR_SLAB_FLOATS + NSR_AUX_FLOATS;
+static_assert(kB3Stride >= (size_t)NSR_PACKED_B3_FLOATS && kH2Stride >= (size_t)NSR_PACKED_FLOATS, "stride covers the forward images");
+constexpr ImageRow kImageRows[kImages] = {
+    {NSR_PACKED_FLOATS, kStream, NSR_PACKED_FLOATS, kStream, kEveryHandle, kEveryHandle, "", ""},
+    {NSR_PACKED_FLOATS, kStream, NSR_PACKED_FLOATS, kStream, kEveryHandle, 0, "16", ""},
+    {kB3Stride, (size_t)NSR_STREAM_SLABS_B3 * NSR_SLAB_FLOATS, NSR_PACKED_B3_FLOATS, (size_t)NSR_STREAM_SLABS_B3_BWD * NSR_SLAB_FLOATS,
+     NSR_FLAG_MLP_BF16X3 | NSR_FLAG_MLP_F16X2, NSR_FLAG_MLP_BF16X3, "_b3",     // (f16x2 handles: the images of the range fallback)
+     ": the handle was created with neither NSR_FLAG_MLP_BF16X3 nor NSR_FLAG_MLP_F16X2"},
+    {kH2Stride, kStream, NSR_PACKED_FLOATS, (size_t)NSR_STREAM_SLABS_H2_BWD * NSR_SLAB_FLOATS, NSR_FLAG_MLP_F16X2, NSR_FLAG_MLP_F16X2,
+     "_h2", ": the handle was not created with NSR_FLAG_MLP_F16X2"},
+};
+constexpr unsigned kHaveTables = 1u << (3 * kImages);       // in a word of `have` bits: bit 3 * image + slot, then the tables
+constexpr unsigned have_bits(Image im, unsigned slots) { return slots << (3 * im); }
+
+// ---- the fused kernels: one row per kernel, by direction, kernel family and sample-count form.  The x32-structured bf16x3 and
+// f16x2 kernels are instantiated for the sample counts (N_samples, N_importance; RN:439, RN:474) of an f16x2 handle: (64, 128 / 0)
+// default, (64, 96 / 64 / 32) n96 / n64 / n32, (32, 64 / 0) c32_n64, (128, 128 / 0) c128_n128 -- a coarse-only handle runs the kernel
+// of its fine partner.  The fp32 kernels exist in the default form only.  `lds` is the row's dynamic LDS size: nsr_create raises
+// the kernel's limit to it and the launch passes it.
 constexpr size_t kRenderLds = nsr::kLdsState + sizeof(nsr::ItemState);
 constexpr size_t kRenderLdsBig = nsr::kLdsState + sizeof(nsr::ItemStateBig);      // N_samples = 128 (r05)
 static_assert(kRenderLdsBig <= 163840, "the N_samples = 128 item state fits the 160 KiB LDS next to the ring and the aux blocks");
 constexpr size_t kRender16Lds = nsr::kLds16State + sizeof(nsr::ItemState16);
 constexpr size_t kVjp16Lds = nsr::kLds16State + sizeof(nsr::ItemStateV16);
 constexpr size_t kNetLds = nsr::kLdsAux + nsr::kAuxFloats * 4;
-// bf16x3 images in d_nets_b3: coarse | fine | fine transposed, kB3Stride floats apart (the transposed stream is the longest)
-constexpr size_t kB3Stride = (size_t)NSR_STREAM_SLABS_B3_BWD * NSR_SLAB_FLOATS + NSR_AUX_FLOATS;
-static_assert(kB3Stride >= (size_t)NSR_PACKED_B3_FLOATS, "stride covers the forward images");
-// f16x2 images in d_nets_h2: coarse | fine | fine transposed, kH2Stride floats apart (the transposed stream is one slab longer)
-constexpr size_t kH2Stride = (size_t)NSR_STREAM_SLABS_H2_BWD * NSR_SLAB_FLOATS + NSR_AUX_FLOATS;
-static_assert(kH2Stride >= (size_t)NSR_PACKED_FLOATS, "stride covers the forward images");
+enum Dir { kRender, kVjp, kDirs };
+enum Family { kFx32, kFx16, kFx16p, kFb3, kFh2, kFamilies };      // x16: per-ray queue / global phases
+enum Form { kDefault, kN96, kN64, kN32, kC32N64, kC128N128, kForms };
+constexpr Image kFamilyImage[kFamilies] = {kX32, kX16, kX16, kB3, kH2};
+struct Kernel { const char* name; const void* fn; int lds; };
+#define NSR_K(NAME, LDS) {#NAME, (const void*)nsr::NAME, (int)(LDS)}
+#define NSR_K6(NAME) {NSR_K(NAME, kRenderLds), NSR_K(NAME##_n96, kRenderLds), NSR_K(NAME##_n64, kRenderLds), \
+                      NSR_K(NAME##_n32, kRenderLds), NSR_K(NAME##_c32_n64, kRenderLds), NSR_K(NAME##_c128_n128, kRenderLdsBig)}
+const Kernel kKernels[kDirs][kFamilies][kForms] = {
+    {{NSR_K(k_render, kRenderLds)}, {NSR_K(k_render16, kRender16Lds)}, {NSR_K(k_render16p, kRender16Lds)}, NSR_K6(k_render_b3),
+     NSR_K6(k_render_h2)},
+    {{NSR_K(k_render_vjp, kRenderLds)}, {NSR_K(k_render_vjp16, kVjp16Lds)}, {NSR_K(k_render_vjp16p, kVjp16Lds)}, NSR_K6(k_render_vjp_b3),
+     NSR_K6(k_render_vjp_h2)}};
+#undef NSR_K6
+#undef NSR_K
 
+inline Form form_of(int ns, int ni) {
+  return ns == 32 ? kC32N64 : ns == 128 ? kC128N128 : ni == 96 ? kN96 : ni == 64 ? kN64 : ni == 32 ? kN32 : kDefault;
+}
+// the rows a handle of this configuration can launch (nsr_create sets their LDS limit): both fp32 structures whatever `variant`
+// (extras and taps run k_render / k_render_vjp), the bf16x3 kernels also as an f16x2 handle's range fallback
+inline bool handle_launches(const NsrConfig& c, int family, Form form) {
+  if (form != kDefault && !((c.flags & NSR_FLAG_MLP_F16X2) && form == form_of(c.n_samples, c.n_importance))) return false;
+  if (family == kFx16p) return (c.flags & NSR_FLAG_SCHED_PHASES) != 0;
+  if (family == kFb3) return (c.flags & (NSR_FLAG_MLP_BF16X3 | NSR_FLAG_MLP_F16X2)) != 0;
+  if (family == kFh2) return (c.flags & NSR_FLAG_MLP_F16X2) != 0;
+  return true;
+}
 
-// The sample counts the x32-structured kernels are instantiated for (RN:439 N_samples, RN:474 N_importance).  N_samples = 64:
-// N_importance 128 on every handle; 0 (coarse only); 96 / 64 / 32 on f16x2 handles.  r05: N_samples = 32 with N_importance 64 (or
-// 0) and N_samples = 128 with N_importance 128 (or 0), f16x2 handles only.
-struct Counts { int ns, ni; };
-typedef void (*RenderKernel)(const nsr::RenderArgs*);
-typedef void (*VjpKernel)(const nsr::VjpArgs*);
-struct KernelSet { RenderKernel h2, b3; VjpKernel vjp_h2, vjp_b3; };
-inline bool special_counts(int ns, int ni) { return ns != NSR_N_SAMPLES || (ni != NSR_N_IMPORTANCE && ni != 0); }
-// kernels of an f16x2 handle with `special_counts`: the coarse-only form of N_samples 32 / 128 runs the kernel of its fine partner
-inline KernelSet special_kernels(int ns, int ni) {
-  if (ns == 32) return {nsr::k_render_h2_c32_n64, nsr::k_render_b3_c32_n64, nsr::k_render_vjp_h2_c32_n64, nsr::k_render_vjp_b3_c32_n64};
-  if (ns == 128) return {nsr::k_render_h2_c128_n128, nsr::k_render_b3_c128_n128, nsr::k_render_vjp_h2_c128_n128, nsr::k_render_vjp_b3_c128_n128};
-  if (ni == 96) return {nsr::k_render_h2_n96, nsr::k_render_b3_n96, nsr::k_render_vjp_h2_n96, nsr::k_render_vjp_b3_n96};
-  if (ni == 64) return {nsr::k_render_h2_n64, nsr::k_render_b3_n64, nsr::k_render_vjp_h2_n64, nsr::k_render_vjp_b3_n64};
-  return {nsr::k_render_h2_n32, nsr::k_render_b3_n32, nsr::k_render_vjp_h2_n32, nsr::k_render_vjp_b3_n32};
+const char* config_error(const NsrConfig& c) {
+  if (c.abi_version != NSR_ABI_VERSION) return "nsr_create: ABI version mismatch";
+  if ((c.flags & NSR_FLAG_MLP_BF16X3) && (c.flags & NSR_FLAG_MLP_F16X2))
+    return "nsr_create: NSR_FLAG_MLP_BF16X3 and NSR_FLAG_MLP_F16X2 are mutually exclusive";
+  if (c.flags & ~(NSR_FLAG_WHITE_BKGD | NSR_FLAG_LINDISP | NSR_FLAG_SCHED_PHASES | NSR_FLAG_MLP_BF16X3 | NSR_FLAG_MLP_F16X2))
+    return "nsr_create: unknown bits in flags";
+  const int ns = c.n_samples, ni = c.n_importance;
+  const bool h2cfg = (c.flags & NSR_FLAG_MLP_F16X2) != 0;
+  const bool ok = (ns == NSR_N_SAMPLES && (ni == NSR_N_IMPORTANCE || ni == 0)) ||
+                  (h2cfg && ns == NSR_N_SAMPLES && (ni == 96 || ni == 64 || ni == 32)) ||
+                  (h2cfg && ns == 32 && (ni == 64 || ni == 0)) || (h2cfg && ns == 128 && (ni == 128 || ni == 0));
+  if (!ok)
+    return "nsr_create: unsupported (N_samples, N_importance): (64, 128) and (64, 0) on every handle; on NSR_FLAG_MLP_F16X2 "
+           "handles also (64, 96 / 64 / 32), (32, 64 / 0) and (128, 128 / 0) -- other handles render fewer importance samples "
+           "with N_importance = 128 and a uniforms table of repeated values (engine._host_tables)";
+  if ((c.flags & NSR_FLAG_SCHED_PHASES) && (c.variant == 32 || ni == 0))
+    return "nsr_create: NSR_FLAG_SCHED_PHASES applies to the x16 coarse+fine forward kernel only";
+  if (c.chunk < 0 || c.chunk > 256) return "nsr_create: chunk must be 0 (default) or 1..256";
+  if (c.variant != 0 && c.variant != 16 && c.variant != 32) return "nsr_create: variant must be 0 (default), 16 or 32";
+  return nullptr;
+}
+
+// ---- the launch plan of one render / input-gradient call: pure host arithmetic, no HIP call, no handle (nsr_launch_plan exposes it)
+struct PlanIn {
+  NsrConfig cfg;
+  int n_cu;
+  unsigned have;                  // have_bits of the uploaded images | kHaveTables
+  Dir dir;
+  bool extras, taps, z_fine;      // the call has per-ray extras / debug taps of the gradient / the caller's fine depths
+  long long n_rays;
+};
+struct Plan {
+  const Kernel* kernel = nullptr;      // null with `refusal`: no kernel serves the call; set with `refusal`: its uploads are missing
+  Image image = kX32;
+  const Kernel* fallback = nullptr;    // f16x2 range safety net: the second launch over the reported items, or none
+  Image fallback_image = kX32;
+  int grid = 0;
+  int chunk = 0;                       // k_render16 / k_render16p: rays per chunk of the work queue
+  bool phases = false;                 // global-phases schedule
+  bool h2 = false;                     // an f16x2 kernel runs: the range list is in use ...
+  bool ovf_armed = false;              // ... and reported items have a fallback to go to (else they are dropped: NaN, counted)
+  const char* refusal = nullptr;
+};
+
+// workgroups that fill the chip: one per CU for the x32-structured kernels (also the entries of the relu-pattern scratch), two for x16
+// (also the entries of k_render16's inter-phase scratch)
+inline long long x32_grid(const NsrConfig& c, int n_cu) { return c.max_workgroups > 0 ? c.max_workgroups : n_cu; }
+inline long long x16_grid(const NsrConfig& c, int n_cu) { return c.max_workgroups > 0 ? c.max_workgroups : 2LL * n_cu; }
+inline int queue_chunk(const NsrConfig& c) { return (c.chunk > 0 && !(c.flags & NSR_FLAG_SCHED_PHASES)) ? c.chunk : 1; }
+
+Plan plan_launch(const PlanIn& in) {
+  Plan p;
+  const NsrConfig& c = in.cfg;
+  const bool vjp = in.dir == kVjp, fine = c.n_importance > 0;
+  const unsigned need = vjp ? 7u : (fine ? 3u : 1u);            // slots of an image the call reads
+  auto have = [&](Image im, unsigned slots) { return (in.have & have_bits(im, slots)) == have_bits(im, slots); };
+  auto refuse = [&](const char* m) { p.refusal = m; return p; };
+  if (vjp && !fine) return refuse("nsr_render_rays_vjp: needs the coarse+fine configuration (N_importance > 0)");
+  // every handle holds the tables and the x32 images (the stage kernels read them; an fp32 handle's per-ray extras)
+  if (!(in.have & kHaveTables)) return refuse("tables not uploaded (nsr_upload_tables)");
+  if (!have(kX32, 1)) return refuse("coarse network not uploaded (nsr_upload_weights net_id 0)");
+  if (fine && !have(kX32, 2)) return refuse("fine network not uploaded (nsr_upload_weights net_id 1)");
+  const bool b3 = (c.flags & NSR_FLAG_MLP_BF16X3) != 0;
+  // an f16x2 handle runs its input gradients on fp16 MFMAs too once the transposed stream is there (nsr_upload_weights_bwd_h2);
+  // without it the fp32 kernels of `variant` serve (they need their own uploads)
+  p.h2 = (c.flags & NSR_FLAG_MLP_F16X2) && (!vjp || have(kH2, 7));
+  const Form form = form_of(c.n_samples, c.n_importance);      // other than kDefault on f16x2 handles only (nsr_create)
+  if (vjp && form != kDefault && !p.h2)
+    return refuse("nsr_render_rays_vjp: a handle of these sample counts needs nsr_upload_weights_bwd_h2 (only the f16x2 kernels are specialised to them)");
+  // library default (variant 0) = x16: measured 145.0 vs 141.5 TFLOP/s for x32 on one 400x400 view (tools/compare_variants.py).
+  // The per-ray extras (NsrRayExtras) and the gradient's debug taps are read by the x32-structured kernels: an fp32 handle serves
+  // them with k_render / k_render_vjp whatever its `variant`
+  const bool x16 = c.variant != 32 && !b3 && !p.h2 && !in.extras && !in.taps;
+  // global-phases schedule, unless the caller supplies the depths itself (then nothing is handed over)
+  p.phases = x16 && fine && (c.flags & NSR_FLAG_SCHED_PHASES) && !in.z_fine;
+  const Family family = p.h2 ? kFh2 : b3 ? kFb3 : p.phases ? kFx16p : x16 ? kFx16 : kFx32;
+  p.kernel = &kKernels[in.dir][family][family == kFh2 ? form : kDefault];
+  p.image = kFamilyImage[family];
+  static const char* const not_ready[kDirs][kImages] = {
+      {nullptr, "variant 16 needs nsr_upload_weights16 for every network", "NSR_FLAG_MLP_BF16X3 needs nsr_upload_weights_b3 for every network",
+       "NSR_FLAG_MLP_F16X2 needs nsr_upload_weights_h2 for every network"},
+      {"nsr_render_rays_vjp: backward stream not uploaded (nsr_upload_weights_bwd)",
+       "nsr_render_rays_vjp: variant 16 needs nsr_upload_weights16 (both networks) and nsr_upload_weights_bwd16",
+       "nsr_render_rays_vjp: NSR_FLAG_MLP_BF16X3 needs nsr_upload_weights_b3 (both networks) and nsr_upload_weights_bwd_b3", nullptr}};
+  if (!have(p.image, need)) return refuse(not_ready[in.dir][p.image]);
+  if (p.h2) {
+    // f16x2 range safety net: the items the kernel reported (a NaN network output or gradient: a scaled activation beyond the fp16
+    // range) run again on the kernel of the same template -- on bf16 MFMAs (three-way split: fp32's exponent range, no failure domain,
+    // 1.7x the fp32-MFMA kernel) once the handle holds the bf16x3 images the call reads (nsr_upload_weights_b3 / _bwd_b3; the Python
+    // engine uploads them), else on fp32 MFMAs, which exist for the default counts only and whose gradient needs nsr_upload_weights_bwd;
+    // with neither, the reported items are dropped (NaN outputs, counted)
+    if (have(kB3, need)) { p.fallback = &kKernels[in.dir][kFb3][form]; p.fallback_image = kB3; }
+    else if (form == kDefault && have(kX32, need)) { p.fallback = &kKernels[in.dir][kFx32][kDefault]; p.fallback_image = kX32; }
+    p.ovf_armed = p.fallback != nullptr;
+#ifdef NSR_EXP_NO_RANGE      // timing experiment: the forward kernels report nothing, no second launch
+    if (!vjp) p.fallback = nullptr;
+#endif
+  }
+  const long long n = in.n_rays, mask_grid = x32_grid(c, in.n_cu);
+  long long g = x16_grid(c, in.n_cu);
+  if (!x16) {                                              // two rays per item, one workgroup per CU
+    g = std::max(std::min(mask_grid, (n + 1) / 2), 1LL);
+    if (vjp) g = std::min(g, mask_grid);                   // the relu-pattern scratch has one block per workgroup
+  } else if (vjp) {                                        // one ray per item, two workgroups per CU
+    g = std::min(std::min(g, 2 * mask_grid), n);           // scratch entries are half the size (uint2)
+  } else if (p.phases) {
+    g = std::min(g, 2 * n);
+    p.chunk = 1;
+  } else {
+    // rays per chunk (see k_render16).  Larger chunks keep one network per L2 for longer (less fabric traffic), but
+    // the chunk is also the granularity of the dynamic load balance between the unevenly progressing workgroups:
+    // measured 1 -> 148.2, 2 -> 148.0, 4 -> 148.0, 8 -> 147.9, 16 -> 145.9 TFLOP/s.  Speed wins: the default is 1
+    // (NsrConfig.chunk).
+    p.chunk = queue_chunk(c);
+    if ((long long)p.chunk * g > n) p.chunk = (int)(n / g > 1 ? n / g : 1);   // small batches: keep every CU busy
+    g = std::min(g, (n + p.chunk - 1) / p.chunk);
+  }
+  p.grid = (int)g;
+  return p;
 }
 
 }  // namespace
@@ -96,23 +258,15 @@ inline KernelSet special_kernels(int ns, int ni) {
 struct nsr_handle_s {
   NsrConfig cfg;
   int n_cu = 0;
-  int chunk = 1;                                        // k_render16: rays per chunk of the work queue
-  float* d_nets = nullptr;
-  float* d_packed[3] = {nullptr, nullptr, nullptr};   // views into d_nets: coarse, fine, fine transposed
-  bool have_net[3] = {false, false, false};
-  float* d_nets16 = nullptr;                            // coarse | fine | fine transposed in the x16 layout
-  bool have_net16[3] = {false, false, false};
-  float* d_nets_b3 = nullptr;                           // coarse | fine | fine transposed in the bf16x3 layout
-  bool have_net_b3[3] = {false, false, false};          // (NSR_FLAG_MLP_BF16X3)
-  float* d_nets_h2 = nullptr;                           // coarse | fine | fine transposed in the f16x2 layout, kH2Stride apart
-  bool have_net_h2[3] = {false, false, false};          // (NSR_FLAG_MLP_F16X2)
+  int super_lg = 12;                  // k_render16p: 4096 rays per super-chunk (8 rounds of the 512-workgroup grid)
+  struct { float* d = nullptr; bool have[3] = {false, false, false}; } img[kImages];   // kImageRows: coarse, fine, fine transposed
   float* d_tables = nullptr;  // [64] + [128]
   bool have_tables = false;
   float* d_scratch = nullptr;  // selftest
   nsr::RenderArgs* d_args = nullptr;  // kernel argument block (device), written stream-ordered by k_set_args
   nsr::VjpArgs* d_vjp_args = nullptr;
-  uint4* d_mask_scratch = nullptr;    // relu patterns of the fine forward passes: x32 [n_cu][3][9][256] uint4 = x16
-  int mask_grid = 0;                  // [2 n_cu][3][9][256] uint2 (same bytes); allocated by nsr_upload_weights_bwd*
+  uint4* d_mask_scratch = nullptr;    // relu patterns of the fine forward passes: x32 [x32_grid][3][9][256] uint4 = x16
+                                      // [2 x32_grid][3][9][256] uint2 (same bytes); allocated by nsr_upload_weights_bwd*
   unsigned long long* d_work_counter = nullptr;  // work-queue heads: [0] the launch, [1] its fp32 fallback launch (f16x2)
   nsr::RenderArgs* d_args_fb = nullptr;          // f16x2 range safety net: argument blocks of the fallback launches,
   nsr::VjpArgs* d_vjp_args_fb = nullptr;
@@ -122,9 +276,8 @@ struct nsr_handle_s {
                                                  // captured earlier, holds their address in its argument block (by value),
                                                  // so they live as long as the handle does
   unsigned* d_ovf_stat = nullptr;                // ... [0] items of the last launch, [1] points, [2] rays, [3] items beyond the cap
-  float* d_zf_scratch = nullptr;      // k_render16: sorted fine z values between the two phases of a chunk, [2 n_cu][chunk][192]
-  int zf_grid = 0;
-  unsigned* d_sched_flags = nullptr;  // global phases: ready / taken generations of the 3 * 2^kSuperLg hand-off slots
+  float* d_zf_scratch = nullptr;      // k_render16: sorted fine z values between the two phases of a chunk, [x16_grid][chunk][192]
+  unsigned* d_sched_flags = nullptr;  // global phases: ready / taken generations of the 3 * 2^super_lg hand-off slots
   unsigned* d_status = nullptr;       // global phases: rays whose fine task recomputed its coarse pass (nsr_schedule_stats)
   int* d_box_scratch = nullptr;       // nsr_find_bbox: parent + stats of one batch of images (nsr_reserve_bbox)
   size_t box_scratch_ints = 0;
@@ -157,69 +310,80 @@ static int stream_capturing(hipStream_t s, bool* capturing) {
   return 0;
 }
 
+static int alloc_image(nsr_handle h, Image im) {
+  if (h->img[im].d) return 0;
+  NSR_HIP(hipMalloc(&h->img[im].d, sizeof(float) * 3 * kImageRows[im].stride));
+  return 0;
+}
+
 // every device allocation, event and kernel attribute a handle needs for its launch calls (setup time only)
 static int allocate_handle(nsr_handle h) {
   const NsrConfig* cfg = &h->cfg;
-  // one allocation: coarse | fine | fine^T (backward stream), NSR_PACKED_FLOATS apart
-  NSR_HIP(hipMalloc(&h->d_nets, sizeof(float) * 3 * NSR_PACKED_FLOATS));
-  for (int i = 0; i < 3; ++i) h->d_packed[i] = h->d_nets + (size_t)i * NSR_PACKED_FLOATS;
-  // d_nets16 (the x16 images) is allocated by the first nsr_upload_weights16 / _bwd16: handles whose kernels never read
-  // it (f16x2 / bf16x3 handles run k_render_h2 / _b3, their fallback and the stage kernels read the x32 image) do not pay for it
-  NSR_HIP(hipFuncSetAttribute((const void*)nsr::k_render_vjp16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kVjp16Lds));
-  NSR_HIP(hipFuncSetAttribute((const void*)nsr::k_render16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRender16Lds));
-  if (cfg->flags & NSR_FLAG_MLP_BF16X3) {
-    NSR_HIP(hipMalloc(&h->d_nets_b3, sizeof(float) * 3 * kB3Stride));
-    NSR_HIP(hipFuncSetAttribute((const void*)nsr::k_render_b3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRenderLds));
-    NSR_HIP(hipFuncSetAttribute((const void*)nsr::k_render_vjp_b3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRenderLds));
-  }
+  for (int im = 0; im < kImages; ++im)
+    if (kImageRows[im].create_flags == kEveryHandle || (cfg->flags & kImageRows[im].create_flags))
+      if (int e = alloc_image(h, (Image)im)) return e;
+  for (int dir = 0; dir < kDirs; ++dir)
+    for (int family = 0; family < kFamilies; ++family)
+      for (int form = 0; form < kForms; ++form) {
+        const Kernel& k = kKernels[dir][family][form];
+        if (k.fn && handle_launches(*cfg, family, (Form)form))
+          NSR_HIP(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds));
+      }
+  NSR_HIP(hipFuncSetAttribute((const void*)nsr::k_run_network, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kNetLds));
   if (cfg->flags & NSR_FLAG_MLP_F16X2) {
-    NSR_HIP(hipMalloc(&h->d_nets_h2, sizeof(float) * 3 * kH2Stride));
     NSR_HIP(hipMalloc(&h->d_args_fb, sizeof(nsr::RenderArgs)));
     NSR_HIP(hipMalloc(&h->d_vjp_args_fb, sizeof(nsr::VjpArgs)));
     NSR_HIP(hipMalloc(&h->d_ovf_items, sizeof(unsigned long long) * kOvfCap));
     h->ovf_cap = kOvfCap;
     NSR_HIP(hipMalloc(&h->d_ovf_stat, 4 * sizeof(unsigned)));
     NSR_HIP(hipMemset(h->d_ovf_stat, 0, 4 * sizeof(unsigned)));
-    NSR_HIP(hipFuncSetAttribute((const void*)nsr::k_render_h2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRenderLds));
-    NSR_HIP(hipFuncSetAttribute((const void*)nsr::k_render_vjp_h2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRenderLds));
-    // the safety net's fallback kernels: bf16x3 once nsr_upload_weights_b3 has been called on this handle
-    NSR_HIP(hipFuncSetAttribute((const void*)nsr::k_render_b3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRenderLds));
-    NSR_HIP(hipFuncSetAttribute((const void*)nsr::k_render_vjp_b3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRenderLds));
-    if (special_counts(cfg->n_samples, cfg->n_importance)) {
-      const KernelSet ks = special_kernels(cfg->n_samples, cfg->n_importance);
-      const int lds = (int)(cfg->n_samples == 128 ? kRenderLdsBig : kRenderLds);
-      for (const void* k : {(const void*)ks.h2, (const void*)ks.b3, (const void*)ks.vjp_h2, (const void*)ks.vjp_b3})
-        NSR_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    }
   }
   NSR_HIP(hipMalloc(&h->d_tables, sizeof(float) * 256));      // [N_samples <= 128] + [128]
   NSR_HIP(hipMalloc(&h->d_scratch, sizeof(float) * 4096));
   NSR_HIP(hipMalloc(&h->d_args, sizeof(nsr::RenderArgs)));
   NSR_HIP(hipMalloc(&h->d_work_counter, 2 * sizeof(unsigned long long)));
   // k_render16's inter-phase scratch: bounded by the grid (2 workgroups per CU, or max_workgroups) x chunk
-  h->zf_grid = cfg->max_workgroups > 0 ? cfg->max_workgroups : 2 * h->n_cu;
-  size_t zf_rays = (size_t)h->zf_grid * h->chunk;
+  size_t zf_rays = (size_t)x16_grid(*cfg, h->n_cu) * queue_chunk(*cfg);
   if (cfg->flags & NSR_FLAG_SCHED_PHASES) {                // the z hand-off ring of the global-phases schedule
     if (const char* e = getenv("NSR_EXP_SUPER_LG")) {      // experiment knob (super-chunk size), read at setup only
       const int v = atoi(e);
-      if (v >= 6 && v <= 20) kSuperLg = v;
+      if (v >= 6 && v <= 20) h->super_lg = v;
     }
-    zf_rays = (size_t)3 << kSuperLg;
+    zf_rays = (size_t)3 << h->super_lg;
     NSR_HIP(hipMalloc(&h->d_sched_flags, sizeof(unsigned) * 2 * zf_rays));
     NSR_HIP(hipMalloc(&h->d_status, 2 * sizeof(unsigned)));      // [0] recomputed rays, [1] launch epoch (device-side counter)
     NSR_HIP(hipMemset(h->d_status, 0, 2 * sizeof(unsigned)));
-    NSR_HIP(hipFuncSetAttribute((const void*)nsr::k_render16p, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRender16Lds));
-    NSR_HIP(hipFuncSetAttribute((const void*)nsr::k_render_vjp16p, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kVjp16Lds));
   }
   // (global phases: 8-byte {value, tag} granules, hence twice the floats)
   NSR_HIP(hipMalloc(&h->d_zf_scratch, sizeof(float) * 192 * zf_rays * ((cfg->flags & NSR_FLAG_SCHED_PHASES) ? 2 : 1)));
   NSR_HIP(hipEventCreateWithFlags(&h->ev_busy, hipEventDisableTiming));
   NSR_HIP(hipMalloc(&h->d_vjp_args, sizeof(nsr::VjpArgs)));
-  NSR_HIP(hipFuncSetAttribute((const void*)nsr::k_render_vjp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRenderLds));
   NSR_HIP(hipEventCreate(&h->ev0));
   NSR_HIP(hipEventCreate(&h->ev1));
-  NSR_HIP(hipFuncSetAttribute((const void*)nsr::k_render, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRenderLds));
-  NSR_HIP(hipFuncSetAttribute((const void*)nsr::k_run_network, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kNetLds));
+  return 0;
+}
+
+static int alloc_mask_scratch(nsr_handle h) {
+  if (h->d_mask_scratch) return 0;   // setup call: the VJP kernels' relu-pattern scratch, one block per x32 workgroup (16 B entries)
+  const int passes = h->cfg.n_samples == 128 ? 4 : 3;      // fine forward passes per item (render_vjp32_body: kMaskPasses)
+  NSR_HIP(hipMalloc(&h->d_mask_scratch, sizeof(uint4) * (size_t)x32_grid(h->cfg, h->n_cu) * passes * 9 * 256));
+  return 0;
+}
+
+// The eight nsr_upload_weights* entry points: a forward image of network `slot` (0 coarse, 1 fine; stream + aux block), or -- `bwd`,
+// slot 2 -- the transposed stream of the fine network, into the family's buffer
+static int upload(nsr_handle h, Image im, int slot, bool bwd, const float* src, size_t n_floats) {
+  const ImageRow& row = kImageRows[im];
+  const std::string who = std::string(bwd ? "nsr_upload_weights_bwd" : "nsr_upload_weights") + row.suffix;
+  if (!h || !src) return fail(who + ": null argument");
+  if (row.upload_flags != kEveryHandle && !(h->cfg.flags & row.upload_flags)) return fail(who + row.refusal);
+  if (!bwd && (slot < 0 || slot > 1)) return fail(who + ": net_id must be 0 (coarse) or 1 (fine)");
+  if (n_floats != (bwd ? row.bwd_stream : row.fwd_floats)) return fail(who + (bwd ? ": wrong stream size" : ": wrong packed size"));
+  NSR_DEVICE(h);
+  if (int e = alloc_image(h, im)) return e;      // (setup call)
+  NSR_HIP(hipMemcpy(h->img[im].d + (size_t)slot * row.stride, src, sizeof(float) * n_floats, hipMemcpyHostToDevice));
+  if (bwd) { if (int e = alloc_mask_scratch(h)) return e; }
+  h->img[im].have[slot] = true;
   return 0;
 }
 
@@ -230,27 +394,7 @@ int nsr_abi_version(void) { return NSR_ABI_VERSION; }
 
 int nsr_create(const NsrConfig* cfg, nsr_handle* out) {
   if (!cfg || !out) return fail("nsr_create: null argument");
-  if (cfg->abi_version != NSR_ABI_VERSION) return fail("nsr_create: ABI version mismatch");
-  if ((cfg->flags & NSR_FLAG_MLP_BF16X3) && (cfg->flags & NSR_FLAG_MLP_F16X2))
-    return fail("nsr_create: NSR_FLAG_MLP_BF16X3 and NSR_FLAG_MLP_F16X2 are mutually exclusive");
-  if (cfg->flags & ~(NSR_FLAG_WHITE_BKGD | NSR_FLAG_LINDISP | NSR_FLAG_SCHED_PHASES | NSR_FLAG_MLP_BF16X3 | NSR_FLAG_MLP_F16X2))
-    return fail("nsr_create: unknown bits in flags");
-  {
-    const int ns = cfg->n_samples, ni = cfg->n_importance;
-    const bool h2cfg = (cfg->flags & NSR_FLAG_MLP_F16X2) != 0;
-    const bool ok = (ns == NSR_N_SAMPLES && (ni == NSR_N_IMPORTANCE || ni == 0)) ||
-                    (h2cfg && ns == NSR_N_SAMPLES && (ni == 96 || ni == 64 || ni == 32)) ||
-                    (h2cfg && ns == 32 && (ni == 64 || ni == 0)) || (h2cfg && ns == 128 && (ni == 128 || ni == 0));
-    if (!ok)
-      return fail("nsr_create: unsupported (N_samples, N_importance): (64, 128) and (64, 0) on every handle; on NSR_FLAG_MLP_F16X2 "
-                  "handles also (64, 96 / 64 / 32), (32, 64 / 0) and (128, 128 / 0) -- other handles render fewer importance samples "
-                  "with N_importance = 128 and a uniforms table of repeated values (engine._host_tables)");
-  }
-  if ((cfg->flags & NSR_FLAG_SCHED_PHASES) && (cfg->variant == 32 || cfg->n_importance == 0))
-    return fail("nsr_create: NSR_FLAG_SCHED_PHASES applies to the x16 coarse+fine forward kernel only");
-  if (cfg->chunk < 0 || cfg->chunk > 256) return fail("nsr_create: chunk must be 0 (default) or 1..256");
-  if (cfg->variant != 0 && cfg->variant != 16 && cfg->variant != 32)
-    return fail("nsr_create: variant must be 0 (default), 16 or 32");
+  if (const char* m = config_error(*cfg)) return fail(m);
   int ndev = 0;
   NSR_HIP(hipGetDeviceCount(&ndev));
   if (cfg->device < 0 || cfg->device >= ndev) return fail("nsr_create: no such HIP device");
@@ -262,7 +406,6 @@ int nsr_create(const NsrConfig* cfg, nsr_handle* out) {
   nsr_handle h = new nsr_handle_s();
   h->cfg = *cfg;
   h->n_cu = prop.multiProcessorCount;
-  h->chunk = (cfg->chunk > 0 && !(cfg->flags & NSR_FLAG_SCHED_PHASES)) ? cfg->chunk : 1;
   if (int e = allocate_handle(h)) {          // nothing half-built escapes: free whatever was allocated
     const std::string msg = g_err;
     nsr_destroy(h);
@@ -276,10 +419,7 @@ int nsr_destroy(nsr_handle h) {
   if (!h) return 0;
   DeviceGuard guard_(h->cfg.device);
   hipDeviceSynchronize();
-  hipFree(h->d_nets);
-  hipFree(h->d_nets16);
-  hipFree(h->d_nets_b3);
-  hipFree(h->d_nets_h2);
+  for (auto& im : h->img) hipFree(im.d);
   hipFree(h->d_tables);
   hipFree(h->d_scratch);
   hipFree(h->d_args);
@@ -302,104 +442,14 @@ int nsr_destroy(nsr_handle h) {
   return 0;
 }
 
-int nsr_upload_weights(nsr_handle h, int net_id, const float* packed, size_t n_floats) {
-  if (!h || !packed) return fail("nsr_upload_weights: null argument");
-  if (net_id < 0 || net_id > 1) return fail("nsr_upload_weights: net_id must be 0 (coarse) or 1 (fine)");
-  if (n_floats != (size_t)NSR_PACKED_FLOATS) return fail("nsr_upload_weights: wrong packed size");
-  NSR_DEVICE(h);
-  NSR_HIP(hipMemcpy(h->d_packed[net_id], packed, sizeof(float) * n_floats, hipMemcpyHostToDevice));
-  h->have_net[net_id] = true;
-  return 0;
-}
-
-int nsr_upload_weights16(nsr_handle h, int net_id, const float* packed, size_t n_floats) {
-  if (!h || !packed) return fail("nsr_upload_weights16: null argument");
-  if (net_id < 0 || net_id > 1) return fail("nsr_upload_weights16: net_id must be 0 (coarse) or 1 (fine)");
-  if (n_floats != (size_t)NSR_PACKED_FLOATS) return fail("nsr_upload_weights16: wrong packed size");
-  NSR_DEVICE(h);
-  if (!h->d_nets16) NSR_HIP(hipMalloc(&h->d_nets16, sizeof(float) * 3 * NSR_PACKED_FLOATS));      // setup call
-  NSR_HIP(hipMemcpy(h->d_nets16 + (size_t)net_id * NSR_PACKED_FLOATS, packed, sizeof(float) * n_floats,
-                    hipMemcpyHostToDevice));
-  h->have_net16[net_id] = true;
-  return 0;
-}
-
-int nsr_upload_weights_b3(nsr_handle h, int net_id, const float* packed, size_t n_floats) {
-  if (!h || !packed) return fail("nsr_upload_weights_b3: null argument");
-  if (!(h->cfg.flags & (NSR_FLAG_MLP_BF16X3 | NSR_FLAG_MLP_F16X2)))
-    return fail("nsr_upload_weights_b3: the handle was created with neither NSR_FLAG_MLP_BF16X3 nor NSR_FLAG_MLP_F16X2");
-  if (net_id < 0 || net_id > 1) return fail("nsr_upload_weights_b3: net_id must be 0 (coarse) or 1 (fine)");
-  if (n_floats != (size_t)NSR_PACKED_B3_FLOATS) return fail("nsr_upload_weights_b3: wrong packed size");
-  NSR_DEVICE(h);
-  if (!h->d_nets_b3) NSR_HIP(hipMalloc(&h->d_nets_b3, sizeof(float) * 3 * kB3Stride));      // f16x2 handle: the fallback's images (setup call)
-  NSR_HIP(hipMemcpy(h->d_nets_b3 + (size_t)net_id * kB3Stride, packed, sizeof(float) * n_floats, hipMemcpyHostToDevice));
-  h->have_net_b3[net_id] = true;
-  return 0;
-}
-
-static int alloc_mask_scratch(nsr_handle h) {
-  if (h->d_mask_scratch) return 0;   // setup call: the VJP kernels' relu-pattern scratch, one block per workgroup
-  h->mask_grid = h->cfg.max_workgroups > 0 ? h->cfg.max_workgroups : h->n_cu;     // in x32 workgroups (16 B entries)
-  const int passes = h->cfg.n_samples == 128 ? 4 : 3;      // fine forward passes per item (render_vjp32_body: kMaskPasses)
-  NSR_HIP(hipMalloc(&h->d_mask_scratch, sizeof(uint4) * (size_t)h->mask_grid * passes * 9 * 256));
-  return 0;
-}
-
-int nsr_upload_weights_bwd(nsr_handle h, const float* stream, size_t n_floats) {
-  if (!h || !stream) return fail("nsr_upload_weights_bwd: null argument");
-  if (n_floats != (size_t)NSR_STREAM_SLABS * NSR_SLAB_FLOATS) return fail("nsr_upload_weights_bwd: wrong stream size");
-  NSR_DEVICE(h);
-  NSR_HIP(hipMemcpy(h->d_packed[2], stream, sizeof(float) * n_floats, hipMemcpyHostToDevice));
-  if (int e = alloc_mask_scratch(h)) return e;
-  h->have_net[2] = true;
-  return 0;
-}
-
-int nsr_upload_weights_h2(nsr_handle h, int net_id, const float* packed, size_t n_floats) {
-  if (!h || !packed) return fail("nsr_upload_weights_h2: null argument");
-  if (!(h->cfg.flags & NSR_FLAG_MLP_F16X2)) return fail("nsr_upload_weights_h2: the handle was not created with NSR_FLAG_MLP_F16X2");
-  if (net_id < 0 || net_id > 1) return fail("nsr_upload_weights_h2: net_id must be 0 (coarse) or 1 (fine)");
-  if (n_floats != (size_t)NSR_PACKED_FLOATS) return fail("nsr_upload_weights_h2: wrong packed size");
-  NSR_DEVICE(h);
-  NSR_HIP(hipMemcpy(h->d_nets_h2 + (size_t)net_id * kH2Stride, packed, sizeof(float) * n_floats, hipMemcpyHostToDevice));
-  h->have_net_h2[net_id] = true;
-  return 0;
-}
-
-int nsr_upload_weights_bwd_h2(nsr_handle h, const float* stream, size_t n_floats) {
-  if (!h || !stream) return fail("nsr_upload_weights_bwd_h2: null argument");
-  if (!(h->cfg.flags & NSR_FLAG_MLP_F16X2)) return fail("nsr_upload_weights_bwd_h2: the handle was not created with NSR_FLAG_MLP_F16X2");
-  if (n_floats != (size_t)NSR_STREAM_SLABS_H2_BWD * NSR_SLAB_FLOATS) return fail("nsr_upload_weights_bwd_h2: wrong stream size");
-  NSR_DEVICE(h);
-  NSR_HIP(hipMemcpy(h->d_nets_h2 + 2 * kH2Stride, stream, sizeof(float) * n_floats, hipMemcpyHostToDevice));
-  if (int e = alloc_mask_scratch(h)) return e;
-  h->have_net_h2[2] = true;
-  return 0;
-}
-
-int nsr_upload_weights_bwd_b3(nsr_handle h, const float* stream, size_t n_floats) {
-  if (!h || !stream) return fail("nsr_upload_weights_bwd_b3: null argument");
-  if (!(h->cfg.flags & (NSR_FLAG_MLP_BF16X3 | NSR_FLAG_MLP_F16X2)))
-    return fail("nsr_upload_weights_bwd_b3: the handle was created with neither NSR_FLAG_MLP_BF16X3 nor NSR_FLAG_MLP_F16X2");
-  if (n_floats != (size_t)NSR_STREAM_SLABS_B3_BWD * NSR_SLAB_FLOATS) return fail("nsr_upload_weights_bwd_b3: wrong stream size");
-  NSR_DEVICE(h);
-  if (!h->d_nets_b3) NSR_HIP(hipMalloc(&h->d_nets_b3, sizeof(float) * 3 * kB3Stride));      // (setup call)
-  NSR_HIP(hipMemcpy(h->d_nets_b3 + 2 * kB3Stride, stream, sizeof(float) * n_floats, hipMemcpyHostToDevice));
-  if (int e = alloc_mask_scratch(h)) return e;
-  h->have_net_b3[2] = true;
-  return 0;
-}
-
-int nsr_upload_weights_bwd16(nsr_handle h, const float* stream, size_t n_floats) {
-  if (!h || !stream) return fail("nsr_upload_weights_bwd16: null argument");
-  if (n_floats != (size_t)NSR_STREAM_SLABS * NSR_SLAB_FLOATS) return fail("nsr_upload_weights_bwd16: wrong stream size");
-  NSR_DEVICE(h);
-  if (!h->d_nets16) NSR_HIP(hipMalloc(&h->d_nets16, sizeof(float) * 3 * NSR_PACKED_FLOATS));      // setup call
-  NSR_HIP(hipMemcpy(h->d_nets16 + (size_t)2 * NSR_PACKED_FLOATS, stream, sizeof(float) * n_floats, hipMemcpyHostToDevice));
-  if (int e = alloc_mask_scratch(h)) return e;
-  h->have_net16[2] = true;
-  return 0;
-}
+int nsr_upload_weights(nsr_handle h, int net_id, const float* packed, size_t n) { return upload(h, kX32, net_id, false, packed, n); }
+int nsr_upload_weights16(nsr_handle h, int net_id, const float* packed, size_t n) { return upload(h, kX16, net_id, false, packed, n); }
+int nsr_upload_weights_b3(nsr_handle h, int net_id, const float* packed, size_t n) { return upload(h, kB3, net_id, false, packed, n); }
+int nsr_upload_weights_h2(nsr_handle h, int net_id, const float* packed, size_t n) { return upload(h, kH2, net_id, false, packed, n); }
+int nsr_upload_weights_bwd(nsr_handle h, const float* stream, size_t n) { return upload(h, kX32, 2, true, stream, n); }
+int nsr_upload_weights_bwd16(nsr_handle h, const float* stream, size_t n) { return upload(h, kX16, 2, true, stream, n); }
+int nsr_upload_weights_bwd_b3(nsr_handle h, const float* stream, size_t n) { return upload(h, kB3, 2, true, stream, n); }
+int nsr_upload_weights_bwd_h2(nsr_handle h, const float* stream, size_t n) { return upload(h, kH2, 2, true, stream, n); }
 
 int nsr_upload_tables(nsr_handle h, const float* t_coarse, int n_coarse, const float* u_fine, int n_fine) {
   if (!h || !t_coarse || !u_fine) return fail("nsr_upload_tables: null argument");
@@ -412,22 +462,12 @@ int nsr_upload_tables(nsr_handle h, const float* t_coarse, int n_coarse, const f
   return 0;
 }
 
-static int check_ready(nsr_handle h, bool need_fine) {
-  if (!h) return fail("null handle");
-  if (!h->have_tables) return fail("tables not uploaded (nsr_upload_tables)");
-  if (!h->have_net[0]) return fail("coarse network not uploaded (nsr_upload_weights net_id 0)");
-  if (need_fine && !h->have_net[1]) return fail("fine network not uploaded (nsr_upload_weights net_id 1)");
-  return 0;
-}
+}  // extern "C"
 
 static int grid_for(nsr_handle h, long long n_items) {
-  long long g = h->cfg.max_workgroups > 0 ? h->cfg.max_workgroups : h->n_cu;
-  if (g > n_items) g = n_items;
+  const long long g = std::min(x32_grid(h->cfg, h->n_cu), n_items);
   return (int)(g < 1 ? 1 : g);
 }
-
-// library default (variant 0) = x16: measured 145.0 vs 141.5 TFLOP/s for x32 on one 400x400 view (tools/compare_variants.py)
-static bool use_x16(nsr_handle h) { return h->cfg.variant != 32; }
 
 // f16x2 range safety net: the list must hold every item of the launch (each may overflow), so that none is dropped.
 // Grows geometrically; the outgrown list is RETIRED, never freed while the handle lives (see nsr_handle_s::retired), and
@@ -464,128 +504,83 @@ static int ensure_range(nsr_handle h, long long n_rays, bool capturing) {
   return 0;
 }
 
-static int launch_render(nsr_handle h, nsr::RenderArgs& a, const NsrRenderOut* out, const NsrDebugOut* dbg,
-                         void* stream) {
-  const bool fine = h->cfg.n_importance > 0;
-  const int ni = h->cfg.n_importance;                      // 64 / 32: the kernels specialised to that many importance samples
-  const bool b3 = (h->cfg.flags & NSR_FLAG_MLP_BF16X3) != 0;
-  const bool h2 = (h->cfg.flags & NSR_FLAG_MLP_F16X2) != 0;
-  // the per-ray extras (NsrRayExtras) are read by the x32-structured kernels: an fp32 handle serves them with k_render
-  // (its x32 stream is always uploaded, see check_ready) whatever its `variant`
-  const bool extras = a.viewdirs || a.t_rand || a.u_rays || a.noise0 || a.noise1 || a.near_rays;
-  const bool x16 = use_x16(h) && !b3 && !h2 && !extras;
-  if (int e = check_ready(h, fine)) return e;
-  if (h2 && (!h->have_net_h2[0] || (fine && !h->have_net_h2[1])))
-    return fail("NSR_FLAG_MLP_F16X2 needs nsr_upload_weights_h2 for every network");
-  if (x16 && (!h->have_net16[0] || (fine && !h->have_net16[1])))
-    return fail("variant 16 needs nsr_upload_weights16 for every network");
-  if (b3 && (!h->have_net_b3[0] || (fine && !h->have_net_b3[1])))
-    return fail("NSR_FLAG_MLP_BF16X3 needs nsr_upload_weights_b3 for every network");
-  if (!out || !out->d_rgb || !out->d_disp || !out->d_acc) return fail("render: rgb/disp/acc outputs are required");
-  if (a.n_rays <= 0) return 0;
-  NSR_DEVICE(h);
-  float* nets = h2 ? h->d_nets_h2 : (b3 ? h->d_nets_b3 : (x16 ? h->d_nets16 : h->d_nets));
-  const size_t net_floats = b3 ? kB3Stride : (h2 ? kH2Stride : (size_t)NSR_PACKED_FLOATS);
-  const size_t stream_floats = (size_t)(b3 ? NSR_STREAM_SLABS_B3 : NSR_STREAM_SLABS) * NSR_SLAB_FLOATS;
+static PlanIn plan_in(nsr_handle h, Dir dir, bool extras, bool taps, bool z_fine, long long n_rays) {
+  unsigned have = h->have_tables ? kHaveTables : 0u;
+  for (int im = 0; im < kImages; ++im)
+    for (unsigned slot = 0; slot < 3; ++slot)
+      if (h->img[im].have[slot]) have |= have_bits((Image)im, 1u << slot);
+  return PlanIn{h->cfg, h->n_cu, have, dir, extras, taps, z_fine, n_rays};
+}
+
+// the argument block reads the networks of one family: slot 0 coarse, slot 1 fine (a coarse-only handle: the coarse one again)
+static void point_at(nsr::RenderArgs& a, nsr_handle h, Image im, bool fine) {
+  const ImageRow& row = kImageRows[im];
+  float* nets = h->img[im].d;
   a.nets = nets;
-  a.net_stride = (long long)sizeof(float) * (long long)net_floats;
-  a.aux[0] = nets + stream_floats;
-  a.aux[1] = nets + (fine ? net_floats : 0) + stream_floats;
+  a.net_stride = (long long)sizeof(float) * (long long)row.stride;
+  a.aux[0] = nets + row.fwd_stream;
+  a.aux[1] = nets + (fine ? row.stride : 0) + row.fwd_stream;
+}
+
+static void set_args(const nsr::RenderArgs& a, nsr::RenderArgs* dst, hipStream_t s) {
+  hipLaunchKernelGGL(nsr::k_set_args, dim3(1), dim3(1), 0, s, a, dst);
+}
+static void set_args(const nsr::VjpArgs& v, nsr::VjpArgs* dst, hipStream_t s) {
+  hipLaunchKernelGGL(nsr::k_set_vjp_args, dim3(1), dim3(1), 0, s, v, dst);
+}
+static nsr::RenderArgs& render_args(nsr::RenderArgs& a) { return a; }
+static nsr::RenderArgs& render_args(nsr::VjpArgs& v) { return v.r; }
+
+// The one launch tail of the render and the input-gradient call: `args` holds what the caller passed in; the handle's side of the
+// block is filled in here, after the range list has its size for this launch.
+template <class Args>
+static int run(nsr_handle h, const Plan& p, Args& args, Args* d_args, Args* d_args_fb, void* stream) {
+  typedef void (*Fn)(const Args*);
+  nsr::RenderArgs& a = render_args(args);
+  const bool fine = h->cfg.n_importance > 0;
+  NSR_DEVICE(h);
+  hipStream_t s = (hipStream_t)stream;
+  bool capturing = false;
+  if (int e = stream_capturing(s, &capturing)) return e;
+  if (int e = claim_stream(h, s, capturing)) return e;
+  if (p.h2) { if (int e = ensure_range(h, a.n_rays, capturing)) return e; }
+  point_at(a, h, p.image, fine);
+#ifdef NSR_EXP_SAMENET       // timing experiment: every pass streams the SAME weight image (L2-resident); results are wrong
+  if (std::is_same<Args, nsr::RenderArgs>::value) a.net_stride = 0;
+#endif
   a.tcoarse = h->d_tables;
   a.ufine = h->d_tables + 128;
   a.fine = fine ? 1 : 0;
   a.white_bkgd = (h->cfg.flags & NSR_FLAG_WHITE_BKGD) ? 1 : 0;
   a.lindisp = (h->cfg.flags & NSR_FLAG_LINDISP) ? 1 : 0;
-  a.rgb = out->d_rgb; a.disp = out->d_disp; a.acc = out->d_acc;
-  a.rgb0 = out->d_rgb0; a.disp0 = out->d_disp0; a.acc0 = out->d_acc0; a.z_std = out->d_z_std;
-  a.dbg_w0 = dbg ? dbg->d_weights0 : nullptr;
-  a.dbg_zs = dbg ? dbg->d_z_samples : nullptr;
-  a.dbg_zf = dbg ? dbg->d_z_fine : nullptr;
-  a.dbg_raw0 = dbg ? dbg->d_raw0 : nullptr;
-  a.dbg_raw = dbg ? dbg->d_raw : nullptr;
-  a.dbg_inds = dbg ? (long long*)dbg->d_inds : nullptr;
-  hipStream_t s = (hipStream_t)stream;
-  bool capturing = false;
-  if (int e = stream_capturing(s, &capturing)) return e;
-  if (int e = claim_stream(h, s, capturing)) return e;
-  if (h2) { if (int e = ensure_range(h, a.n_rays, capturing)) return e; }
-  long long g = 0;
-  const bool phases = x16 && fine && (h->cfg.flags & NSR_FLAG_SCHED_PHASES);
-  if (phases) {                                            // global-phases schedule: k_render16p
-    g = h->zf_grid;
-    if (g > 2 * a.n_rays) g = 2 * a.n_rays;
+  a.work_counter = h->d_work_counter;
+  if (p.h2) { a.ovf_items = h->d_ovf_items; a.ovf_stat = h->d_ovf_stat; a.ovf_cap = p.ovf_armed ? h->ovf_cap : 0u; }
+  if (p.phases) {
     a.zf_scratch = h->d_zf_scratch;
     a.sched_flags = h->d_sched_flags;
     a.status = h->d_status;
-    a.super_lg = kSuperLg;
+    a.super_lg = h->super_lg;
     a.spin_max = h->cfg.chunk > 0 ? h->cfg.chunk - 1 : 64;   // looks at the ready flag before recomputing locally
-    a.epoch_counter = h->d_status + 1;                     // k_set_args advances it in stream order (also under graph replay)
-    a.chunk = 1;
-    NSR_HIP(hipMemsetAsync(h->d_sched_flags, 0, sizeof(unsigned) * 2 * ((size_t)3 << kSuperLg), s));
-  } else if (x16) {
-    g = h->zf_grid;                                        // two workgroups per CU (or max_workgroups)
-    // rays per chunk (see k_render16).  Larger chunks keep one network per L2 for longer (less fabric traffic), but
-    // the chunk is also the granularity of the dynamic load balance between the unevenly progressing workgroups:
-    // measured 1 -> 148.2, 2 -> 148.0, 4 -> 148.0, 8 -> 147.9, 16 -> 145.9 TFLOP/s.  Speed wins: the default is 1
-    // (NsrConfig.chunk).
-    int chunk = h->chunk;
-    if ((long long)chunk * g > a.n_rays) chunk = (int)(a.n_rays / g > 1 ? a.n_rays / g : 1);   // small batches: keep every CU busy
-    const long long n_chunks = (a.n_rays + chunk - 1) / chunk;
-    if (g > n_chunks) g = n_chunks;
-    a.zf_scratch = h->d_zf_scratch;
-    a.chunk = chunk;
-  } else {
-    g = grid_for(h, (a.n_rays + 1) / 2);
+    a.epoch_counter = h->d_status + 1;                     // the set-args kernel advances it in stream order (also under graph replay)
+    NSR_HIP(hipMemsetAsync(h->d_sched_flags, 0, sizeof(unsigned) * 2 * ((size_t)3 << h->super_lg), s));
   }
-  a.work_counter = h->d_work_counter;
-  // (the kernels specialised to other sample counts have a bf16x3 fallback only: without nsr_upload_weights_b3 every reported item is
-  // dropped -- NaN outputs, counted)
-  const int ns = h->cfg.n_samples;
-  const bool special = special_counts(ns, ni);            // f16x2 handles only (nsr_create): kernels specialised to the counts
-  const size_t lds32 = ns == 128 ? kRenderLdsBig : kRenderLds;
-  const bool have_fb = h2 && ((h->have_net_b3[0] && (!fine || h->have_net_b3[1])) || !special);
-  if (h2) { a.ovf_items = h->d_ovf_items; a.ovf_stat = h->d_ovf_stat; a.ovf_cap = have_fb ? h->ovf_cap : 0u; }
-#ifdef NSR_EXP_SAMENET       // timing experiment: every pass streams the SAME weight image (L2-resident); results are wrong
-  a.net_stride = 0;
-#endif
-  hipLaunchKernelGGL(nsr::k_set_args, dim3(1), dim3(1), 0, s, a, h->d_args);     // also zeroes the work counter
+  set_args(args, d_args, s);                               // also zeroes the work counter
   if (!capturing) NSR_HIP(hipEventRecord(h->ev0, s));
-  if (phases)
-    hipLaunchKernelGGL(nsr::k_render16p, dim3((int)g), dim3(256), kRender16Lds, s, (const nsr::RenderArgs*)h->d_args);
-  else if (x16)
-    hipLaunchKernelGGL(nsr::k_render16, dim3((int)g), dim3(256), kRender16Lds, s, (const nsr::RenderArgs*)h->d_args);
-  else if (b3)
-    hipLaunchKernelGGL(nsr::k_render_b3, dim3((int)g), dim3(256), kRenderLds, s, (const nsr::RenderArgs*)h->d_args);
-  else if (h2 && special)
-    hipLaunchKernelGGL(special_kernels(ns, ni).h2, dim3((int)g), dim3(256), lds32, s, (const nsr::RenderArgs*)h->d_args);
-  else if (h2)
-    hipLaunchKernelGGL(nsr::k_render_h2, dim3((int)g), dim3(256), kRenderLds, s, (const nsr::RenderArgs*)h->d_args);
-  else
-    hipLaunchKernelGGL(nsr::k_render, dim3((int)g), dim3(256), kRenderLds, s, (const nsr::RenderArgs*)h->d_args);
-#ifndef NSR_EXP_NO_RANGE
-  if (have_fb) {
-    // f16x2 range safety net: the items k_render_h2 reported (a NaN network output: a scaled activation beyond the fp16
-    // range) are rendered again by the fp32 kernel of the same template, which overwrites their outputs.  The list and
-    // its length stay on the device; with an empty list every workgroup of this launch returns at once.
-    nsr::RenderArgs f = a;
-    // ... on bf16 MFMAs (three-way split: fp32's exponent range, no failure domain, 1.7x the fp32-MFMA kernel) once the
-    // handle holds the bf16x3 images (nsr_upload_weights_b3; the Python engine uploads them), else on fp32 MFMAs
-    const bool fb3 = h->have_net_b3[0] && (!fine || h->have_net_b3[1]);
-    float* fnets = fb3 ? h->d_nets_b3 : h->d_nets;
-    const size_t fnet_floats = fb3 ? kB3Stride : (size_t)NSR_PACKED_FLOATS;
-    const size_t fstream_floats = (size_t)(fb3 ? NSR_STREAM_SLABS_B3 : NSR_STREAM_SLABS) * NSR_SLAB_FLOATS;
-    f.nets = fnets;
-    f.net_stride = (long long)sizeof(float) * (long long)fnet_floats;
-    f.aux[0] = fnets + fstream_floats;
-    f.aux[1] = fnets + (fine ? fnet_floats : 0) + fstream_floats;
-    f.ovf_items = nullptr; f.ovf_stat = nullptr; f.ovf_cap = 0;
-    f.item_list = h->d_ovf_items; f.item_count = h->d_ovf_stat; f.item_cap = h->ovf_cap;
-    f.work_counter = h->d_work_counter + 1;
-    hipLaunchKernelGGL(nsr::k_set_args, dim3(1), dim3(1), 0, s, f, h->d_args_fb);
-    RenderKernel fk = fb3 ? (special ? special_kernels(ns, ni).b3 : nsr::k_render_b3) : nsr::k_render;
-    hipLaunchKernelGGL(fk, dim3((int)g), dim3(256), lds32, s, (const nsr::RenderArgs*)h->d_args_fb);
+  const Fn kernel = (Fn)p.kernel->fn;
+  hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(256), p.kernel->lds, s, (const Args*)d_args);
+  if (p.fallback) {
+    // the reported items again on the fallback kernel, which overwrites their outputs.  The list and its length stay on the
+    // device; with an empty list every workgroup of this launch returns at once.
+    Args f = args;
+    nsr::RenderArgs& fa = render_args(f);
+    point_at(fa, h, p.fallback_image, fine);
+    fa.ovf_items = nullptr; fa.ovf_stat = nullptr; fa.ovf_cap = 0;
+    fa.item_list = h->d_ovf_items; fa.item_count = h->d_ovf_stat; fa.item_cap = h->ovf_cap;
+    fa.work_counter = h->d_work_counter + 1;
+    set_args(f, d_args_fb, s);
+    const Fn fallback = (Fn)p.fallback->fn;
+    hipLaunchKernelGGL(fallback, dim3(p.grid), dim3(256), p.fallback->lds, s, (const Args*)d_args_fb);
   }
-#endif
   NSR_HIP(hipGetLastError());
   if (!capturing) {
     NSR_HIP(hipEventRecord(h->ev1, s));
@@ -596,10 +591,46 @@ static int launch_render(nsr_handle h, nsr::RenderArgs& a, const NsrRenderOut* o
   return 0;
 }
 
+static int launch_render(nsr_handle h, nsr::RenderArgs& a, const NsrRenderOut* out, const NsrDebugOut* dbg, void* stream) {
+  if (!h) return fail("null handle");
+  const bool extras = a.viewdirs || a.t_rand || a.u_rays || a.noise0 || a.noise1 || a.near_rays;
+  const Plan p = plan_launch(plan_in(h, kRender, extras, false, false, a.n_rays));
+  if (p.refusal) return fail(p.refusal);
+  if (!out || !out->d_rgb || !out->d_disp || !out->d_acc) return fail("render: rgb/disp/acc outputs are required");
+  if (a.n_rays <= 0) return 0;
+  a.rgb = out->d_rgb; a.disp = out->d_disp; a.acc = out->d_acc;
+  a.rgb0 = out->d_rgb0; a.disp0 = out->d_disp0; a.acc0 = out->d_acc0; a.z_std = out->d_z_std;
+  a.dbg_w0 = dbg ? dbg->d_weights0 : nullptr;
+  a.dbg_zs = dbg ? dbg->d_z_samples : nullptr;
+  a.dbg_zf = dbg ? dbg->d_z_fine : nullptr;
+  a.dbg_raw0 = dbg ? dbg->d_raw0 : nullptr;
+  a.dbg_raw = dbg ? dbg->d_raw : nullptr;
+  a.dbg_inds = dbg ? (long long*)dbg->d_inds : nullptr;
+  if (p.image == kX16) { a.zf_scratch = h->d_zf_scratch; a.chunk = p.chunk; }
+  return run(h, p, a, h->d_args, h->d_args_fb, stream);
+}
+
 static void set_extras(nsr::RenderArgs& a, const NsrRayExtras* ex) {
   if (!ex) return;
   a.viewdirs = ex->d_viewdirs; a.t_rand = ex->d_t_rand; a.u_rays = ex->d_u; a.noise0 = ex->d_noise0; a.noise1 = ex->d_noise1;
   a.near_rays = ex->d_near; a.far_rays = ex->d_far;
+}
+
+extern "C" {
+
+int nsr_launch_plan(const NsrConfig* cfg, int n_cu, unsigned uploaded_bits, int direction, unsigned call_bits, int64_t n_rays,
+                    NsrLaunchPlan* out) {
+  if (!cfg || !out) return fail("nsr_launch_plan: null argument");
+  if (const char* m = config_error(*cfg)) return fail(m);
+  if (n_cu < 1 || n_rays < 1 || (direction != NSR_PLAN_RENDER && direction != NSR_PLAN_VJP))
+    return fail("nsr_launch_plan: n_cu and n_rays must be positive, direction NSR_PLAN_RENDER or NSR_PLAN_VJP");
+  const bool vjp = direction == NSR_PLAN_VJP;
+  const Plan p = plan_launch(PlanIn{*cfg, n_cu, uploaded_bits & (2 * kHaveTables - 1), vjp ? kVjp : kRender, (call_bits & NSR_CALL_EXTRAS) != 0,
+                                    vjp && (call_bits & NSR_CALL_TAPS), vjp && (call_bits & NSR_CALL_Z_FINE), n_rays});
+  if (p.refusal) return fail(p.refusal);
+  *out = NsrLaunchPlan{p.kernel->name, p.fallback ? p.fallback->name : nullptr, (int)p.image, p.fallback ? (int)p.fallback_image : -1,
+                       p.grid, p.kernel->lds, p.fallback ? p.fallback->lds : 0, p.chunk, p.phases ? 1 : 0, p.ovf_armed ? 1 : 0};
+  return 0;
 }
 
 int nsr_render_rays_ex(nsr_handle h, const float* d_rays_o, const float* d_rays_d, int64_t n_rays, float near_,
@@ -655,126 +686,28 @@ int nsr_render_rays_vjp_dbg(nsr_handle h, const float* d_rays_o, const float* d_
                             const NsrVjpDebugOut* dbg, void* stream) {
   if (h && n_rays == 0) return 0;      // an empty batch is a valid no-op (buffers may be null)
   if (!h) return fail("nsr_render_rays_vjp: null handle");
-  if (h->cfg.n_importance == 0) return fail("nsr_render_rays_vjp: needs the coarse+fine configuration (N_importance > 0)");
-  const int ni = h->cfg.n_importance;
-  if (int e = check_ready(h, true)) return e;
-  const bool b3 = (h->cfg.flags & NSR_FLAG_MLP_BF16X3) != 0;
-  // an f16x2 handle runs its input gradients on fp16 MFMAs too once the transposed stream is there (nsr_upload_weights_bwd_h2);
-  // without it the fp32 kernels of `variant` serve (they need their own uploads)
-  const bool h2 = (h->cfg.flags & NSR_FLAG_MLP_F16X2) && h->have_net_h2[0] && h->have_net_h2[1] && h->have_net_h2[2];
-  const int ns = h->cfg.n_samples;
-  const bool special = special_counts(ns, ni);
-  const size_t lds32 = ns == 128 ? kRenderLdsBig : kRenderLds;
-  if (special && !h2)
-    return fail("nsr_render_rays_vjp: a handle of these sample counts needs nsr_upload_weights_bwd_h2 (only the f16x2 kernels are specialised to them)");
   const bool extras = ex && (ex->d_viewdirs || ex->d_t_rand || ex->d_u || ex->d_noise0 || ex->d_noise1 || ex->d_near);
+  const bool taps = dbg && (dbg->d_relu_masks || dbg->d_grad_raw || dbg->d_grad_pts);
+  const Plan p = plan_launch(plan_in(h, kVjp, extras, taps, d_z_fine != nullptr, n_rays));
+  if (p.refusal && !p.kernel) return fail(p.refusal);
   if (ex && ((ex->d_near == nullptr) != (ex->d_far == nullptr))) return fail("nsr_render_rays_vjp_ex: d_near and d_far come together");
   if (d_grad_viewdirs && !(ex && ex->d_viewdirs))
     return fail("nsr_render_rays_vjp_ex: d_grad_viewdirs without d_viewdirs (the view directions are rays_d / |rays_d| then, "
                 "and their gradient is part of d_grad_d)");
-  const bool taps = dbg && (dbg->d_relu_masks || dbg->d_grad_raw || dbg->d_grad_pts);
-  const bool x16 = use_x16(h) && !b3 && !h2 && !extras && !taps;   // extras and debug taps: the x32-structured kernels
-  if (b3 && !(h->have_net_b3[0] && h->have_net_b3[1] && h->have_net_b3[2]))
-    return fail("nsr_render_rays_vjp: NSR_FLAG_MLP_BF16X3 needs nsr_upload_weights_b3 (both networks) and nsr_upload_weights_bwd_b3");
-  if (x16 && !(h->have_net16[0] && h->have_net16[1] && h->have_net16[2]))
-    return fail("nsr_render_rays_vjp: variant 16 needs nsr_upload_weights16 (both networks) and nsr_upload_weights_bwd16");
-  if (!x16 && !b3 && !h2 && !h->have_net[2]) return fail("nsr_render_rays_vjp: backward stream not uploaded (nsr_upload_weights_bwd)");
+  if (p.refusal) return fail(p.refusal);
   if (!d_rays_o || !d_rays_d || !d_grad_rgb || !d_grad_o || !d_grad_d) return fail("nsr_render_rays_vjp: null argument");
-  if (n_rays <= 0) return n_rays == 0 ? 0 : fail("nsr_render_rays_vjp: negative ray count");
-  NSR_DEVICE(h);
-  hipStream_t s = (hipStream_t)stream;
-  bool capturing = false;
-  if (int e = stream_capturing(s, &capturing)) return e;
-  if (int e = claim_stream(h, s, capturing)) return e;
-  if (h2) { if (int e = ensure_range(h, n_rays, capturing)) return e; }
-  long long grid;
-  if (x16) {                                               // one ray per item, two workgroups per CU
-    grid = h->cfg.max_workgroups > 0 ? h->cfg.max_workgroups : 2LL * h->n_cu;
-    if (grid > 2LL * h->mask_grid) grid = 2LL * h->mask_grid;   // scratch entries are half the size (uint2)
-    if (grid > n_rays) grid = n_rays;
-  } else {
-    grid = grid_for(h, (n_rays + 1) / 2);
-    if (grid > h->mask_grid) grid = h->mask_grid;          // the relu-pattern scratch was sized at upload time
-  }
+  if (n_rays < 0) return fail("nsr_render_rays_vjp: negative ray count");
   nsr::VjpArgs v;
   memset(&v, 0, sizeof(v));
   nsr::RenderArgs& a = v.r;
   a.rays_o = d_rays_o; a.rays_d = d_rays_d; a.n_rays = n_rays; a.near_ = near_; a.far_ = far_; a.camera = 0;
   set_extras(a, ex);
-  v.grad_viewdirs = d_grad_viewdirs;
-  float* nets = h2 ? h->d_nets_h2 : (b3 ? h->d_nets_b3 : (x16 ? h->d_nets16 : h->d_nets));
-  const size_t net_floats = b3 ? kB3Stride : (h2 ? kH2Stride : (size_t)NSR_PACKED_FLOATS);
-  const size_t stream_floats = (size_t)(b3 ? NSR_STREAM_SLABS_B3 : NSR_STREAM_SLABS) * NSR_SLAB_FLOATS;
-  a.nets = nets;
-  a.net_stride = (long long)sizeof(float) * (long long)net_floats;
-  a.aux[0] = nets + stream_floats;
-  a.aux[1] = nets + net_floats + stream_floats;
-  a.tcoarse = h->d_tables;
-  a.ufine = h->d_tables + 128;
-  a.fine = 1;
-  a.work_counter = h->d_work_counter;
-  a.white_bkgd = (h->cfg.flags & NSR_FLAG_WHITE_BKGD) ? 1 : 0;
-  a.lindisp = (h->cfg.flags & NSR_FLAG_LINDISP) ? 1 : 0;
   if (out) { a.rgb = out->d_rgb; a.disp = out->d_disp; a.acc = out->d_acc; }
+  v.grad_viewdirs = d_grad_viewdirs;
   v.grad_rgb = d_grad_rgb; v.grad_o = d_grad_o; v.grad_d = d_grad_d; v.mask_scratch = h->d_mask_scratch;
   v.z_fine = d_z_fine;
   if (dbg) { v.dbg_masks = (uint4*)dbg->d_relu_masks; v.dbg_graw = dbg->d_grad_raw; v.dbg_gpts = dbg->d_grad_pts; }
-  // f16x2 range safety net (see launch_render): the fallback runs on bf16 MFMAs when the handle holds the bf16x3 images
-  // and their transposed stream (nsr_upload_weights_b3 / _bwd_b3), else on fp32 MFMAs (nsr_upload_weights_bwd; N_importance
-  // 128 only); with neither, the reported items are dropped (NaN, counted)
-  const bool fb3 = h2 && h->have_net_b3[0] && h->have_net_b3[1] && h->have_net_b3[2];
-  const bool fallback = fb3 || (h2 && h->have_net[2] && !special);
-  if (h2) { a.ovf_items = h->d_ovf_items; a.ovf_stat = h->d_ovf_stat; a.ovf_cap = fallback ? h->ovf_cap : 0u; }
-  // global-phases schedule (k_render_vjp16p) unless the caller supplies the depths itself (then nothing is handed over)
-  const bool phases = x16 && (h->cfg.flags & NSR_FLAG_SCHED_PHASES) && !d_z_fine;
-  if (phases) {
-    a.zf_scratch = h->d_zf_scratch;
-    a.sched_flags = h->d_sched_flags;
-    a.status = h->d_status;
-    a.super_lg = kSuperLg;
-    a.spin_max = h->cfg.chunk > 0 ? h->cfg.chunk - 1 : 64;
-    a.epoch_counter = h->d_status + 1;
-    NSR_HIP(hipMemsetAsync(h->d_sched_flags, 0, sizeof(unsigned) * 2 * ((size_t)3 << kSuperLg), s));
-  }
-  hipLaunchKernelGGL(nsr::k_set_vjp_args, dim3(1), dim3(1), 0, s, v, h->d_vjp_args);   // also zeroes the work counter
-  if (!capturing) NSR_HIP(hipEventRecord(h->ev0, s));
-  if (phases)
-    hipLaunchKernelGGL(nsr::k_render_vjp16p, dim3((int)grid), dim3(256), kVjp16Lds, s, (const nsr::VjpArgs*)h->d_vjp_args);
-  else if (x16)
-    hipLaunchKernelGGL(nsr::k_render_vjp16, dim3((int)grid), dim3(256), kVjp16Lds, s, (const nsr::VjpArgs*)h->d_vjp_args);
-  else if (b3)
-    hipLaunchKernelGGL(nsr::k_render_vjp_b3, dim3((int)grid), dim3(256), kRenderLds, s, (const nsr::VjpArgs*)h->d_vjp_args);
-  else if (h2 && special)
-    hipLaunchKernelGGL(special_kernels(ns, ni).vjp_h2, dim3((int)grid), dim3(256), lds32, s, (const nsr::VjpArgs*)h->d_vjp_args);
-  else if (h2)
-    hipLaunchKernelGGL(nsr::k_render_vjp_h2, dim3((int)grid), dim3(256), kRenderLds, s, (const nsr::VjpArgs*)h->d_vjp_args);
-  else
-    hipLaunchKernelGGL(nsr::k_render_vjp, dim3((int)grid), dim3(256), kRenderLds, s, (const nsr::VjpArgs*)h->d_vjp_args);
-  if (fallback) {          // the reported items again, forward and backward, on the fp32 kernel of the same template
-    nsr::VjpArgs f = v;
-    nsr::RenderArgs& fa = f.r;
-    float* fnets = fb3 ? h->d_nets_b3 : h->d_nets;
-    const size_t fnet_floats = fb3 ? kB3Stride : (size_t)NSR_PACKED_FLOATS;
-    const size_t fstream_floats = (size_t)(fb3 ? NSR_STREAM_SLABS_B3 : NSR_STREAM_SLABS) * NSR_SLAB_FLOATS;
-    fa.nets = fnets;
-    fa.net_stride = (long long)sizeof(float) * (long long)fnet_floats;
-    fa.aux[0] = fnets + fstream_floats;
-    fa.aux[1] = fnets + fnet_floats + fstream_floats;
-    fa.ovf_items = nullptr; fa.ovf_stat = nullptr; fa.ovf_cap = 0;
-    fa.item_list = h->d_ovf_items; fa.item_count = h->d_ovf_stat; fa.item_cap = h->ovf_cap;
-    fa.work_counter = h->d_work_counter + 1;
-    hipLaunchKernelGGL(nsr::k_set_vjp_args, dim3(1), dim3(1), 0, s, f, h->d_vjp_args_fb);
-    VjpKernel fk = fb3 ? (special ? special_kernels(ns, ni).vjp_b3 : nsr::k_render_vjp_b3) : nsr::k_render_vjp;
-    hipLaunchKernelGGL(fk, dim3((int)grid), dim3(256), lds32, s, (const nsr::VjpArgs*)h->d_vjp_args_fb);
-  }
-  NSR_HIP(hipGetLastError());
-  if (!capturing) {
-    NSR_HIP(hipEventRecord(h->ev1, s));
-    NSR_HIP(hipEventRecord(h->ev_busy, s));
-  }
-  h->launched = true;
-  h->timed = !capturing;
-  return 0;
+  return run(h, p, v, h->d_vjp_args, h->d_vjp_args_fb, stream);
 }
 
 int nsr_pose_grad(nsr_handle h, const float* d_grad_o, const float* d_grad_d, int H, int W, const double* K9,
@@ -964,12 +897,12 @@ int nsr_run_network(nsr_handle h, int net_id, const float* d_pts, const float* d
                     float* d_raw, void* stream) {
   if (h && n_pts == 0) return 0;      // an empty batch is a valid no-op (buffers may be null)
   if (!h || !d_pts || !d_viewdirs || !d_raw) return fail("nsr_run_network: null argument");
-  if (net_id < 0 || net_id > 1 || !h->have_net[net_id]) return fail("nsr_run_network: network not uploaded");
+  if (net_id < 0 || net_id > 1 || !h->img[kX32].have[net_id]) return fail("nsr_run_network: network not uploaded");
   if (n_pts <= 0) return n_pts == 0 ? 0 : fail("nsr_run_network: negative point count");
   NSR_DEVICE(h);
   nsr::NetArgs a;
-  a.stream = h->d_packed[net_id];
-  a.aux = h->d_packed[net_id] + (size_t)NSR_STREAM_SLABS * NSR_SLAB_FLOATS;
+  a.stream = h->img[kX32].d + (size_t)net_id * kImageRows[kX32].stride;
+  a.aux = a.stream + kImageRows[kX32].fwd_stream;
   a.pts = d_pts; a.dirs = d_viewdirs; a.raw = d_raw; a.n_pts = n_pts;
   const long long tiles = (n_pts + 127) / 128;
   hipLaunchKernelGGL(nsr::k_run_network, dim3(grid_for(h, tiles)), dim3(256), kNetLds, (hipStream_t)stream, a);

@@ -3,6 +3,7 @@
 PyTorch is plumbing here: it owns the device buffers (torch tensors -> raw device pointers) and the stream;
 all arithmetic happens inside the hand-written gfx950 kernels.  Mirrors what the reference keeps in its
 `render_kwargs` dict (network_fn, network_fine, N_samples, N_importance; RN:318-334)."""
+import collections
 import ctypes as C
 import os
 
@@ -53,6 +54,42 @@ IMPORTANCE_COUNTS = (0, 1, 2, 4, 8, 16, 32, 64, 96, 128)   # 0 = coarse only; th
 NATIVE_IMPORTANCE = (96, 64, 32)   # f16x2 handles: kernels specialised to these counts (k_render_h2_n96 / _n64 / _n32 and their VJPs)
 # (N_samples, N_importance) pairs beyond N_samples = 64 that f16x2 handles serve with kernels of their own (r05; RN:439, RN:474)
 NATIVE_COUNTS = ((32, 64), (32, 0), (128, 128), (128, 0))
+
+
+# One row per family of weight image (csrc/nsr_api.hip: kImageRows): the packers of a forward image and of the fine network's
+# transposed stream, the two upload entry points, the floats of a forward image
+Image = collections.namedtuple("Image", "pack pack_bwd upload upload_bwd floats")
+IMAGES = {
+    "x32": Image(pack_network, pack_network_backward, "nsr_upload_weights", "nsr_upload_weights_bwd", PACKED_FLOATS),
+    "x16": Image(pack_network16, pack_network_backward16, "nsr_upload_weights16", "nsr_upload_weights_bwd16", PACKED_FLOATS),
+    "b3": Image(pack_network_b3, pack_network_backward_b3, "nsr_upload_weights_b3", "nsr_upload_weights_bwd_b3", PACKED_B3_FLOATS),
+    "h2": Image(pack_network_h2, pack_network_backward_h2, "nsr_upload_weights_h2", "nsr_upload_weights_bwd_h2", PACKED_FLOATS),
+}
+
+
+def handle_images(mlp, variant, range_fallback="bf16x3"):
+    """(forward, backward): the families whose forward images a handle holds, in upload order -- only what its kernels read: the
+    x32 fp32 image always (stage kernels; an fp32 handle's per-ray extras), the x16 image for fp32 handles of variant 0 / 16 only,
+    the bf16x3 image for bf16x3 handles and, as the fallback of the range safety net, for f16x2 handles -- and those whose
+    transposed stream of the fine network the first input gradient uploads: the kernel's own, then an f16x2 handle's fallback."""
+    if mlp == "f16x2":
+        fb = "b3" if range_fallback == "bf16x3" else "x32"
+        return ("x32", "b3", "h2") if fb == "b3" else ("x32", "h2"), ("h2", fb)
+    if mlp == "bf16x3":
+        return ("x32", "b3"), ("b3",)
+    return (("x32",), ("x32",)) if variant == 32 else (("x32", "x16"), ("x16",))      # 0 = library default = x16
+
+
+def launch_plan(cfg, n_cu, uploaded_bits, direction, call_bits, n_rays):
+    """nsr_launch_plan (diagnostic; no device, no handle): what a render (direction 0) or input-gradient (1) call of n_rays rays
+    launches on a handle of _lib.NsrConfig `cfg` on n_cu compute units -- see include/nsr.h for the two bit words.  Raises
+    NsrError with the launch call's message where that call refuses."""
+    plan = _lib.NsrLaunchPlan()
+    _lib.check(_lib.load().nsr_launch_plan(C.byref(cfg), int(n_cu), int(uploaded_bits), int(direction), int(call_bits), int(n_rays),
+                                           C.byref(plan)))
+    d = {name: getattr(plan, name) for name, _ in plan._fields_}
+    d.update(kernel=plan.kernel.decode(), fallback=plan.fallback.decode() if plan.fallback else None)
+    return d
 
 
 def _fptr(a):
@@ -155,40 +192,14 @@ class NsrModel:
     def upload(self, sd_coarse, sd_fine=None):
         to_np = lambda sd: {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v))
                             for k, v in sd.items()}
-        sd_c = to_np(sd_coarse)
-        p = pack_network(sd_c)
-        _lib.check(self.lib.nsr_upload_weights(self.h, 0, _fptr(p), PACKED_FLOATS))
-        # only the images this handle's kernels read: the x32 fp32 image always (stage kernels; an fp32 handle's per-ray
-        # extras), the x16 image for fp32 handles of variant 0 / 16 only, the bf16x3 image for bf16x3 handles and -- as the
-        # fallback of the range safety net -- for f16x2 handles
-        x16 = self.variant != 32 and self.mlp == "fp32"
-        if x16:
-            p = pack_network16(sd_c)
-            _lib.check(self.lib.nsr_upload_weights16(self.h, 0, _fptr(p), PACKED_FLOATS))
-        fb3 = self.mlp == "bf16x3" or (self.mlp == "f16x2" and self.range_fallback == "bf16x3")
-        if fb3:                                      # (f16x2: the images of the range safety net's bf16x3 fallback)
-            p = pack_network_b3(sd_c)
-            _lib.check(self.lib.nsr_upload_weights_b3(self.h, 0, _fptr(p), PACKED_B3_FLOATS))
-        if self.mlp == "f16x2":
-            p = pack_network_h2(sd_c)
-            _lib.check(self.lib.nsr_upload_weights_h2(self.h, 0, _fptr(p), PACKED_FLOATS))
-            self.h2_range = (h2_report(sd_c), None)
-        self._sd_fine_np = None
+        self._sd_fine_np = to_np(sd_fine) if sd_fine is not None else None
         self._bwd_ready = self._bwd32_ready = False     # both transposed streams belong to the previous fine network
-        if sd_fine is not None:
-            self._sd_fine_np = to_np(sd_fine)
-            p = pack_network(self._sd_fine_np)
-            _lib.check(self.lib.nsr_upload_weights(self.h, 1, _fptr(p), PACKED_FLOATS))
-            if x16:
-                p = pack_network16(self._sd_fine_np)
-                _lib.check(self.lib.nsr_upload_weights16(self.h, 1, _fptr(p), PACKED_FLOATS))
-            if fb3:
-                p = pack_network_b3(self._sd_fine_np)
-                _lib.check(self.lib.nsr_upload_weights_b3(self.h, 1, _fptr(p), PACKED_B3_FLOATS))
-            if self.mlp == "f16x2":
-                p = pack_network_h2(self._sd_fine_np)
-                _lib.check(self.lib.nsr_upload_weights_h2(self.h, 1, _fptr(p), PACKED_FLOATS))
-                self.h2_range = (self.h2_range[0], h2_report(self._sd_fine_np))
+        for net, sd in enumerate([to_np(sd_coarse)] + ([] if sd_fine is None else [self._sd_fine_np])):
+            for family in handle_images(self.mlp, self.variant, self.range_fallback)[0]:
+                im = IMAGES[family]
+                _lib.check(getattr(self.lib, im.upload)(self.h, net, _fptr(im.pack(sd)), im.floats))
+            if self.mlp == "f16x2":                  # pack-time range report of (coarse, fine)
+                self.h2_range = (h2_report(sd), None) if net == 0 else (self.h2_range[0], h2_report(sd))
 
     def close(self):
         if getattr(self, "h", None):
@@ -321,32 +332,15 @@ class NsrModel:
             raise NotImplementedError("the VJP kernel needs the coarse+fine configuration (N_importance > 0)")
         has_extras = bool(extras) and any(v is not None for v in extras.values())
         need32 = (has_extras or debug) and self.mlp == "fp32" and self.variant != 32
-        if need32 and not self._bwd32_ready:
-            # the fp32 x32 transposed stream: the extras and the debug taps are served by the x32-structured kernels (an fp32
-            # handle of another variant runs k_render_vjp for them)
-            b = pack_network_backward(self._sd_fine_np)
-            _lib.check(self.lib.nsr_upload_weights_bwd(self.h, _fptr(b), b.size))
-            self._bwd32_ready = True
-        if not self._bwd_ready:                      # the transposed stream is packed on first use only
-            if self.mlp == "bf16x3":
-                b = pack_network_backward_b3(self._sd_fine_np)
-                _lib.check(self.lib.nsr_upload_weights_bwd_b3(self.h, _fptr(b), b.size))
-            elif self.mlp == "f16x2":
-                b = pack_network_backward_h2(self._sd_fine_np)
-                _lib.check(self.lib.nsr_upload_weights_bwd_h2(self.h, _fptr(b), b.size))
-                if self.range_fallback == "bf16x3":                     # ... and the range safety net's fallback stream
-                    b = pack_network_backward_b3(self._sd_fine_np)
-                    _lib.check(self.lib.nsr_upload_weights_bwd_b3(self.h, _fptr(b), b.size))
-                else:
-                    b = pack_network_backward(self._sd_fine_np)
-                    _lib.check(self.lib.nsr_upload_weights_bwd(self.h, _fptr(b), b.size))
-            elif self.variant == 32:
-                b = pack_network_backward(self._sd_fine_np)
-                _lib.check(self.lib.nsr_upload_weights_bwd(self.h, _fptr(b), b.size))
-            else:                                    # 0 = library default = x16
-                b = pack_network_backward16(self._sd_fine_np)
-                _lib.check(self.lib.nsr_upload_weights_bwd16(self.h, _fptr(b), b.size))
-            self._bwd_ready = True
+        # the transposed streams are packed on first use only.  need32: the extras and the debug taps are served by the x32-structured
+        # kernels (an fp32 handle of another variant runs k_render_vjp for them)
+        families = (("x32",) if need32 and not self._bwd32_ready else ()) \
+            + (() if self._bwd_ready else handle_images(self.mlp, self.variant, self.range_fallback)[1])
+        for family in families:
+            b = IMAGES[family].pack_bwd(self._sd_fine_np)
+            _lib.check(getattr(self.lib, IMAGES[family].upload_bwd)(self.h, _fptr(b), b.size))
+        self._bwd32_ready = self._bwd32_ready or need32
+        self._bwd_ready = True
         rays_o = self._f32(rays_o, (-1, 3))
         rays_d = self._f32(rays_d, (-1, 3))
         n = rays_o.shape[0]
