@@ -43,6 +43,11 @@ enum { NSRW_FLAG_WHITE_BKGD = 1,     /* RN:384-385 */
                                       * weights pre-scaled per matrix, gradients normalised per point).  A network pass -- forward or
                                       * backward -- in which a value reaches fp16's largest number is run again on bf16x3 inside the
                                       * same call (nsrw_range_status counts them), so no result depends on the range. */
+enum { NSRW_FLAG_TRUNK_ONCHIP = 16 };/* opt-in, f16x2 handles only (nsrw_create refuses it without NSRW_FLAG_MLP_F16X2): a network of padded width
+                                      * <= 128 and depth >= 2 runs ALL its pts_linears in one launch with the activations in LDS
+                                      * (csrc/nsr_wide_trunk.inc) wherever no activation is kept for a backward -- the same arithmetic per
+                                      * output element, so the same bits as layer by layer.  Any other network on such a handle runs
+                                      * layer by layer, as do the bf16x3 re-runs (nsrw_trunk_plan says which). */
 
 typedef struct NsrwConfig {
   int32_t device;
@@ -195,9 +200,19 @@ typedef struct NsrwGemmPart {
 } NsrwGemmPart;
 int nsrw_gemm_plan(int n_packed_rows, int n_stored_columns, int tile_wm, NsrwGemmPart* parts_out, int max_parts);
 
+/* DIAGNOSTIC; needs no device and no handle.  How a handle created with `flags` runs the pts_linears of `net`: onchip = 1
+ * -- one kw_trunk_h2<nj> launch over tiles of tile_rows points with lds_bytes of LDS per workgroup -- or onchip = 0 (layer by layer;
+ * nj = tile_rows = lds_bytes = 0) with the reason.  Returns 0, or -1 for an invalid network description (nsrw_last_error says why). */
+typedef struct NsrwTrunkPlan {
+  int32_t onchip, nj, tile_rows, lds_bytes;
+  char reason[64];
+} NsrwTrunkPlan;
+int nsrw_trunk_plan(const NsrwNet* net, int flags, NsrwTrunkPlan* plan_out);
+
 /* libnsr_debug.so (-DNSR_DEBUG_BOUNDS) checks every global / LDS index of this unit's kernels against its extent; a violation is
  * recorded, not trapped.  built_with_checks: 1 in that build, 0 in the product library; first_bad_line: 0 = clean, else the source
- * line of the (highest) failed check -- nsr_wide.hip's line, or 100000 + the line of nsr_wide_gemm.inc.  Synchronises the device. */
+ * line of the (highest) failed check -- nsr_wide.hip's line, 100000 + the line of nsr_wide_gemm.inc, or 200000 + the line of
+ * nsr_wide_trunk.inc.  Synchronises the device. */
 int nsrw_debug_bounds_status(int* built_with_checks, unsigned* first_bad_line);
 
 #ifdef __cplusplus

@@ -43,7 +43,7 @@ __device__ unsigned g_wide_violation = 0u;
 #else
 #define NSRW_CHECK(cond) do { } while (0)
 #endif
-#define NSRW_FILE_TAG 0            /* nsr_wide.hip: the line itself; nsr_wide_gemm.inc: 100000 + line (it sets its own tag) */
+#define NSRW_FILE_TAG 0            /* nsr_wide.hip: the line itself; nsr_wide_gemm.inc: 100000 + line, nsr_wide_trunk.inc: 200000 + line (they set their own tags) */
 
 // ------------------------------------------------------------------------------------------------------------------------
 // GEMM: C[m][n] = epi( sum_k A[m][k] * Wt[n][k] + bias[n] ), A = [A1 | A2] (two row-major segments: the skip concatenation
@@ -59,6 +59,7 @@ __device__ unsigned g_wide_violation = 0u;
 enum { kRelu = 1, kAccum = 2, kMaskEpi = 4 };
 
 #include "nsr_wide_gemm.inc"
+#include "nsr_wide_trunk.inc"
 #undef NSRW_FILE_TAG
 #define NSRW_FILE_TAG 0
 
@@ -680,9 +681,12 @@ struct Net {
   int ldraw = 32;                     // row length of the raw outputs: 4 = [r g b sigma] dense (view directions), else 32
   std::vector<char> skip_in;          // skip_in[i]: layer i takes cat[input_pts, h]  (i - 1 in skips)
   float* dBias = nullptr;             // device: every bias, padded (all the device reads in fp32 form)
+  unsigned bias_floats = 0;
   char* dImg[kArithSlots] = {};       // device, per arithmetic the handle has an image of: the weight images of every matrix
   size_t img_bytes[kArithSlots] = {};
   std::vector<Mat> fwd;               // pts_linears
+  int trunk_nj = 0;                   // trunk_plan: 0 = the trunk runs layer by layer, else the NJ of kw_trunk_h2 that runs it on chip
+  TrunkLayer* dTrunk = nullptr;       // device: the per-layer table of kw_trunk_h2 (trunk_nj != 0)
   Mat fa, al, hv, rgb, out;           // feature_linear, alpha_linear, views_linears.0, rgb_linear / output_linear
   std::vector<Mat> bwd_h, bwd_e;      // per pts layer: G W_i[:, hidden part] (i >= 1), G W_i[:, encoding part] (layer 0, skip layers)
   Mat b_rgb, b_feat, b_ed, b_head;
@@ -700,6 +704,8 @@ void for_each_mat(Net& n, F f) {
 void free_net(Net& n) {      // (the caller has selected the handle's device)
   if (n.dBias) (void)hipFree(n.dBias);
   n.dBias = nullptr;
+  if (n.dTrunk) (void)hipFree(n.dTrunk);
+  n.dTrunk = nullptr;
   for (Arith a : kAriths) {
     if (n.dImg[a]) (void)hipFree(n.dImg[a]);
     n.dImg[a] = nullptr;
@@ -741,6 +747,7 @@ struct GemmCfg {
   int cus = 256;                        // compute units of the handle's device
   Arith arith = kF32;                   // NsrwConfig::flags: NSRW_FLAG_MLP_F16X2 -> kH2, NSRW_FLAG_MLP_BF16X3 -> kB3, neither -> kF32
   int tile_wm = 4;                      // 256-column tiles with 256 rows / 512 threads (4) or 128 rows / 256 threads (2: NSRW_B3_WM = 2)
+  int flags = 0;                        // NsrwConfig::flags (trunk_plan reads NSRW_FLAG_TRUNK_ONCHIP)
   unsigned* d_range = nullptr;          // device: [0] flag of the f16x2 pass in flight, [1] passes run, [2] passes re-run on bf16x3
 };
 
@@ -997,12 +1004,55 @@ int gemm(const GemmCfg& cfg, Run run, hipStream_t st, const Net& net, const Mat&
   return 0;
 }
 
+// Whether kw_trunk_h2 runs the pts_linears of `d` on a handle created with `flags` -- pure host arithmetic, no HIP call
+// (nsrw_trunk_plan exposes it).  On chip: an f16x2 handle with NSRW_FLAG_TRUNK_ONCHIP, at least two layers, and a packed width of at
+// most 128, so that the whole N extent is one tile (NJ = 1: <= 64 columns, NJ = 2: 128).  Tiles are 128 rows.
+NsrwTrunkPlan trunk_plan(const NsrwNet& d, int flags) {
+  NsrwTrunkPlan p{};
+  auto no = [&](const char* why) { p.onchip = 0; snprintf(p.reason, sizeof p.reason, "%s", why); return p; };
+  const std::string why = check_net(d);
+  if (!why.empty()) return no("invalid network");
+  if (!(flags & NSRW_FLAG_TRUNK_ONCHIP)) return no("NSRW_FLAG_TRUNK_ONCHIP not set");
+  if (!(flags & NSRW_FLAG_MLP_F16X2)) return no("not an f16x2 handle");
+  if (d.D < 2) return no("one layer: nothing to keep on chip");
+  if (pad32(d.W) > 128) return no("padded width above 128");
+  if (pad32(3 + 6 * d.multires) > kTrunkCiMax) return no("encoding wider than 96");
+  p.onchip = 1;
+  p.nj = pad32(d.W) <= 64 ? 1 : 2;
+  p.tile_rows = kTrunkRows;
+  p.lds_bytes = p.nj == 1 ? trunk_lds_bytes<1>() : trunk_lds_bytes<2>();
+  return p;
+}
+
+// all D pts_linears layers over P points in ONE launch: k.E -> k.H[(D - 1) & 1], where net_forward_chain's layer loop leaves them
+void trunk_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P) {
+  TrunkArgs t{};
+  t.E = k.E; t.ldE = n.Ci;
+  t.img = n.dImg[kH2]; t.img_bytes = (unsigned)n.img_bytes[kH2];
+  t.bias = n.dBias; t.bias_floats = n.bias_floats;
+  t.layers = n.dTrunk; t.D = n.d.D;
+  t.C = k.H[(n.d.D - 1) & 1]; t.Wp = n.Wp;
+  t.M = P;
+  t.range_flag = cfg.d_range;
+  const long long mblocks = (P + kTrunkRows - 1) / kTrunkRows;
+  const unsigned grid = (unsigned)std::min<long long>(mblocks, cfg.cus);
+  if (n.trunk_nj == 1) hipLaunchKernelGGL(kw_trunk_h2<1>, dim3(grid), dim3(512), 0, st, t);
+  else hipLaunchKernelGGL(kw_trunk_h2<2>, dim3(grid), dim3(512), 0, st, t);
+}
+
 // RH:99-122 over P points whose encodings are in k.E / k.ED: leaves the rgb logits in k.RAW (ld 32; all output_linear rows
 // without view directions) and the density at sigma / ld_sigma.  keep: every pts layer's activation stays (k.H[i]).
 int net_forward_chain(const GemmCfg& cfg, Run run, hipStream_t st, const Net& n, const Chunk& k, long long P, bool keep, const float** sigma,
                       int* ld_sigma) {
   const float* h = nullptr;
-  for (int i = 0; i < n.d.D; ++i) {
+  // f16x2 pass of an eligible network on an on-chip handle, no activation kept: the one trunk launch (the conditional bf16x3
+  // re-run and every pass that keeps its activations for a backward stay layer by layer)
+  const bool onchip = run.arith == kH2 && !run.run_if && !keep && n.trunk_nj != 0 && P > 0 && P / kTrunkRows < 0x7fffffffll;
+  if (onchip) {
+    trunk_launch(cfg, st, n, k, P);
+    h = k.H[(n.d.D - 1) & 1];
+  }
+  for (int i = 0; i < n.d.D && !onchip; ++i) {
     float* out = k.H[keep ? i : (i & 1)];
     int rc;
     if (i == 0) rc = gemm(cfg, run, st, n, n.fwd[0], k.E, n.Ci, nullptr, 0, out, n.Wp, n.Wp, P, kRelu);
@@ -1282,11 +1332,14 @@ int nsrw_create(const NsrwConfig* cfg, nsrw_handle* out) {
   int count = 0;
   NSRW_HIP(hipGetDeviceCount(&count));
   if (cfg->device < 0 || cfg->device >= count) return fail("nsrw_create: no such device");
+  if ((cfg->flags & NSRW_FLAG_TRUNK_ONCHIP) && !(cfg->flags & NSRW_FLAG_MLP_F16X2))
+    return fail("nsrw_create: NSRW_FLAG_TRUNK_ONCHIP needs NSRW_FLAG_MLP_F16X2 (the on-chip trunk exists for the f16x2 arithmetic only)");
   GemmCfg gc;
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess && prop.multiProcessorCount > 0) gc.cus = prop.multiProcessorCount;
   }
+  gc.flags = cfg->flags;
   gc.arith = (cfg->flags & NSRW_FLAG_MLP_F16X2) ? kH2 : (cfg->flags & NSRW_FLAG_MLP_BF16X3) ? kB3 : kF32;
   if (const char* wm = getenv("NSRW_B3_WM")) gc.tile_wm = atoi(wm) == 2 ? 2 : 4;
   Handle* h = new Handle();
@@ -1472,9 +1525,26 @@ int nsrw_upload_network(nsrw_handle hh, int net_id, const NsrwNet* desc, const f
     });
     if (image[a].size() >= 0x7fffffffull) return fail(std::string("nsrw_upload_network: network too large for the ") + arith_name(a) + " image");
   }
+  // the on-chip trunk's per-layer table (launch calls only enqueue)
+  std::vector<TrunkLayer> trunk;
+  const NsrwTrunkPlan tp = trunk_plan(*desc, h->gemm_cfg.flags);
+  if (tp.onchip) {
+    n.trunk_nj = tp.nj;
+    for (int i = 0; i < D; ++i) {
+      const Mat& m = n.fwd[i];
+      TrunkLayer t{};
+      t.img_off = (unsigned)m.img[kH2]; t.bias_off = (unsigned)m.b;
+      t.kbe = (i == 0 || n.skip_in[i]) ? Ci / 16 : 0; t.kbh = i == 0 ? 0 : Wp / 16;
+      t.cscale = m.cscale;
+      trunk.push_back(t);
+    }
+  }
+  n.bias_floats = (unsigned)bias.size();
   NSRW_DEVICE(h);
   // (every failure path below frees what this call allocated: ADVICE r05)
   hipError_t e = hipMalloc(&n.dBias, bias.size() * sizeof(float));
+  if (e == hipSuccess && !trunk.empty()) e = hipMalloc(&n.dTrunk, trunk.size() * sizeof(TrunkLayer));
+  if (e == hipSuccess && !trunk.empty()) e = hipMemcpy(n.dTrunk, trunk.data(), trunk.size() * sizeof(TrunkLayer), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(n.dBias, bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice);
   for (Arith a : kAriths) {
     if (e != hipSuccess || image[a].empty()) continue;
@@ -1602,6 +1672,14 @@ int nsrw_gemm_plan(int n_packed_rows, int n_stored_columns, int tile_wm, NsrwGem
   const int count = gemm_plan(col_blocks(n_packed_rows), n_stored_columns, tile_wm, parts);
   for (int i = 0; i < std::min(count, max_parts); ++i) parts_out[i] = parts[i];
   return count;
+}
+
+int nsrw_trunk_plan(const NsrwNet* net, int flags, NsrwTrunkPlan* plan_out) {
+  if (!net || !plan_out) { fail("nsrw_trunk_plan: null argument"); return -1; }
+  const std::string why = check_net(*net);
+  if (!why.empty()) { fail("nsrw_trunk_plan: " + why); return -1; }
+  *plan_out = trunk_plan(*net, flags);
+  return 0;
 }
 
 int nsrw_debug_bounds_status(int* built_with_checks, unsigned* first_bad_line) {

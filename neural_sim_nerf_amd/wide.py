@@ -48,6 +48,10 @@ class NsrwGemmPart(C.Structure):
     _fields_ = [("nj", C.c_int32), ("wm", C.c_int32), ("tiles", C.c_int32), ("col_block", C.c_int32)]
 
 
+class NsrwTrunkPlan(C.Structure):
+    _fields_ = [("onchip", C.c_int32), ("nj", C.c_int32), ("tile_rows", C.c_int32), ("lds_bytes", C.c_int32), ("reason", C.c_char * 64)]
+
+
 # render()'s differentiable outputs (RN:488-494) -> the field of NsrwCotangents and the shape of one ray's cotangent
 COTANGENTS = {"rgb_map": ("d_rgb", 3), "disp_map": ("d_disp", 1), "acc_map": ("d_acc", 1),
               "rgb0": ("d_rgb0", 3), "disp0": ("d_disp0", 1), "acc0": ("d_acc0", 1)}
@@ -75,6 +79,7 @@ SIGNATURES = {
                                    C.c_void_p]),
     "nsrw_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "nsrw_gemm_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(NsrwGemmPart), C.c_int]),
+    "nsrw_trunk_plan": (C.c_int, [C.POINTER(NsrwNet), C.c_int, C.POINTER(NsrwTrunkPlan)]),
     "nsrw_debug_bounds_status": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
     "nsrw_range_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "nsrw_sample_pdf": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -82,8 +87,9 @@ SIGNATURES = {
     "nsrw_embed_vjp": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
-FLAG_WHITE_BKGD, FLAG_LINDISP, FLAG_MLP_BF16X3, FLAG_MLP_F16X2 = 1, 2, 4, 8
+FLAG_WHITE_BKGD, FLAG_LINDISP, FLAG_MLP_BF16X3, FLAG_MLP_F16X2, FLAG_TRUNK_ONCHIP = 1, 2, 4, 8, 16
 MLPS = ("bf16x3", "fp32", "f16x2")
+TRUNKS = ("layers", "onchip")
 
 DEFAULT_MLP = "f16x2"           # r06: the fused default kernel's arithmetic; same parity bounds as the fp32 MFMAs and bf16x3 (tests/test_gpu_wide.py
                                 # runs every case on all three), 2.6x / 1.5x their speed; never range-dependent (re-run on bf16x3)
@@ -121,6 +127,25 @@ def gemm_plan(n_packed_rows, n_stored_columns, tile_wm=4):
     if not 0 <= count <= len(parts):
         raise _lib.NsrError(lib.nsrw_last_error().decode("utf-8", "replace"))
     return [(p.nj, p.wm, p.tiles, 32 * p.col_block) for p in parts[:count]]
+
+
+def _mlp_flags(mlp):
+    return (FLAG_MLP_BF16X3 if mlp == "bf16x3" else 0) | (FLAG_MLP_F16X2 if mlp == "f16x2" else 0)
+
+
+def trunk_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip"):
+    """nsrw_trunk_plan (diagnostic; no device, no handle): how a handle of arithmetic `mlp` created with trunk=`trunk` runs the
+    pts_linears of a network (an NsrwNet or a state dict) -- dict(mode="onchip", nj, tile_rows, lds_bytes) for the one-launch
+    trunk of csrc/nsr_wide_trunk.inc, or dict(mode="layers", reason=...) for a GEMM launch per layer."""
+    lib = load()
+    net = net_or_sd if isinstance(net_or_sd, NsrwNet) else describe(net_or_sd)[0]
+    plan = NsrwTrunkPlan()
+    flags = _mlp_flags(mlp) | (FLAG_TRUNK_ONCHIP if trunk == "onchip" else 0)
+    if lib.nsrw_trunk_plan(C.byref(net), flags, C.byref(plan)) != 0:
+        raise _lib.NsrError(lib.nsrw_last_error().decode("utf-8", "replace"))
+    if plan.onchip:
+        return dict(mode="onchip", nj=int(plan.nj), tile_rows=int(plan.tile_rows), lds_bytes=int(plan.lds_bytes))
+    return dict(mode="layers", reason=plan.reason.decode("utf-8", "replace"))
 
 
 def _np(v):
@@ -237,14 +262,27 @@ class WideModel:
     schedule = "layers"
 
     def __init__(self, sd_coarse, sd_fine=None, device=None, n_importance=128, white_bkgd=False, lindisp=False, n_samples=64,
-                 mlp=None):
+                 mlp=None, trunk=None):
         """mlp: the arithmetic of the layer GEMMs -- "bf16x3" (bf16 MFMAs on three-way split fp32 operands, fp32-grade results at
         2.67x the matrix-pipe rate: csrc/nsr_wide_gemm.inc), "fp32" (fp32 MFMAs, the strict mode) or "f16x2" (fp16 MFMAs with
         two-piece operands -- the fused default kernel's arithmetic; a network pass that leaves fp16's range is re-run on bf16x3
-        inside the call); default $NSR_WIDE_MLP, else DEFAULT_MLP."""
+        inside the call); default $NSR_WIDE_MLP, else DEFAULT_MLP.
+        trunk: "layers" (a GEMM launch per pts_linears layer, activations through HBM) or "onchip" (f16x2 only: a network of
+        padded width <= 128 and depth >= 2 runs its pts_linears in ONE launch with the activations in LDS wherever no activation is
+        kept for a backward -- the same bits; any other network on the handle runs layer by layer: trunk_plan); default
+        $NSR_WIDE_TRUNK (which handles of the other arithmetics ignore, while an explicit trunk="onchip" there raises), else "layers"."""
         mlp = mlp or os.environ.get("NSR_WIDE_MLP") or DEFAULT_MLP
         if mlp not in MLPS:
             raise ValueError("mlp must be one of %s (got %r)" % (MLPS, mlp))
+        from_env = not trunk
+        trunk = trunk or os.environ.get("NSR_WIDE_TRUNK") or "layers"
+        if trunk not in TRUNKS:
+            raise ValueError("trunk must be one of %s (got %r)" % (TRUNKS, trunk))
+        if from_env and mlp != "f16x2":       # the environment's wish applies where it can: the drop-in API also builds bf16x3 / fp32 handles
+            trunk = "layers"
+        if trunk == "onchip" and mlp != "f16x2":
+            raise NotImplementedError("trunk=\"onchip\" exists for mlp=\"f16x2\" only (got mlp=%r)" % (mlp,))
+        self.trunk = trunk
         self.mlp = "layered-" + mlp
         if not torch.cuda.is_available():
             raise _lib.NsrError("no HIP device visible: the render path has no CPU fallback")
@@ -267,7 +305,7 @@ class WideModel:
         self._ws_need = {}                                # (rays, grad) -> bytes one chunk of that many rays needs
         cfg = NsrwConfig(self.device.index, n_samples, n_importance,
                          (FLAG_WHITE_BKGD if white_bkgd else 0) | (FLAG_LINDISP if lindisp else 0) |
-                         (FLAG_MLP_BF16X3 if mlp == "bf16x3" else 0) | (FLAG_MLP_F16X2 if mlp == "f16x2" else 0))
+                         _mlp_flags(mlp) | (FLAG_TRUNK_ONCHIP if trunk == "onchip" else 0))
         h = C.c_void_p()
         check(self.lib.nsrw_create(C.byref(cfg), C.byref(h)))
         self.h = h

@@ -3,7 +3,10 @@ algorithmic fp32 TFLOP/s of the network evaluations against the fp32-MFMA peak (
 roofline of its strict mode (kw_gemm_f32: v_mfma_f32_32x32x2_f32) and the yardstick the split arithmetics (kw_gemm_h2, kw_gemm_b3: --mlp) are
 quoted against; for those the issued fraction of the fp16 / bf16 peak is reported as well.
 
-    python tools/bench_wide.py [--hw 400] [--cases ycbv,w512,d10w384,small] [--steps 3]
+    python tools/bench_wide.py [--hw 400] [--cases ycbv,w512,d10w384,small] [--steps 3] [--trunk layers|onchip|both]
+
+--trunk (f16x2): the pts_linears layer by layer (the default), in the one-launch on-chip trunk (csrc/nsr_wide_trunk.inc), or both in
+turn on the same rays in one process -- the comparison DESIGN.md 8 quotes.
 """
 import argparse
 import json
@@ -67,14 +70,16 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--no-grad", action="store_true")
     ap.add_argument("--mlp", default=None, help="bf16x3 | fp32 | f16x2 (default: the library's)")
+    ap.add_argument("--trunk", default="layers", choices=("layers", "onchip", "both"))
     a = ap.parse_args()
+    trunks = ("layers", "onchip") if a.trunk == "both" else (a.trunk,)
     K = S.scaled_K(400.0 / a.hw)
     pose = S.sweep_poses(1, seed=0)[0]
     out = {}
-    for name in a.cases.split(","):
+    for name, trunk in [(c, t) for c in a.cases.split(",") for t in trunks]:
         D, W, L, Lv, skips, ns, ni = CASES[name]
         sd = net_sd(D, W, L, Lv, skips, 1)
-        m = WideModel(sd, sd, n_samples=ns, n_importance=ni, mlp=a.mlp)
+        m = WideModel(sd, sd, n_samples=ns, n_importance=ni, mlp=a.mlp, trunk=trunk)
         n = a.hw * a.hw
         evals = n * (ns + ns + ni)
         flop = evals * flop_per_point(sd)
@@ -82,7 +87,7 @@ def main():
         ro, rd = ro.reshape(-1, 3), rd.reshape(-1, 3)
         cot = torch.randn(n, 3, device=m.device)
         res = {"network": "%d x %d, skips %s, %d + %d samples" % (D, W, skips, ns, ni), "rays": n,
-               "flop_per_point": flop_per_point(sd), "mlp": m.mlp}
+               "flop_per_point": flop_per_point(sd), "mlp": m.mlp, "trunk": m.trunk}
         for what in ("forward",) + (() if a.no_grad else ("forward+input-gradient",)):
             ms = []
             ps = None
@@ -99,7 +104,7 @@ def main():
             power = ps.stop() if ps else None
             t = float(np.median(ms[1:]))
             f = flop if what == "forward" else flop + n * (ns + ni) * flop_per_point(sd)     # + the fine pass's transposed GEMMs
-            res[what] = {"ms_per_view": round(t, 2), "chunks": chunks, "workspace_GB": round(m.workspace_bytes / 2 ** 30, 2),
+            res[what] = {"ms_per_view": round(t, 2), "ms_min_max": [round(min(ms[1:]), 2), round(max(ms[1:]), 2)], "chunks": chunks, "workspace_GB": round(m.workspace_bytes / 2 ** 30, 2),
                          "algorithmic_TFLOPs": round(f / t / 1e9, 1), "frac_of_fp32_mfma_peak": round(f / t / 1e9 / PEAK_FP32_MFMA, 3)}
             if m.mlp.endswith("bf16x3"):       # six bf16 piece products per product: ceiling 2500 / 6 TFLOP/s of algorithmic work
                 res[what]["issued_frac_of_bf16_peak"] = round(6 * f / t / 1e9 / 2500.0, 3)
@@ -111,8 +116,9 @@ def main():
                 res[what]["Mray_samples_per_s"] = round(n * (ns + ni) / t / 1e3, 2)
         if m.mlp.endswith("f16x2"):
             res["range_status"] = m.range_status()
-        out[name] = res
-        print(name, json.dumps(res), flush=True)
+        key = name if a.trunk != "both" else name + ":" + trunk
+        out[key] = res
+        print(key, json.dumps(res), flush=True)
         m.close()
         del m
         torch.cuda.empty_cache()
