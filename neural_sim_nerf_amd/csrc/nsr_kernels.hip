@@ -566,10 +566,12 @@ struct ItemStateT {
   float zs[2][128];         // importance samples     RH:241
   float zf[2][NFS];         // sorted merged z        RN:477
   float rawf[2][NFS][4];    // fine raw               RN:483
-  float alpha[2][NFS];      // compositing scratch
+  float alpha[2][NFS];      // compositing scratch (not touched by the render32_body kernels: composite_wave keeps alpha in registers)
   float wf[2][NFS];         // fine weights           RN:485
   float tf[2][NFS];         // transmittance T_i (RN:376)
   float om[2][NFS];         // 1 - alpha + 1e-10 (RN:376) / pdf (RH:202): fp32 values, widened to fp64 inside the scans
+  // bwd_scratch .. gnorm are the input-gradient kernels'; the FORWARD kernels built from render32_body view the same bytes as
+  // FwdItemExtra (below): their coarse chain's scratch and the second copy of the per-item state
   float bwd_scratch[2][NFS][2];   // backward compositing: A_i*w_i suffix sums and A_i*T_i
   float psum[2][NFS / 32][12];    // backward: per (pass, wave) partial sums of d/dpts, z*d/dpts, d/dviewdir
   float gnorm[2];           // backward: dL/d|rays_d| from dists*|d| (RN:361)
@@ -577,6 +579,8 @@ struct ItemStateT {
 };
 typedef ItemStateT<64, 192> ItemState;
 typedef ItemStateT<128, 256> ItemStateBig;
+// (124 928 + 23 048 B of the 163 840 B of LDS; ItemStateBig: 124 928 + 32 712 B.  The forward kernels' second copy of the
+// per-item state and their coarse chain's scratch, FwdItemExtra below, live INSIDE bwd_scratch .. gnorm: no size changes.)
 static_assert(sizeof(ItemState) == 23048, "the YCB-V layout is part of the shipped kernels' LDS budget");
 template <int NS> struct ItemStateFor { typedef ItemState type; };
 template <> struct ItemStateFor<128> { typedef ItemStateBig type; };
@@ -1053,6 +1057,16 @@ __device__ __forceinline__ long long queue_next_item(const RenderArgs& q) {
   }
   return v < (unsigned long long)((q.n_rays + 1) >> 1) ? (long long)(v | (3ull << 62)) : -1ll;
 }
+// ... the same for a counter value `v` fetched earlier: the forward kernels issue the atomicAdd ahead of time and resolve
+// it where its latency has passed
+__device__ __forceinline__ long long queue_item_of(const RenderArgs& q, unsigned long long v) {
+  if (q.item_list) {
+    unsigned n = *q.item_count;
+    n = n < q.item_cap ? n : q.item_cap;
+    return v < (unsigned long long)n ? (long long)q.item_list[v] : -1ll;
+  }
+  return v < (unsigned long long)((q.n_rays + 1) >> 1) ? (long long)(v | (3ull << 62)) : -1ll;
+}
 __device__ __forceinline__ long long queue_items(const RenderArgs& q) {
   if (q.item_list) { const unsigned n = *q.item_count; return (long long)(n < q.item_cap ? n : q.item_cap); }
   return (q.n_rays + 1) >> 1;
@@ -1099,6 +1113,261 @@ __device__ __forceinline__ void range_poison(const RenderArgs& a, long long ray0
   }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Wave-local forms of the per-ray stages (render32_body).  One wave runs one ray's chain from LDS; its steps are ordered by
+// the wave's own in-order LDS queue (s_waitcnt lgkmcnt), not by workgroup barriers, so two rays' chains -- and the coarse
+// chain of one item next to the fine composite of the item before it -- run side by side.  The arithmetic and every
+// association order are those of composite / sample_pdf_item[_ns] / merge_sort_item above, which the VJP and the
+// stand-alone stage kernels keep using.
+// ------------------------------------------------------------------------------------------------------
+// Between two steps of one wave that communicate through LDS across lanes: a wave's LDS operations execute in program
+// order, so this only has to keep the compiler from reordering them.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// Workgroup barrier between stages that communicate through LDS only: waits for the wave's LDS (and scalar) operations,
+// not for vmcnt -- the ring's LDS-DMA, the output stores and the queue atomic stay in flight across it.
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// Forward-only view of ItemStateT's backward scratch (bwd_scratch .. gnorm, which no forward kernel touches): the coarse
+// chain's own scratch and the second copy of what an item must keep until its deferred fine composite has run.
+template <typename ST>
+struct FwdItemExtra {
+  float om[2][ST::kNS];     // coarse chain: 1 - alpha + 1e-10, then the pdf
+  float tf[2][ST::kNS];     // coarse chain: transmittance, then x = w + 1e-5
+  float zf[2][ST::kNF];     // sorted merged z of the items of odd parity (st.zf: even)
+  float ray[2][16];         // st.ray of the items of odd parity (incl. their range counters in [1][14..15])
+  float res[2][8];          // coarse results (st.res: fine)
+  long long pend;           // packed handle of the item whose fine composite is pending, -1: none
+  long long next;           // packed handle of the item after the current one, pulled from the queue a coarse chain ahead
+};
+
+// composite for one ray on one wave.  Lane l owns samples l, l + 64, ... in phase 1 AND phase 3, so alpha stays in registers.
+// res (lane 0): rgb(3) disp acc depth.
+template <int S>
+__device__ __forceinline__ void composite_wave(const float* ry, const float* zr, float* q, float* wr, float* tr, float* omr,
+                                               int lane, const float* noise /* global [S] of this ray, or null */,
+                                               float (&res)[6]) {
+  static_assert(S % 8 == 0, "scan is unrolled by 8");
+  constexpr int K = (S + 63) / 64;
+  float al[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const int i = lane + 64 * k;
+    al[k] = 0.0f;
+    if (i < S) {
+      float dist = (i < S - 1) ? (zr[i + 1] - zr[i]) : 1e10f;   // RN:358-359
+      dist = dist * ry[11];                                      // RN:361
+      if (noise) q[i * 4 + 3] = q[i * 4 + 3] + noise[i];         // RN:374
+      const float sigma = fmaxf(q[i * 4 + 3], 0.0f);
+      const float a = 1.0f - expf(-sigma * dist);                // RN:356
+      al[k] = a;
+      omr[i] = (1.0f - a) + 1e-10f;                              // RN:376 factor (widened to fp64 in the scan)
+      q[i * 4 + 0] = sigmoidf_(q[i * 4 + 0]);                    // RN:363
+      q[i * 4 + 1] = sigmoidf_(q[i * 4 + 1]);
+      q[i * 4 + 2] = sigmoidf_(q[i * 4 + 2]);
+    }
+  }
+  wave_lds_sync();
+  if (lane == 0) {
+    double T = 1.0;
+#pragma unroll 1
+    for (int i0 = 0; i0 < S; i0 += 8) {
+      double f[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) f[k] = (double)omr[i0 + k];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        tr[i0 + k] = (float)T;                                   // exclusive product, rounded per prefix
+        T = T * f[k];
+      }
+    }
+  }
+  wave_lds_sync();
+  float cr = 0.f, cg = 0.f, cb = 0.f, depth = 0.f, acc = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const int i = lane + 64 * k;
+    if (i < S) {
+      const float w = al[k] * tr[i];                             // RN:376
+      wr[i] = w;
+      cr = cr + w * q[i * 4 + 0];                                // RN:378
+      cg = cg + w * q[i * 4 + 1];
+      cb = cb + w * q[i * 4 + 2];
+      depth = depth + w * zr[i];                                 // RN:380
+      acc = acc + w;                                             // RN:382
+    }
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    cr += __shfl_xor(cr, m); cg += __shfl_xor(cg, m); cb += __shfl_xor(cb, m);
+    depth += __shfl_xor(depth, m); acc += __shfl_xor(acc, m);
+  }
+  const float qd = depth / acc;
+  float disp;
+  if (qd != qd) disp = qd;                                       // 0/0 -> NaN propagates through torch.max (RN:381)
+  else disp = 1.0f / fmaxf(1e-10f, qd);
+  if (ry[12] != 0.0f) {                                          // white_bkgd, RN:384-385
+    const float bg = 1.0f - acc;
+    cr = cr + bg; cg = cg + bg; cb = cb + bg;
+  }
+  res[0] = cr; res[1] = cg; res[2] = cb; res[3] = disp; res[4] = acc; res[5] = depth;
+  wave_lds_sync();
+}
+
+// sample_pdf for one ray on one wave: w = coarse weights[1:-1] (NS - 2), bins = mid-points of zc.  x: scratch [NS], pdf:
+// scratch [NS].  The eight vector-lane partial sums of ATen's cascade are computed by eight lanes and folded into `total`
+// in ATen's order; lane l owns weights l, l + 64 and importance samples l, l + 64.
+template <int NI, int NS>
+__device__ __forceinline__ void sample_pdf_wave(const float* w, const float* zc, float* x, float* pdf, float* cdf, float* zs,
+                                                const float* u /* [NI of 128]: LDS table or this ray's global row */,
+                                                int64_t* inds_out /* [NI] of this ray, or null */, int lane) {
+  constexpr int NW = NS - 2, NC = NS - 1;                        // weights; bins = cdf entries
+  constexpr int NVEC = NW / 8, SILP = NVEC / 4;
+  constexpr int KW = (NW + 63) / 64;
+  float xv[KW];
+#pragma unroll
+  for (int k = 0; k < KW; ++k) {
+    const int i = lane + 64 * k;
+    xv[k] = 0.0f;
+    if (i < NW) { xv[k] = w[i] + 1e-5f; x[i] = xv[k]; }          // RH:201
+  }
+  wave_lds_sync();
+  const int j = lane & 7;
+  float lj;
+  if constexpr (NS == 64) {                                      // torch.sum over 62 contiguous floats (RH:202), exact order
+    const float p0 = ((x[j] + x[32 + j]) + x[40 + j]) + x[48 + j];
+    lj = ((p0 + x[8 + j]) + x[16 + j]) + x[24 + j];
+  } else {
+    float ps[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int i = 0; i < SILP; ++i)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) ps[k] = ps[k] + x[(i * 4 + k) * 8 + j];
+#pragma unroll
+    for (int v = SILP * 4; v < NVEC; ++v) ps[0] = ps[0] + x[v * 8 + j];
+    lj = ((ps[0] + ps[1]) + ps[2]) + ps[3];
+  }
+  float total = 0.0f;
+#pragma unroll
+  for (int i = NVEC * 8; i < NW; ++i) total = total + x[i];
+#pragma unroll
+  for (int jj = 0; jj < 8; ++jj) total = total + __shfl(lj, jj);
+#pragma unroll
+  for (int k = 0; k < KW; ++k) {
+    const int i = lane + 64 * k;
+    if (i < NW) pdf[i] = xv[k] / total;                          // pdf (RH:202), widened to fp64 in the scan
+  }
+  wave_lds_sync();
+  if (lane == 0) {
+    // cdf = [0, cumsum(pdf)]: sequential fp64 accumulator, each prefix rounded to fp32 (RH:203-204)
+    double run = 0.0;
+    cdf[0] = 0.0f;
+#pragma unroll 1
+    for (int i0 = 0; i0 < NVEC * 8; i0 += 8) {
+      double f[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) f[k] = (double)pdf[i0 + k];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) { run = run + f[k]; cdf[i0 + k + 1] = (float)run; }
+    }
+#pragma unroll
+    for (int i = NVEC * 8; i < NW; ++i) { run = run + (double)pdf[i]; cdf[i + 1] = (float)run; }
+  }
+  wave_lds_sync();
+#pragma unroll
+  for (int kk = 0; kk < (NI + 63) / 64; ++kk) {
+    const int k = lane + 64 * kk;
+    if (k < NI) {
+      const float uu = u[k];
+      int lo = 0, hi = NC;                                       // searchsorted(cdf, u, right=True) among NC entries (RH:227)
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (cdf[NSR_IDX(mid, NC)] <= uu) lo = mid + 1; else hi = mid;
+      }
+      const int ind = lo;
+      const int below = NSR_IDX(max(ind - 1, 0), NC);
+      const int above = NSR_IDX(min(ind, NC - 1), NC);
+      const float c0 = cdf[below], c1 = cdf[above];
+      const float b0 = 0.5f * (zc[below + 1] + zc[below]), b1 = 0.5f * (zc[above + 1] + zc[above]);   // RN:473
+      float denom = c1 - c0;
+      if (denom < 1e-5f) denom = 1.0f;                           // RH:238-239
+      const float t = (uu - c0) / denom;
+      zs[NSR_IDX(k, 128)] = b0 + t * (b1 - b0);                  // RH:241
+      if (inds_out) inds_out[k] = (int64_t)ind;
+    }
+  }
+  wave_lds_sync();
+}
+
+// merge_sort_item for one ray on one wave; the fast / slow path is this ray's own decision (both give the same stable ranks).
+template <int NI, int NS>
+__device__ __forceinline__ void merge_wave(const float* zc, const float* zs, float* zf, int lane) {
+  constexpr int NF = NS + NI;
+  constexpr bool kPow2 = (NI & (NI - 1)) == 0 && (NS & (NS - 1)) == 0;
+  constexpr int K = (NF + 63) / 64;
+  int bad = 0;
+#pragma unroll
+  for (int kk = 0; kk < K; ++kk) {
+    const int k = lane + 64 * kk;
+    if (k < NS - 1) bad |= !(zc[k] <= zc[k + 1]);
+    else if (k >= NS && k < NF - 1) bad |= !(zs[k - NS] <= zs[k - NS + 1]);
+  }
+  const bool any_bad = __builtin_amdgcn_ballot_w64(bad != 0) != 0;
+  if (!any_bad) {
+#pragma unroll
+    for (int kk = 0; kk < K; ++kk) {
+      const int k = lane + 64 * kk;
+      if (k < NS) {                                    // own index + #(z_samples < x)
+        const float x = zc[k];
+        int lb = 0;
+        if constexpr (kPow2) {
+#pragma unroll
+          for (int sft = NI / 2; sft > 0; sft >>= 1) lb += (zs[lb + sft - 1] < x) ? sft : 0;
+          lb += (zs[lb] < x) ? 1 : 0;
+        } else {
+          int hi = NI;
+          while (lb < hi) { const int mid = (lb + hi) >> 1; if (zs[NSR_IDX(mid, NI)] < x) lb = mid + 1; else hi = mid; }
+        }
+        zf[NSR_IDX(k + lb, NF)] = x;
+      } else if (k < NF) {                             // own index + #(z_coarse <= x)
+        const float x = zs[k - NS];
+        int ub = 0;
+        if constexpr (kPow2) {
+#pragma unroll
+          for (int sft = NS / 2; sft > 0; sft >>= 1) ub += (zc[ub + sft - 1] <= x) ? sft : 0;
+          ub += (zc[ub] <= x) ? 1 : 0;
+        } else {
+          int hi = NS;
+          while (ub < hi) { const int mid = (ub + hi) >> 1; if (zc[NSR_IDX(mid, NS)] <= x) ub = mid + 1; else hi = mid; }
+        }
+        zf[NSR_IDX((k - NS) + ub, NF)] = x;
+      }
+    }
+  } else {
+#pragma unroll 1
+    for (int kk = 0; kk < K; ++kk) {
+      const int k = lane + 64 * kk;
+      if (k < NF) {
+        const float x = (k < NS) ? zc[k] : zs[k - NS];
+        int rank = 0;
+        for (int jx = 0; jx < NS; ++jx) {
+          const float y = zc[jx];
+          rank += (y < x) || (y == x && jx < k);
+        }
+        for (int jx = 0; jx < NI; ++jx) {
+          const float y = zs[jx];
+          rank += (y < x) || (y == x && (jx + NS) < k);
+        }
+        zf[NSR_IDX(rank, NF)] = x;
+      }
+    }
+  }
+  wave_lds_sync();
+}
+
 #ifdef NSR_PHASE_TIMING      // diagnostic build: per-workgroup cycle totals of the item phases (thread 0), see tools
 #define NSR_T(i) do { if (threadIdx.x == 0) { const long long t_ = clock64(); tacc[i] += t_ - tlast; tlast = t_; } } while (0)
 #else
@@ -1139,7 +1408,13 @@ __device__ __forceinline__ void render32_body(const RenderArgs* __restrict__ ap,
   const long long n_rays = a_setup.n_rays;
   if ((long long)blockIdx.x >= queue_items(a_setup)) return;
   const int fine = a_setup.fine;
-  int* ovf = (int*)&st.ray[1][14];                       // f16x2: [2] points with NaN network outputs, per ray of the current item
+  // Forward view of the backward scratch: the coarse chain's scratch and the odd-parity copies of the item state.  Items
+  // alternate parity: item N's ray block, range counters and sorted z stay intact while item N + 1 is staged, runs its
+  // coarse pass and its coarse chain -- next to which N's deferred fine composite runs.
+  typedef FwdItemExtra<ST> XT;
+  static_assert(offsetof(ST, res) - offsetof(ST, bwd_scratch) >= sizeof(XT) && offsetof(ST, bwd_scratch) % 8 == 0 &&
+                offsetof(XT, pend) % 8 == 0, "the forward scratch lives in the item state's backward scratch");
+  XT& xs = *(XT*)&st.bwd_scratch[0][0][0];
 
   Ring rg;
   ring_init(rg, smem, a_setup.nets, a_setup.net_stride, fine ? NPC + NP : NPC, wave, lane);
@@ -1153,20 +1428,67 @@ __device__ __forceinline__ void render32_body(const RenderArgs* __restrict__ ap,
   load_aux(smem, a_setup, tid0);
   if (tid0 < NS) st.tcoarse[tid0] = a_setup.tcoarse[tid0];
   if (tid0 < NI) st.ufine[tid0] = a_setup.ufine[tid0];
+  if (tid0 == 0) xs.pend = -1ll;
   __syncthreads();
   const float* aux_c = (const float*)(smem + kLdsAux);
 
   // items come from a global counter: nothing forces the workgroups to progress at the same rate
-  long long* item_slot = (long long*)&st.ray[0][14];     // 8-byte slot in the unused tail of ray 0's block
+  long long* item_slot = (long long*)&st.ray[0][14];     // 8-byte slot in the unused tail of the even ray 0's block
   auto next_item = [&]() -> long long {
     if (opaque_v(tid0) == 0) *item_slot = queue_next_item(*opaque_s(ap));
-    __syncthreads();
+    lds_barrier();
     const long long v = uniform64(*item_slot);
-    __syncthreads();
+    lds_barrier();
     return v;
   };
+
+  // The deferred fine post-phase of the item `pk` (parity pp).  fine_wave: raw2outputs of ray r on the calling wave, from
+  // rawf and that parity's z / ray block.  fine_out: the output stores and the range report, one wave (a poisoned ray's NaNs
+  // must follow its own output stores in the same wave), after a barrier behind fine_wave.
+  auto fine_wave = [&](long long pk, int pp, int r) {
+    const RenderArgs& a = *opaque_s(ap);
+    const long long ray0 = (pk & kItemMask) * 2;
+    const int valid = (ray0 + 1 < n_rays) ? 2 : 1;
+    const int wmask = (int)((unsigned long long)pk >> 62) & (valid == 2 ? 3 : 1);
+    const float* ry = pp ? xs.ray[r] : st.ray[r];
+    const float* zr = pp ? xs.zf[r] : st.zf[r];
+    float* q = &st.rawf[r][0][0];
+    if (a.dbg_raw && ((wmask >> r) & 1)) {
+      for (int idx = lane; idx < NF * 4; idx += 64) a.dbg_raw[(ray0 + r) * (NF * 4) + idx] = q[idx];
+      wave_lds_sync();
+    }
+    float res[6];
+    composite_wave<NF>(ry, zr, q, st.wf[r], st.tf[r], st.om[r], lane,
+                       a.noise1 ? a.noise1 + (ray0 + (r < valid ? r : 0)) * NF : nullptr, res);
+    if (lane == 0) {
+#pragma unroll
+      for (int c = 0; c < 6; ++c) st.res[r][c] = res[c];
+    }
+  };
+  auto fine_out = [&](long long pk, int pp) {
+    const RenderArgs& a = *opaque_s(ap);
+    const int tid = opaque_v(tid0);
+    const long long item = pk & kItemMask;
+    const long long ray0 = item * 2;
+    const int valid = (ray0 + 1 < n_rays) ? 2 : 1;
+    const int wmask = (int)((unsigned long long)pk >> 62) & (valid == 2 ? 3 : 1);
+    if (tid < 16 && ((wmask >> (tid >> 3)) & 1)) {
+      const int r = tid >> 3, c = tid & 7;
+      const long long rr = ray0 + r;
+      const float v = st.res[r][c];
+      if (c < 3) { if (a.rgb) a.rgb[rr * 3 + c] = v; }
+      else if (c == 3) { if (a.disp) a.disp[rr] = v; }
+      else if (c == 4) { if (a.acc) a.acc[rr] = v; }
+    }
+    if (MODE == kMlpH2 && tid == 0) {
+      int* povf = (int*)(pp ? &xs.ray[1][14] : &st.ray[1][14]);
+      if (const unsigned m = range_report(a, povf, item, valid)) range_poison(a, ray0, m);
+    }
+  };
+
   long long packed = next_item();
   int pass = 0;              // 0 .. NPC - 1 = coarse pass(es), NPC .. NPC + NP - 1 = fine passes of the current item
+  int par = 0;               // parity of the current item: which copy of the ray block / range counters / sorted z it owns
 #pragma unroll 1
   while (packed != -1ll) {
     const long long item = packed & kItemMask;
@@ -1174,6 +1496,9 @@ __device__ __forceinline__ void render32_body(const RenderArgs* __restrict__ ap,
     const int valid = (ray0 + 1 < n_rays) ? 2 : 1;
     const int wmask = (int)((unsigned long long)packed >> 62) & (valid == 2 ? 3 : 1);     // rays this launch writes
     auto wr = [&](int r) { return ((wmask >> r) & 1) != 0; };
+    float (*const ray)[16] = par ? xs.ray : st.ray;
+    float* const zf = par ? &xs.zf[0][0] : &st.zf[0][0];   // [2][ST::kNF]
+    int* const ovf = (int*)&ray[1][14];                   // f16x2: [2] points with NaN network outputs, per ray of the current item
     if (pass == 0) {
       // ---- stage the two rays --------------------------------------------------------------------
       const RenderArgs& a = *opaque_s(ap);                // see opaque_v / opaque_s
@@ -1195,13 +1520,13 @@ __device__ __forceinline__ void render32_body(const RenderArgs* __restrict__ ap,
         const float* vd = a.camera ? nullptr : a.viewdirs;                           // given view directions: RN:91-103
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-          st.ray[tid][c] = o[c]; st.ray[tid][3 + c] = d[c];
-          st.ray[tid][6 + c] = vd ? vd[rr * 3 + c] : d[c] / nrm;
+          ray[tid][c] = o[c]; ray[tid][3 + c] = d[c];
+          ray[tid][6 + c] = vd ? vd[rr * 3 + c] : d[c] / nrm;
         }
-        st.ray[tid][9] = a.near_rays ? a.near_rays[rr] : near_;       // per-ray bounds (RN:106-108) or the call's scalars
-        st.ray[tid][10] = a.near_rays ? a.far_rays[rr] : far_;
-        st.ray[tid][11] = nrm;
-        st.ray[tid][12] = a.white_bkgd ? 1.0f : 0.0f;
+        ray[tid][9] = a.near_rays ? a.near_rays[rr] : near_;          // per-ray bounds (RN:106-108) or the call's scalars
+        ray[tid][10] = a.near_rays ? a.far_rays[rr] : far_;
+        ray[tid][11] = nrm;
+        ray[tid][12] = a.white_bkgd ? 1.0f : 0.0f;
       }
       if (MODE == kMlpH2 && (tid == 64 || tid == 65)) ovf[tid - 64] = 0;
       if (tid < 2 * NS) {
@@ -1210,7 +1535,7 @@ __device__ __forceinline__ void render32_body(const RenderArgs* __restrict__ ap,
         const long long rb = ray0 + (r < valid ? r : 0);
         st.zc[r][i] = coarse_z(a.near_rays ? a.near_rays[rb] : near_, a.near_rays ? a.far_rays[rb] : far_, t, a.lindisp);
       }
-      __syncthreads();
+      lds_barrier();
       if (a.t_rand) perturb_coarse_z<NS>(st, a.t_rand, ray0, valid, tid);
       NSR_T(0);
     }
@@ -1236,10 +1561,10 @@ __device__ __forceinline__ void render32_body(const RenderArgs* __restrict__ ap,
         int q0 = 128 * (pass - NPC) + 32 * wave;
         if (2 * NF % 128 != 0 && q0 >= 2 * NF) { q0 = 2 * NF - 32; real = false; }
         r = q0 / NF; i = q0 - r * NF + j;
-        zsrc = &st.zf[r][i]; dst = st.rawf[r][i];
+        zsrc = &zf[r * ST::kNF + i]; dst = st.rawf[r][i];
       }
       const float z = *zsrc;
-      const float* ry = st.ray[r];
+      const float* ry = ray[r];
       float raw[4];
       mlp_pass<false, MODE>(rg, aux_c + (((NPC == 1) ? (pass == 0) : (pass < NPC)) ? 0 : kAuxFloats), A0, A1, lane, ry[0] + ry[3] * z, ry[1] + ry[4] * z,
                ry[2] + ry[5] * z, ry[6], ry[7], ry[8], raw, nullptr, 0, NSR_TPASS);
@@ -1253,21 +1578,69 @@ __device__ __forceinline__ void render32_body(const RenderArgs* __restrict__ ap,
     if (NPC > 1 && pass < NPC - 1) {
       ++pass;                                              // (N_samples = 128: the item's second coarse pass)
     } else if ((NPC == 1) ? (pass == 0) : (pass < NPC)) {
-      __syncthreads();
-      if (a.dbg_raw0) {
-        if constexpr (NS == ST::kNS) {
-          for (int idx = tid; idx < 2 * NS * 4; idx += 256) if (wr(idx >> (LNS + 2))) a.dbg_raw0[ray0 * (NS * 4) + idx] = (&st.rawc[0][0][0])[idx];
-        } else {
-          for (int idx = tid; idx < 2 * NS * 4; idx += 256)
-            if (wr(idx >> (LNS + 2))) a.dbg_raw0[ray0 * (NS * 4) + idx] = (&st.rawc[idx >> (LNS + 2)][0][0])[idx & (NS * 4 - 1)];
+      // ---- side by side: waves 0 / 1 run the coarse chains of this item's two rays, waves 2 / 3 the deferred fine composites
+      //      of the item before it; one barrier in, one barrier out ----------------------------------
+      lds_barrier();
+      const long long pend = fine ? uniform64(xs.pend) : -1ll;
+      // the queue pull of the NEXT item: issued here by one lane of the fine role, resolved behind its composite -- the atomic's
+      // round trip is off the critical path, at the price of an item reserved NP passes early (the end of the queue only)
+      const bool puller = fine && tid == 192;
+      unsigned long long ticket = 0ull;
+      if (puller) ticket = atomicAdd(a.work_counter, 1ull);
+      if (wave < 2) {
+        const int r = wave;
+        float* q = &st.rawc[r][0][0];
+        if (a.dbg_raw0 && wr(r)) {
+          for (int idx = lane; idx < NS * 4; idx += 64) a.dbg_raw0[(ray0 + r) * (NS * 4) + idx] = q[idx];
+          wave_lds_sync();
         }
-        __syncthreads();
+        float res[6];
+        composite_wave<NS>(ray[r], st.zc[r], q, st.w0[r], xs.tf[r], xs.om[r], lane,
+                           a.noise0 ? a.noise0 + (ray0 + (r < valid ? r : 0)) * NS : nullptr, res);
+        if (lane == 0) {
+#pragma unroll
+          for (int c = 0; c < 6; ++c) xs.res[r][c] = res[c];
+        }
+        if (a.dbg_w0 && wr(r))
+          for (int idx = lane; idx < NS; idx += 64) a.dbg_w0[(ray0 + r) * NS + idx] = st.w0[r][idx];
+        NSR_T(2);
+        if (fine) {
+          // ---- hierarchical resampling ------------------------------------------------------------
+#ifdef NSR_PHASE_TIMING
+          int64_t* inds = nullptr;             // dbg_inds carries the cycle totals in this build
+#else
+          int64_t* inds = (int64_t*)a.dbg_inds;
+#endif
+          sample_pdf_wave<NI, NS>(&st.w0[r][1], st.zc[r], xs.tf[r], xs.om[r], st.cdf[r], st.zs[r],
+                                  a.u_rays ? a.u_rays + (ray0 + (r < valid ? r : 0)) * 128 : st.ufine,
+                                  (inds && wr(r)) ? inds + (ray0 + r) * NI : nullptr, lane);
+          NSR_T(3);
+          const float sd = zstd_wave<NI>(st, r, lane);
+          if (lane == 0 && wr(r) && a.z_std) a.z_std[ray0 + r] = sd;
+          if (a.dbg_zs && wr(r))
+            for (int k = lane; k < NI; k += 64) a.dbg_zs[(ray0 + r) * NI + k] = st.zs[r][k];
+          NSR_T(4);
+          merge_wave<NI, NS>(st.zc[r], st.zs[r], zf + r * ST::kNF, lane);
+          if (a.dbg_zf && wr(r))
+            for (int k = lane; k < NF; k += 64) a.dbg_zf[(ray0 + r) * NF + k] = zf[r * ST::kNF + k];
+          NSR_T(5);
+        }
+      } else if (pend != -1ll) {
+#ifdef NSR_PHASE_TIMING
+        const long long t0_ = clock64();
+#endif
+        fine_wave(pend, par ^ 1, wave - 2);
+#ifdef NSR_PHASE_TIMING
+        if (threadIdx.x == 128) tacc[7] += clock64() - t0_;
+#endif
       }
-      composite<NS, 2, ST::kNS>(st, &st.zc[0][0], &st.rawc[0][0][0], &st.w0[0][0], &st.tf[0][0], tid, a.noise0, ray0, valid);
+      if (puller) xs.next = queue_item_of(a, ticket);
+      lds_barrier();
+      if (pend != -1ll) fine_out(pend, par ^ 1);
       if (tid < 16 && wr(tid >> 3)) {
         const int r = tid >> 3, c = tid & 7;
         const long long rr = ray0 + r;
-        const float v = st.res[r][c];
+        const float v = xs.res[r][c];
         float* rgb_dst = fine ? a.rgb0 : a.rgb;
         float* disp_dst = fine ? a.disp0 : a.disp;
         float* acc_dst = fine ? a.acc0 : a.acc;
@@ -1275,71 +1648,38 @@ __device__ __forceinline__ void render32_body(const RenderArgs* __restrict__ ap,
         else if (c == 3) { if (disp_dst) disp_dst[rr] = v; }
         else if (c == 4) { if (acc_dst) acc_dst[rr] = v; }
       }
-      if (a.dbg_w0)
-        for (int idx = tid; idx < 2 * NS; idx += 256)
-          if (wr(idx >> LNS)) a.dbg_w0[ray0 * NS + idx] = NS == ST::kNS ? (&st.w0[0][0])[idx] : st.w0[idx >> LNS][idx & (NS - 1)];
+      NSR_T(6);
       if (!fine) {
         if (MODE == kMlpH2 && tid == 0) { if (const unsigned m = range_report(a, ovf, item, valid)) range_poison(a, ray0, m); }
-        __syncthreads();
         if constexpr (NPC > 1) pass = 0;                   // (N_samples = 128: the next item starts with its first coarse pass)
         packed = next_item(); continue;
       }
-      NSR_T(2);
-
-      // ---- hierarchical resampling ----------------------------------------------------------------
-#ifdef NSR_PHASE_TIMING
-      int64_t* inds = nullptr;                 // dbg_inds carries the cycle totals in this build
-#else
-      int64_t* inds = (int64_t*)a.dbg_inds;
-#endif
-      sample_pdf_item<2, NI, NS>(st, st.ufine, &st.w0[0][1], ST::kNS,
-                             [&](int r, int k) { return 0.5f * (st.zc[r][k + 1] + st.zc[r][k]); },   // RN:473
-                             inds ? inds + ray0 * NI : nullptr, NI, tid, valid, a.u_rays, ray0, wmask);
-      NSR_T(3);
-      if (wave < 2) {
-        const float sd = zstd_wave<NI>(st, wave, lane);
-        if (lane == 0 && wr(wave) && a.z_std) a.z_std[ray0 + wave] = sd;
-      }
-      if (a.dbg_zs)
-        for (int idx = tid; idx < 2 * 128; idx += 256)      // st.zs rows are 128 apart, the tap's NI
-          if (wr(idx >> 7) && (idx & 127) < NI) a.dbg_zs[(ray0 + (idx >> 7)) * NI + (idx & 127)] = (&st.zs[0][0])[idx];
-      NSR_T(4);
-      merge_sort_item<2, NI, NS>(st, tid);
-      if (a.dbg_zf)
-        for (int idx = tid; idx < 2 * ST::kNF; idx += 256)      // st.zf rows are kNF apart, the tap's NF
-          if (wr(idx / ST::kNF) && idx % ST::kNF < NF) a.dbg_zf[(ray0 + idx / ST::kNF) * NF + idx % ST::kNF] = (&st.zf[0][0])[idx];
-      NSR_T(5);
       pass = NPC;
     } else if (pass < NPC + NP - 1) {
       ++pass;
     } else {
-      __syncthreads();
-      if (a.dbg_raw) {
-        for (int idx = tid; idx < 2 * ST::kNF * 4; idx += 256)      // st.rawf rows are kNF x 4 apart, the tap's NF x 4
-          if (wr(idx / (ST::kNF * 4)) && idx % (ST::kNF * 4) < NF * 4)
-            a.dbg_raw[(ray0 + idx / (ST::kNF * 4)) * (NF * 4) + idx % (ST::kNF * 4)] = (&st.rawf[0][0][0])[idx];
-        __syncthreads();
-      }
-      composite<NF, 2, ST::kNF>(st, &st.zf[0][0], &st.rawf[0][0][0], &st.wf[0][0], &st.tf[0][0], tid, a.noise1, ray0, valid);
-      if (tid < 16 && wr(tid >> 3)) {
-        const int r = tid >> 3, c = tid & 7;
-        const long long rr = ray0 + r;
-        const float v = st.res[r][c];
-        if (c < 3) { if (a.rgb) a.rgb[rr * 3 + c] = v; }
-        else if (c == 3) { if (a.disp) a.disp[rr] = v; }
-        else if (c == 4) { if (a.acc) a.acc[rr] = v; }
-      }
-      if (MODE == kMlpH2 && tid == 0) { if (const unsigned m = range_report(a, ovf, item, valid)) range_poison(a, ray0, m); }
-      __syncthreads();
-      NSR_T(6);
+      // the item's fine composite, outputs and range report wait for the next item's coarse chain (or the end of the queue)
+      if (tid == 0) xs.pend = packed;
       pass = 0;
-      packed = next_item();
+      par ^= 1;
+      packed = uniform64(xs.next);                         // pulled and published before this item's join barrier
     }
+  }
+  if (fine) {                                  // the last item's fine post-phase has no partner
+    lds_barrier();
+    const long long pend = uniform64(xs.pend);
+    if (pend != -1ll) {
+      if (wave < 2) fine_wave(pend, par ^ 1, wave);
+      lds_barrier();
+      fine_out(pend, par ^ 1);
+    }
+    NSR_T(6);                                  // (timing build: the lone last composite counts into the join / output slot)
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup
 #ifdef NSR_PHASE_TIMING
+  if (tid0 == 128 && a_setup.dbg_raw == nullptr && a_setup.dbg_inds) a_setup.dbg_inds[blockIdx.x * 8 + 7] = tacc[7];   // the fine role's total
   if (tid0 == 0 && a_setup.dbg_raw == nullptr && a_setup.dbg_inds)      // diagnostic hijack: dbg_inds receives [grid][8] cycle totals
-    for (int i = 0; i < 8; ++i) a_setup.dbg_inds[blockIdx.x * 8 + i] = tacc[i];
+    for (int i = 0; i < 7; ++i) a_setup.dbg_inds[blockIdx.x * 8 + i] = tacc[i];
   if (tid0 == 0 && a_setup.dbg_raw == nullptr && a_setup.dbg_inds)      // ... and [grid][4] network-pass breakdowns behind them
     for (int i = 0; i < 4; ++i) a_setup.dbg_inds[(long long)gridDim.x * 8 + blockIdx.x * 4 + i] = tpass[i];
 #endif

@@ -24,12 +24,27 @@ tt = raw_t[:G * 8].reshape(G, 8)
 tt = tt[tt.sum(1) > 0]
 print('variant', V, 'mlp', m.mlp, 'workgroups', len(tt))
 names = ["stage rays", "network passes", "coarse composite+out", "sample_pdf", "z_std+dbg", "merge sort", "fine composite+out", "-"]
+overlapped = None
+if x32:
+    # the x32-structured forward kernels run the post-phases per wave and side by side: slots 2-5 are wave 0's coarse chain (ray 0
+    # of the current item), slot 6 its wait at the join barrier + the output stores of both items, slot 7 the cycles wave 2 spends
+    # in the deferred fine composite of the item before -- next to slots 2-5, so it is not part of the total
+    names = ["stage rays", "network passes", "coarse chain: composite", "coarse chain: sample_pdf", "coarse chain: z_std+dbg",
+             "coarse chain: merge", "join wait + output stores", None]
+    overlapped = tt[:, 7].copy()
+    tt[:, 7] = 0
 if m.schedule == "phases":
     names = ["task start (wait, ray, z load)", "network passes", "coarse post-phase", "z publish", "fine post-phase", "queue pull", "-", "-"]
 tot = tt.sum(1).mean()
 print("kernel ms %.2f  total cycles/WG %.3e (100 MHz counter? ratio to ms: %.1f MHz)" % (ms, tot, tot / ms / 1e3))
 for i, nm in enumerate(names):
-    print("%-22s %6.2f %%   %.3e cycles/WG" % (nm, 100 * tt[:, i].mean() / tot, tt[:, i].mean()))
+    if nm is not None:
+        print("%-26s %6.2f %%   %.3e cycles/WG" % (nm, 100 * tt[:, i].mean() / tot, tt[:, i].mean()))
+if overlapped is not None:
+    chain = tt[:, 2:6].sum(1).mean()
+    print("roles of the merged post-phase: coarse chain (wave 0) %.3e, deferred fine composite (wave 2) %.3e cycles/WG -> critical: %s"
+          % (chain, overlapped.mean(), "coarse chain" if chain >= overlapped.mean() else "fine composite"))
+    print("post-phases on the critical path (all but the network passes): %.2f %%" % (100 * (tot - tt[:, 1].mean()) / tot))
 
 if x32:                                          # the x32-structured kernels also break the network passes down
     tp = raw_t[G * 8:G * 8 + G * 4].reshape(G, 4)
