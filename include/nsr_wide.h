@@ -49,6 +49,13 @@ enum { NSRW_FLAG_TRUNK_ONCHIP = 16 };/* opt-in, f16x2 handles only (nsrw_create 
                                       * output element, so the same bits as layer by layer.  Any other network on such a handle runs
                                       * layer by layer, as do the bf16x3 re-runs (nsrw_trunk_plan says which). */
 
+enum { NSRW_FLAG_HEADS_ONCHIP = 32 };/* opt-in, with NSRW_FLAG_TRUNK_ONCHIP only (nsrw_create refuses it without): wherever the trunk runs on chip
+                                      * the heads -- alpha_linear, feature_linear, views_linears.0 and rgb_linear, or output_linear --
+                                      * run behind it in the same launch on the same rows, and nothing but the raw outputs of a point
+                                      * reaches memory; the same arithmetic per output element, so the same bits.  With view directions
+                                      * the direction encoding must be at most 96 columns wide (multires_views <= 15 is); otherwise
+                                      * the heads stay one launch each behind the trunk launch (nsrw_heads_plan says which). */
+
 typedef struct NsrwConfig {
   int32_t device;
   int32_t n_samples;                 /* N_samples (RN:439): 3 .. NSRW_MAX_SAMPLES -- sample_pdf needs an interior weight; nsrw_create refuses less */
@@ -208,6 +215,15 @@ typedef struct NsrwTrunkPlan {
   char reason[64];
 } NsrwTrunkPlan;
 int nsrw_trunk_plan(const NsrwNet* net, int flags, NsrwTrunkPlan* plan_out);
+
+/* DIAGNOSTIC; needs no device and no handle.  How a handle created with `flags` runs the heads of `net` behind its pts_linears
+ * (DESIGN.md 8): onchip = 1 -- inside the trunk's one launch, kw_trunk_h2<nj, true>, with lds_bytes of LDS per workgroup -- or
+ * onchip = 0 (a GEMM launch per head; lds_bytes = 0) with the reason.  Returns 0, or -1 for an invalid network description. */
+typedef struct NsrwHeadsPlan {
+  int32_t onchip, lds_bytes;
+  char reason[64];
+} NsrwHeadsPlan;
+int nsrw_heads_plan(const NsrwNet* net, int flags, NsrwHeadsPlan* plan_out);
 
 /* libnsr_debug.so (-DNSR_DEBUG_BOUNDS) checks every global / LDS index of this unit's kernels against its extent; a violation is
  * recorded, not trapped.  built_with_checks: 1 in that build, 0 in the product library; first_bad_line: 0 = clean, else the source

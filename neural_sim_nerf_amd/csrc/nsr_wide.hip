@@ -687,6 +687,8 @@ struct Net {
   std::vector<Mat> fwd;               // pts_linears
   int trunk_nj = 0;                   // trunk_plan: 0 = the trunk runs layer by layer, else the NJ of kw_trunk_h2 that runs it on chip
   TrunkLayer* dTrunk = nullptr;       // device: the per-layer table of kw_trunk_h2 (trunk_nj != 0)
+  int trunk_rows = 0;                 // its rows: D, or with heads_onchip the heads behind them (heads_plan)
+  bool heads_onchip = false;          // heads_plan: the trunk launch is the heads form, which leaves nothing but k.RAW
   Mat fa, al, hv, rgb, out;           // feature_linear, alpha_linear, views_linears.0, rgb_linear / output_linear
   std::vector<Mat> bwd_h, bwd_e;      // per pts layer: G W_i[:, hidden part] (i >= 1), G W_i[:, encoding part] (layer 0, skip layers)
   Mat b_rgb, b_feat, b_ed, b_head;
@@ -747,7 +749,7 @@ struct GemmCfg {
   int cus = 256;                        // compute units of the handle's device
   Arith arith = kF32;                   // NsrwConfig::flags: NSRW_FLAG_MLP_F16X2 -> kH2, NSRW_FLAG_MLP_BF16X3 -> kB3, neither -> kF32
   int tile_wm = 4;                      // 256-column tiles with 256 rows / 512 threads (4) or 128 rows / 256 threads (2: NSRW_B3_WM = 2)
-  int flags = 0;                        // NsrwConfig::flags (trunk_plan reads NSRW_FLAG_TRUNK_ONCHIP)
+  int flags = 0;                        // NsrwConfig::flags (trunk_plan reads NSRW_FLAG_TRUNK_ONCHIP, heads_plan NSRW_FLAG_HEADS_ONCHIP)
   unsigned* d_range = nullptr;          // device: [0] flag of the f16x2 pass in flight, [1] passes run, [2] passes re-run on bf16x3
 };
 
@@ -1024,20 +1026,40 @@ NsrwTrunkPlan trunk_plan(const NsrwNet& d, int flags) {
   return p;
 }
 
-// all D pts_linears layers over P points in ONE launch: k.E -> k.H[(D - 1) & 1], where net_forward_chain's layer loop leaves them
+// Whether the heads run behind the on-chip trunk in its launch (kw_trunk_h2<NJ, true>) -- pure host arithmetic, no HIP call
+// (nsrw_heads_plan exposes it).  On chip: NSRW_FLAG_HEADS_ONCHIP, a trunk that trunk_plan puts on chip, and, with view directions,
+// a direction encoding that fits the encoding image it takes over.  The kernel's LDS is the trunk's.
+NsrwHeadsPlan heads_plan(const NsrwNet& d, int flags) {
+  NsrwHeadsPlan p{};
+  auto no = [&](const char* why) { p.onchip = 0; snprintf(p.reason, sizeof p.reason, "%s", why); return p; };
+  if (!check_net(d).empty()) return no("invalid network");
+  if (!(flags & NSRW_FLAG_HEADS_ONCHIP)) return no("NSRW_FLAG_HEADS_ONCHIP not set");
+  const NsrwTrunkPlan t = trunk_plan(d, flags);
+  if (!t.onchip) return no("the trunk is not on chip");
+  if (d.use_viewdirs && pad32(3 + 6 * d.multires_views) > kTrunkCiMax) return no("direction encoding wider than 96");
+  p.onchip = 1;
+  p.lds_bytes = t.lds_bytes;
+  return p;
+}
+
+// all D pts_linears layers over P points in ONE launch: k.E -> k.H[(D - 1) & 1], where net_forward_chain's layer loop leaves them;
+// or (Net::heads_onchip) the heads too: k.E, k.ED -> k.RAW, where net_forward_chain's head launches leave them
 void trunk_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P) {
   TrunkArgs t{};
   t.E = k.E; t.ldE = n.Ci;
   t.img = n.dImg[kH2]; t.img_bytes = (unsigned)n.img_bytes[kH2];
   t.bias = n.dBias; t.bias_floats = n.bias_floats;
-  t.layers = n.dTrunk; t.D = n.d.D;
+  t.layers = n.dTrunk; t.D = n.trunk_rows; t.Dt = n.d.D;
   t.C = k.H[(n.d.D - 1) & 1]; t.Wp = n.Wp;
+  t.ED = n.d.use_viewdirs ? k.ED : nullptr; t.ldED = n.Cv;
+  t.RAW = k.RAW;
   t.M = P;
   t.range_flag = cfg.d_range;
   const long long mblocks = (P + kTrunkRows - 1) / kTrunkRows;
   const unsigned grid = (unsigned)std::min<long long>(mblocks, cfg.cus);
-  if (n.trunk_nj == 1) hipLaunchKernelGGL(kw_trunk_h2<1>, dim3(grid), dim3(512), 0, st, t);
-  else hipLaunchKernelGGL(kw_trunk_h2<2>, dim3(grid), dim3(512), 0, st, t);
+  auto kernel = n.heads_onchip ? (n.trunk_nj == 1 ? kw_trunk_h2<1, true> : kw_trunk_h2<2, true>)
+                               : (n.trunk_nj == 1 ? kw_trunk_h2<1, false> : kw_trunk_h2<2, false>);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), 0, st, t);
 }
 
 // RH:99-122 over P points whose encodings are in k.E / k.ED: leaves the rgb logits in k.RAW (ld 32; all output_linear rows
@@ -1050,6 +1072,10 @@ int net_forward_chain(const GemmCfg& cfg, Run run, hipStream_t st, const Net& n,
   const bool onchip = run.arith == kH2 && !run.run_if && !keep && n.trunk_nj != 0 && P > 0 && P / kTrunkRows < 0x7fffffffll;
   if (onchip) {
     trunk_launch(cfg, st, n, k, P);
+    if (n.heads_onchip) {             // the heads ran behind the trunk: k.H, k.FA and k.HV are not written
+      *sigma = k.RAW + 3; *ld_sigma = n.ldraw;
+      return 0;
+    }
     h = k.H[(n.d.D - 1) & 1];
   }
   for (int i = 0; i < n.d.D && !onchip; ++i) {
@@ -1334,6 +1360,8 @@ int nsrw_create(const NsrwConfig* cfg, nsrw_handle* out) {
   if (cfg->device < 0 || cfg->device >= count) return fail("nsrw_create: no such device");
   if ((cfg->flags & NSRW_FLAG_TRUNK_ONCHIP) && !(cfg->flags & NSRW_FLAG_MLP_F16X2))
     return fail("nsrw_create: NSRW_FLAG_TRUNK_ONCHIP needs NSRW_FLAG_MLP_F16X2 (the on-chip trunk exists for the f16x2 arithmetic only)");
+  if ((cfg->flags & NSRW_FLAG_HEADS_ONCHIP) && !(cfg->flags & NSRW_FLAG_TRUNK_ONCHIP))
+    return fail("nsrw_create: NSRW_FLAG_HEADS_ONCHIP needs NSRW_FLAG_TRUNK_ONCHIP (the on-chip heads run behind the on-chip trunk, in its launch)");
   GemmCfg gc;
   {
     hipDeviceProp_t prop;
@@ -1525,19 +1553,33 @@ int nsrw_upload_network(nsrw_handle hh, int net_id, const NsrwNet* desc, const f
     });
     if (image[a].size() >= 0x7fffffffull) return fail(std::string("nsrw_upload_network: network too large for the ") + arith_name(a) + " image");
   }
-  // the on-chip trunk's per-layer table (launch calls only enqueue)
+  // the on-chip trunk's per-layer table (launch calls only enqueue), with the heads behind the layers where heads_plan says so
   std::vector<TrunkLayer> trunk;
   const NsrwTrunkPlan tp = trunk_plan(*desc, h->gemm_cfg.flags);
   if (tp.onchip) {
     n.trunk_nj = tp.nj;
-    for (int i = 0; i < D; ++i) {
-      const Mat& m = n.fwd[i];
+    n.heads_onchip = heads_plan(*desc, h->gemm_cfg.flags).onchip != 0;
+    // a row: the matrix, its K as k16 blocks of the encoding image and of the activation image, and its epilogue
+    auto row = [&](const Mat& m, int kbe, int kbh, bool h_first, bool relu, int dest, int ncols = 0, int col0 = 0, int ld = 0) {
       TrunkLayer t{};
       t.img_off = (unsigned)m.img[kH2]; t.bias_off = (unsigned)m.b;
-      t.kbe = (i == 0 || n.skip_in[i]) ? Ci / 16 : 0; t.kbh = i == 0 ? 0 : Wp / 16;
+      t.kbe = kbe; t.kbh = kbh;
       t.cscale = m.cscale;
+      t.form = trunk_form(m.ncb, m.Np / 32, h_first, relu, dest); t.store = trunk_store(ncols, col0, ld);
       trunk.push_back(t);
+    };
+    for (int i = 0; i < D; ++i)
+      row(n.fwd[i], (i == 0 || n.skip_in[i]) ? Ci / 16 : 0, i == 0 ? 0 : Wp / 16, false, true,
+          (i + 1 < D || n.heads_onchip) ? kTrunkToLds : kTrunkToC);
+    if (n.heads_onchip && desc->use_viewdirs) {      // net_forward_chain's four head launches, alpha_linear first: it reads the h
+      row(n.al, 0, Wp / 16, false, false, kTrunkToRaw, 1, 3, n.ldraw);                 // that feature_linear overwrites
+      row(n.fa, 0, Wp / 16, false, false, kTrunkToLds);
+      row(n.hv, n.Cv / 16, Wp / 16, true, true, kTrunkToLds);
+      row(n.rgb, 0, n.W2p / 16, false, false, kTrunkToRaw, 3, 0, n.ldraw);
+    } else if (n.heads_onchip) {
+      row(n.out, 0, Wp / 16, false, false, kTrunkToRaw, desc->output_ch, 0, 32);
     }
+    n.trunk_rows = (int)trunk.size();
   }
   n.bias_floats = (unsigned)bias.size();
   NSRW_DEVICE(h);
@@ -1679,6 +1721,14 @@ int nsrw_trunk_plan(const NsrwNet* net, int flags, NsrwTrunkPlan* plan_out) {
   const std::string why = check_net(*net);
   if (!why.empty()) { fail("nsrw_trunk_plan: " + why); return -1; }
   *plan_out = trunk_plan(*net, flags);
+  return 0;
+}
+
+int nsrw_heads_plan(const NsrwNet* net, int flags, NsrwHeadsPlan* plan_out) {
+  if (!net || !plan_out) { fail("nsrw_heads_plan: null argument"); return -1; }
+  const std::string why = check_net(*net);
+  if (!why.empty()) { fail("nsrw_heads_plan: " + why); return -1; }
+  *plan_out = heads_plan(*net, flags);
   return 0;
 }
 

@@ -1,14 +1,25 @@
-// nsr_wide_trunk.inc -- the ON-CHIP trunk of the layered renderer's f16x2 arithmetic: kw_trunk_h2<NJ>, ONE persistent launch that
-// runs all D pts_linears layers (RH:99-107) of a network of packed width Wp <= 128 on a block of 128 points, with the activation
+// nsr_wide_trunk.inc -- the ON-CHIP trunk of the layered renderer's f16x2 arithmetic: kw_trunk_h2<NJ, HEADS>, ONE persistent launch
+// that runs all D pts_linears layers (RH:99-107) of a network of packed width Wp <= 128 on a block of 128 points, with the activation
 // between two layers in LDS instead of HBM.  Included inside namespace nsrw (nsr_wide.hip), after nsr_wide_gemm.inc, whose
-// arithmetic it restates per output element and must reproduce BIT FOR BIT (tests/test_gpu_wide_trunk.py):
+// arithmetic it restates per output element and must reproduce BIT FOR BIT (tests/test_gpu_wide_trunk.py, test_gpu_wide_heads.py):
 //   * the accumulator of an output element starts at 0 and takes the k16 blocks of K = [encoding | h] in ascending order, per
 //     block the piece products (1,0) (0,1) (0,0) on v_mfma_f32_32x32x16_f16, A operand = activation, B operand = weight -- the
 //     operands are the very fragments gemm_split_body feeds: the weights are the same image (Mat::img[kH2]) moved by the same
 //     LDS-DMA, the activation pieces come from split8_h2 and reach the lane (row % 32 + 32 (k % 16 / 8), element k % 8);
 //   * epilogue acc * cscale + bias, relu with NaN kept; the value is then split by split8_h2's formulas (RNE fp16, exact
 //     residual -> fp16) into the next layer's A pieces and fed to amax, so the range flag rises exactly when the per-layer chain's
-//     next launch would raise it.  Only the last layer's fp32 output goes to HBM (rows of Wp floats: what the heads read).
+//     next launch would raise it.  HEADS = false: only the last layer's fp32 output goes to HBM (rows of Wp floats: what the
+//     heads read).
+//
+// HEADS = true (NSRW_FLAG_HEADS_ONCHIP): the last layer is split into LDS like every other and the SAME workgroup runs the heads
+// (RH:109-122) on its 128 rows as further rows of the layer table -- alpha_linear (before h is overwritten), feature_linear (plain
+// epilogue, in place), views_linears.0 on K = [feature | direction encoding] (the direction encodings of the block are split into
+// the encoding image, which the trunk no longer reads), rgb_linear; or output_linear alone -- and stores nothing but the raw
+// outputs, 16 bytes a point with view directions.  A row says its K order, how many column blocks its image has (what the LDS-DMA
+// moves) and how many are computed (a wave whose column blocks hold zero weights only issues no MFMA), its epilogue and where
+// its output goes; the two column halves of the workgroup take the column blocks in turn, so that a head of two column blocks
+// occupies all eight waves.  Every value the per-layer chain would split as an A operand is split here and fed to amax: h, the feature,
+// the direction encoding, the views layer's output.
 //
 // Shape.  512 threads = 8 waves = two per SIMD, as 4 (rows) x 2 (columns): wave w owns rows 32 (w % 4) .. + 31 of the block and the
 // NJ column blocks of half w / 4 (NJ accumulators of 32 x 32).  The accumulator has the column on the lane and the rows in
@@ -20,24 +31,40 @@
 // (8 NJ KiB), fetched one stage ahead ACROSS layer and block boundaries; one barrier per stage = per 6 NJ MFMAs of a wave.
 //
 // LDS (static, one workgroup per CU): weights 2 x 8 NJ KiB, activation 2 pieces x 128 x (128 NJ + 16) B, encoding 2 pieces x
-// 128 x 208 B (Ci <= 96) -- 155 648 B at NJ = 2, 106 496 B at NJ = 1.
+// 128 x 208 B (Ci <= 96; heads form: Cv <= 96 too) -- 155 648 B at NJ = 2, 106 496 B at NJ = 1, in either form.
 #undef NSRW_FILE_TAG
 #define NSRW_FILE_TAG 200000        /* a failed NSRW_CHECK of this file reports 200000 + its line (nsrw_debug_bounds_status) */
 
-struct TrunkLayer {                 // one pts_linears layer; the table is built by nsrw_upload_network (Net::dTrunk)
+enum { kTrunkToLds = 0, kTrunkToC = 1, kTrunkToRaw = 2 };       // TrunkLayer::dest
+
+struct TrunkLayer {                 // one pts_linears layer or, behind them, one head; the table is built by nsrw_upload_network (Net::dTrunk)
   unsigned img_off;                 // byte offset of the layer's f16x2 weight image in Net::dImg[kH2]
   unsigned bias_off;                // its bias in Net::dBias (floats)
-  int kbe, kbh;                     // k16 blocks of K taken from the encoding (layer 0 and skip layers) / from the previous layer
+  int kbe, kbh;                     // k16 blocks of K taken from the encoding image / from the activation image
   float cscale;                     // Mat::cscale
-  int pad_[3];
+  // what the heads form reads on top (the trunk-only form has them fixed: encoding first, 2 NJ col-blocks, relu, the last layer to
+  // C), packed into two words (trunk_form, trunk_store) so that a row stays eight scalar registers:
+  //   form   bits 0-3  col-blocks of the weight image (Mat::ncb <= 2 NJ): what the LDS-DMA moves
+  //          bits 4-7  col-blocks of output that are computed (the rest of the image holds zero weights)
+  //          bit 8     the matrix's K order: 0 = [encoding | hidden] (pts_linears), 1 = [hidden | encoding] (views_linears.0)
+  //          bit 9     epilogue: relu behind acc * cscale + bias
+  //          bits 10-11  kTrunkToLds: split in place into the activation image; kTrunkToC: TrunkArgs::C; kTrunkToRaw:
+  //   store  ... columns 0 .. (bits 0-7) - 1 to TrunkArgs::RAW[row * (bits 16-23) + (bits 8-15) + column]
+  int form, store;
+  int pad_;
 };
+inline int trunk_form(int ncb, int ncbo, bool h_first, bool relu, int dest) { return ncb | ncbo << 4 | (int)h_first << 8 | (int)relu << 9 | dest << 10; }
+inline int trunk_store(int ncols, int col0, int ld) { return ncols | col0 << 8 | ld << 16; }
 
 struct TrunkArgs {
   const float* E; int ldE;          // encodings [M, ldE], ldE = Ci <= kTrunkCiMax
   const char* img; unsigned img_bytes;
   const float* bias; unsigned bias_floats;
-  const TrunkLayer* layers; int D;
-  float* C; int Wp;                 // the last layer's output [M, Wp]
+  const TrunkLayer* layers; int D;  // rows of the table: the pts_linears (trunk-only form), and the heads behind them (heads form)
+  float* C; int Wp;                 // trunk-only form: the last layer's output [M, Wp]
+  int Dt;                           // heads form: the pts_linears among the D rows; the direction encodings [M, ldED], ldED = Cv <=
+  const float* ED; int ldED;        // kTrunkCiMax (nullptr: a network without view directions); the raw outputs the kTrunkToRaw
+  float* RAW;                       // rows store to
   long long M;
   unsigned* range_flag;
 };
@@ -50,8 +77,9 @@ template <int NJ> constexpr int trunk_lds_bytes() { return 2 * trunk_wstage<NJ>(
 
 typedef unsigned short __attribute__((may_alias)) u16a;
 typedef u32x4 __attribute__((may_alias)) u32x4a;
+template <int N> struct TrunkCount { static constexpr int value = N; };          // a compile-time count as a function argument
 
-template <int NJ>
+template <int NJ, bool HEADS>
 __global__ void __launch_bounds__(512, 1) kw_trunk_h2(const TrunkArgs g) {
   constexpr int NCB = 2 * NJ;
   constexpr int kWStage = trunk_wstage<NJ>(), kSH = trunk_sh<NJ>(), kHPiece = kTrunkRows * kSH, kEPiece = kTrunkRows * kTrunkSE;
@@ -61,17 +89,26 @@ __global__ void __launch_bounds__(512, 1) kw_trunk_h2(const TrunkArgs g) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave & 3, wc = wave >> 2;
   const int lrow = lane & 31, lh = lane >> 5;
+  // accumulator j of this wave is column block cb_of(j).  Trunk-only form: the NJ blocks of the wave's half.  Heads form: the two
+  // halves take the blocks in turn, so that a head of two column blocks (views_linears.0 of a wide network) occupies all eight waves
+  auto cb_of = [&](int j) { return HEADS ? 2 * j + wc : wc * NJ + j; };
   const int mblocks = (int)((g.M + kTrunkRows - 1) / kTrunkRows);      // (the host refuses more than 2^31 - 1 blocks)
   if ((int)blockIdx.x >= mblocks) return;
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)g.img, 0, (int)g.img_bytes, 0x00020000);
   const int KBE = g.ldE >> 4, KBH = g.Wp >> 4, ncbr = g.Wp >> 5;
   NSRW_CHECK(KBE >= 2 && KBE <= kKbeMax && KBH >= 2 && KBH <= 8 * NJ && g.D >= 1);
+  if constexpr (HEADS) NSRW_CHECK(g.Dt >= 1 && g.Dt < g.D && (!g.ED || ((g.ldED >> 4) >= 2 && (g.ldED >> 4) <= kKbeMax)));
 
   // weights of the stage (k16 blocks kb0, kb0 + 1 of a layer with KB blocks) -> LDS buffer `buf`: 4 NJ chunks of 2 KiB, each
   // [piece 2][64 lanes][8 fp16] as the image holds it; wave w moves chunk w % (4 NJ) (NJ = 1: every chunk twice, the same bytes to
-  // the same place, so that one wait serves all waves)
-  auto dma = [&](unsigned img_off, int KB, int kb0, int buf) {
+  // the same place, so that one wait serves all waves).  Heads form: the image of a head may have fewer than 2 NJ col-blocks
+  // (`ncb`); the chunks behind them are not moved, and no MFMA reads them.
+  auto dma = [&](unsigned img_off, int KB, int kb0, int buf, int ncb) {
     const int u = wave % (2 * NCB), cb = u % NCB, kbl = u / NCB;
+    if constexpr (HEADS) {
+      NSRW_CHECK(ncb >= 1 && ncb <= NCB);
+      if (cb >= ncb) return;
+    }
     char* l = smem + buf * kWStage + (cb * 2 + kbl) * 2048;
     const int soff = __builtin_amdgcn_readfirstlane((int)img_off + (cb * KB + kb0 + kbl) * 2048);
     NSRW_CHECK(kb0 >= 0 && kb0 + kbl < KB && soff >= 0 && (unsigned)soff + 2048u <= g.img_bytes && (buf == 0 || buf == 1));
@@ -92,48 +129,100 @@ __global__ void __launch_bounds__(512, 1) kw_trunk_h2(const TrunkArgs g) {
   int buf = 0;
   const int row_e = kEOff + (32 * wr + lrow) * kTrunkSE + lh * 16;     // this lane's A fragment of k16 block 0, piece 0
   const int row_h = kHOff + (32 * wr + lrow) * kSH + lh * 16;
+
+  // the encodings X [M, ld] (KBX k16 blocks) of the block at m0 -> the encoding image, in two steps (the heads form puts a layer
+  // between them): lane = (row, k half) loads the 8 consecutive k of its fragment, as gemm_split_body's gload does, for the k16
+  // blocks of its wave's parity; rows behind M are clamped on the way in and never stored.  (Branch-free loads: a block behind KBX
+  // re-reads the last one and is not written.)
+  auto enc_fetch = [&](const float* X, int ld, int KBX, long long m0, f32x4 (&e)[kKbeMax / 2][2]) {
+    long long am = m0 + 32 * wr + lrow;
+    if (am >= g.M) am = g.M - 1;
+    NSRW_CHECK(am >= 0 && am < g.M);
+    const float* ep = X + am * ld + 8 * lh;
+#pragma unroll
+    for (int i = 0; i < kKbeMax / 2; ++i) {
+      const int kb = 2 * i + wc, kc = kb < KBX ? kb : KBX - 1;
+      NSRW_CHECK(kc >= 0 && kc * 16 + 8 * lh + 8 <= ld);
+      e[i][0] = *reinterpret_cast<const f32x4*>(ep + kc * 16);
+      e[i][1] = *reinterpret_cast<const f32x4*>(ep + kc * 16 + 4);
+    }
+  };
+  auto enc_store = [&](int KBX, const f32x4 (&e)[kKbeMax / 2][2]) {
+#pragma unroll
+    for (int i = 0; i < kKbeMax / 2; ++i) {
+      const int kb = 2 * i + wc;
+      if (kb < KBX) {
+        u32x4 p[2];
+        split8_h2(e[i][0], e[i][1], p, amax);
+        NSRW_CHECK(row_e + kEPiece + kb * 32 + 16 <= kLds);
+        *reinterpret_cast<u32x4a*>(smem + row_e + kb * 32) = p[0];
+        *reinterpret_cast<u32x4a*>(smem + row_e + kEPiece + kb * 32) = p[1];
+      }
+    }
+  };
+
+  // one stage of this wave's first NA accumulators: the A fragments at aoff (pieces pstride apart), the weights of buffer `buf`
+  auto stage = [&](auto na, f32x16 (&acc)[NJ], int aoff, int pstride) {
+    constexpr int NA = decltype(na)::value;
+    const char* pb = smem + buf * kWStage + lane * 16;
+    u32x4 fa[2][2], fb[2][NA][2];
+#pragma unroll
+    for (int kbl = 0; kbl < 2; ++kbl) {
+#pragma unroll
+      for (int q = 0; q < 2; ++q) fa[kbl][q] = *reinterpret_cast<const u32x4a*>(smem + aoff + q * pstride + kbl * 32);
+#pragma unroll
+      for (int j = 0; j < NA; ++j)
+#pragma unroll
+        for (int q = 0; q < 2; ++q) fb[kbl][j][q] = *reinterpret_cast<const u32x4a*>(pb + (cb_of(j) * 2 + kbl) * 2048 + q * 1024);
+    }
+    // per accumulator the order of gemm_split_body: k16 blocks ascending, per block (1,0) (0,1) (0,0); the column blocks alternate
+#pragma unroll
+    for (int kbl = 0; kbl < 2; ++kbl) {
+#pragma unroll
+      for (int j = 0; j < NA; ++j) acc[j] = mfma_h2w(fa[kbl][1], fb[kbl][j][0], acc[j]);
+#pragma unroll
+      for (int j = 0; j < NA; ++j) acc[j] = mfma_h2w(fa[kbl][0], fb[kbl][j][1], acc[j]);
+#pragma unroll
+      for (int j = 0; j < NA; ++j) acc[j] = mfma_h2w(fa[kbl][0], fb[kbl][j][0], acc[j]);
+    }
+    NSRW_SGB(NSRW_MASK_DSRD, 4 + 4 * NA);                                // every fragment read of the stage ahead of its MFMAs
+    NSRW_SGB(NSRW_MASK_MFMA, 6 * NA);
+  };
+
   {
     const TrunkLayer l0 = g.layers[0];
-    dma(l0.img_off, l0.kbe + l0.kbh, 0, 0);
+    dma(l0.img_off, l0.kbe + l0.kbh, 0, 0, l0.form & 15);
   }
   for (int mb = blockIdx.x; mb < mblocks; mb += gridDim.x) {
     const long long m0 = (long long)mb * kTrunkRows;
     {
-      // the block's encodings: lane = (row, k half) loads the 8 consecutive k of its fragment, as gemm_split_body's gload does, for
-      // the k16 blocks of its wave's parity; rows behind M are clamped on the way in and never stored.  (Branch-free loads: a
-      // block behind KBE re-reads the last one and is not written.)
-      long long am = m0 + 32 * wr + lrow;
-      if (am >= g.M) am = g.M - 1;
-      NSRW_CHECK(am >= 0 && am < g.M);
-      const float* ep = g.E + am * g.ldE + 8 * lh;
       f32x4 e[kKbeMax / 2][2];
-#pragma unroll
-      for (int i = 0; i < kKbeMax / 2; ++i) {
-        const int kb = 2 * i + wc, kc = kb < KBE ? kb : KBE - 1;
-        NSRW_CHECK(kc >= 0 && kc * 16 + 8 * lh + 8 <= g.ldE);
-        e[i][0] = *reinterpret_cast<const f32x4*>(ep + kc * 16);
-        e[i][1] = *reinterpret_cast<const f32x4*>(ep + kc * 16 + 4);
-      }
-#pragma unroll
-      for (int i = 0; i < kKbeMax / 2; ++i) {
-        const int kb = 2 * i + wc;
-        if (kb < KBE) {
-          u32x4 p[2];
-          split8_h2(e[i][0], e[i][1], p, amax);
-          NSRW_CHECK(row_e + kEPiece + kb * 32 + 16 <= kLds);
-          *reinterpret_cast<u32x4a*>(smem + row_e + kb * 32) = p[0];
-          *reinterpret_cast<u32x4a*>(smem + row_e + kEPiece + kb * 32) = p[1];
-        }
-      }
+      enc_fetch(g.E, g.ldE, KBE, m0, e);
+      enc_store(KBE, e);
     }
     sync();                         // the encodings are written (and, in the first block, the first stage of weights has landed)
     for (int li = 0; li < g.D; ++li) {
       const TrunkLayer L = g.layers[li];
-      const int ln = li + 1 < g.D ? li + 1 : 0;                       // behind the last layer: layer 0 of the next block
+      const int ln = li + 1 < g.D ? li + 1 : 0;                       // behind the last row: layer 0 of the next block
       const unsigned img_next = g.layers[ln].img_off;
       const int kb_next = g.layers[ln].kbe + g.layers[ln].kbh;
+      const int ncb_next = HEADS ? (g.layers[ln].form & 15) : NCB;
       const int KB = L.kbe + L.kbh, nst = KB >> 1;
-      NSRW_CHECK((L.kbe == 0 || L.kbe == KBE) && (L.kbh == 0 || L.kbh == KBH) && KB >= 2 && (KB & 1) == 0);
+      const int L_ncb = L.form & 15, L_ncbo = L.form >> 4 & 15;
+      const bool L_h_first = L.form >> 8 & 1, L_relu = L.form >> 9 & 1;
+      if constexpr (HEADS)
+        NSRW_CHECK(L.kbe >= 0 && L.kbe <= kKbeMax && (L.kbe & 1) == 0 && L.kbh >= 0 && L.kbh <= KBH && (L.kbh & 1) == 0 && KB >= 2 &&
+                   L_ncb >= 1 && L_ncb <= NCB && L_ncbo >= 1 && L_ncbo <= L_ncb);
+      else
+        NSRW_CHECK((L.kbe == 0 || L.kbe == KBE) && (L.kbh == 0 || L.kbh == KBH) && KB >= 2 && (KB & 1) == 0);
+      // heads form: the accumulators of this wave that a column block of the row's output stands behind (cb_of(j) < ncbo: j < na)
+      const int na = HEADS ? ((L_ncbo - wc + 1) >> 1 > NJ ? NJ : (L_ncbo - wc + 1) >> 1) : NJ;
+      // heads form: the block's direction encodings are fetched in front of the last pts_linears layer and stored behind it
+      f32x4 ed[kKbeMax / 2][2];
+      const bool ed_here = HEADS && li + 1 == g.Dt && g.ED;
+      if constexpr (HEADS) {
+        if (ed_here) enc_fetch(g.ED, g.ldED, g.ldED >> 4, m0, ed);
+      }
       f32x16 acc[NJ];
 #pragma unroll
       for (int j = 0; j < NJ; ++j)
@@ -141,57 +230,45 @@ __global__ void __launch_bounds__(512, 1) kw_trunk_h2(const TrunkArgs g) {
         for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
       for (int s = 0; s < nst; ++s) {
         const bool last = s + 1 >= nst;
-        dma(last ? img_next : L.img_off, last ? kb_next : KB, last ? 0 : 2 * s + 2, buf ^ 1);
+        dma(last ? img_next : L.img_off, last ? kb_next : KB, last ? 0 : 2 * s + 2, buf ^ 1, last ? ncb_next : L_ncb);
         const int kb0 = 2 * s;
-        const bool from_e = kb0 < L.kbe;
-        const int aoff = from_e ? row_e + kb0 * 32 : row_h + (kb0 - L.kbe) * 32;
+        bool from_e;
+        int kbr;                                                         // kb0 within its image
+        if (HEADS && L_h_first) { from_e = kb0 >= L.kbh; kbr = from_e ? kb0 - L.kbh : kb0; }
+        else { from_e = kb0 < L.kbe; kbr = from_e ? kb0 : kb0 - L.kbe; }
+        const int aoff = (from_e ? row_e : row_h) + kbr * 32;
         const int pstride = from_e ? kEPiece : kHPiece;
-        NSRW_CHECK(from_e ? (kb0 + 1 < KBE) : (kb0 - L.kbe >= 0 && kb0 - L.kbe + 1 < KBH));
+        if constexpr (HEADS) NSRW_CHECK(kbr >= 0 && kbr + 1 < (from_e ? L.kbe : L.kbh));
+        else NSRW_CHECK(from_e ? (kb0 + 1 < KBE) : (kb0 - L.kbe >= 0 && kb0 - L.kbe + 1 < KBH));
         NSRW_CHECK(aoff >= kHOff && aoff + pstride + 32 + 16 <= kLds);
-        const char* pb = smem + buf * kWStage + (wc * NJ) * 4096 + lane * 16;
-        u32x4 fa[2][2], fb[2][NJ][2];
-#pragma unroll
-        for (int kbl = 0; kbl < 2; ++kbl) {
-#pragma unroll
-          for (int q = 0; q < 2; ++q) fa[kbl][q] = *reinterpret_cast<const u32x4a*>(smem + aoff + q * pstride + kbl * 32);
-#pragma unroll
-          for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int q = 0; q < 2; ++q) fb[kbl][j][q] = *reinterpret_cast<const u32x4a*>(pb + (j * 2 + kbl) * 2048 + q * 1024);
+        if constexpr (HEADS) {
+          if (na >= NJ) stage(TrunkCount<NJ>(), acc, aoff, pstride);
+          else if (NJ > 1 && na == 1) stage(TrunkCount<1>(), acc, aoff, pstride);
+        } else {
+          stage(TrunkCount<NJ>(), acc, aoff, pstride);
         }
-        // per accumulator the order of gemm_split_body: k16 blocks ascending, per block (1,0) (0,1) (0,0); the column blocks alternate
-#pragma unroll
-        for (int kbl = 0; kbl < 2; ++kbl) {
-#pragma unroll
-          for (int j = 0; j < NJ; ++j) acc[j] = mfma_h2w(fa[kbl][1], fb[kbl][j][0], acc[j]);
-#pragma unroll
-          for (int j = 0; j < NJ; ++j) acc[j] = mfma_h2w(fa[kbl][0], fb[kbl][j][1], acc[j]);
-#pragma unroll
-          for (int j = 0; j < NJ; ++j) acc[j] = mfma_h2w(fa[kbl][0], fb[kbl][j][0], acc[j]);
-        }
-        NSRW_SGB(NSRW_MASK_DSRD, 4 + 4 * NJ);                            // every fragment read of the stage ahead of its MFMAs
-        NSRW_SGB(NSRW_MASK_MFMA, 6 * NJ);
         sync();
         buf ^= 1;
       }
       // epilogue: lane owns column n, rows 8 (r / 4) + 4 (lane / 32) + r % 4 of its wave's 32.  Column blocks behind Wp hold zero weights and are dropped.
-      const bool to_hbm = li + 1 == g.D;
+      const int dest = HEADS ? (L.form >> 10 & 3) : (li + 1 == g.D ? kTrunkToC : kTrunkToLds);
+      const int ncbo = HEADS ? L_ncbo : ncbr;
       const bool inside = m0 + kTrunkRows <= g.M;
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
-        const int cb = wc * NJ + j;
-        if (cb < ncbr) {
+        const int cb = cb_of(j);
+        if (cb < ncbo) {
           const int n = cb * 32 + lrow;
-          NSRW_CHECK(n < g.Wp && L.bias_off + (unsigned)n < g.bias_floats);
+          NSRW_CHECK(n < (HEADS ? 32 * ncbo : g.Wp) && L.bias_off + (unsigned)n < g.bias_floats);
           const float b = g.bias[L.bias_off + n];
           f32x4 v[4];
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             float x = acc[j][r] * L.cscale + b;
-            x = (x < 0.0f) ? 0.0f : x;                                   // NaN stays NaN, as through torch's relu
+            if (!HEADS || L_relu) x = (x < 0.0f) ? 0.0f : x;             // NaN stays NaN, as through torch's relu
             v[r >> 2][r & 3] = x;
           }
-          if (!to_hbm) {
+          if (dest == kTrunkToLds) {
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {                             // registers 8 hf .. 8 hf + 7 -> pieces, packed pairs (r, r + 1)
               u32x4 p[2];
@@ -209,7 +286,7 @@ __global__ void __launch_bounds__(512, 1) kw_trunk_h2(const TrunkArgs g) {
                 }
               }
             }
-          } else {
+          } else if (!HEADS) {
             const long long mt = m0 + 32 * wr + 4 * lh;
             float* cp = g.C + mt * g.Wp + n;
             if (inside) {
@@ -223,10 +300,25 @@ __global__ void __launch_bounds__(512, 1) kw_trunk_h2(const TrunkArgs g) {
                 if (mt + ro < g.M) cp[ro * g.Wp] = v[r >> 2][r & 3];
               }
             }
+          } else if (n < (L.store & 255)) {                              // a head's few columns of the raw outputs
+            const int col0 = L.store >> 8 & 255, ld = L.store >> 16 & 255;
+            const long long mt = m0 + 32 * wr + 4 * lh;
+            NSRW_CHECK(dest == kTrunkToRaw && col0 + n < ld);
+            float* rp = g.RAW + mt * ld + col0 + n;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const int ro = 8 * (r >> 2) + (r & 3);
+              if (inside || mt + ro < g.M) rp[ro * ld] = v[r >> 2][r & 3];
+            }
           }
         }
       }
-      if (!to_hbm) {                                                     // the next layer reads what every wave of its rows has written
+      if constexpr (HEADS) {
+        // behind the last pts_linears layer the encoding image is dead: the block's direction encodings take its place (the barrier
+        // below stands between this and views_linears.0's reads, and every later read of the image is behind a stage's barrier)
+        if (ed_here) enc_store(g.ldED >> 4, ed);
+      }
+      if (dest == kTrunkToLds) {                                         // the next layer reads what every wave of its rows has written
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");

@@ -52,6 +52,10 @@ class NsrwTrunkPlan(C.Structure):
     _fields_ = [("onchip", C.c_int32), ("nj", C.c_int32), ("tile_rows", C.c_int32), ("lds_bytes", C.c_int32), ("reason", C.c_char * 64)]
 
 
+class NsrwHeadsPlan(C.Structure):
+    _fields_ = [("onchip", C.c_int32), ("lds_bytes", C.c_int32), ("reason", C.c_char * 64)]
+
+
 # render()'s differentiable outputs (RN:488-494) -> the field of NsrwCotangents and the shape of one ray's cotangent
 COTANGENTS = {"rgb_map": ("d_rgb", 3), "disp_map": ("d_disp", 1), "acc_map": ("d_acc", 1),
               "rgb0": ("d_rgb0", 3), "disp0": ("d_disp0", 1), "acc0": ("d_acc0", 1)}
@@ -80,6 +84,7 @@ SIGNATURES = {
     "nsrw_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "nsrw_gemm_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(NsrwGemmPart), C.c_int]),
     "nsrw_trunk_plan": (C.c_int, [C.POINTER(NsrwNet), C.c_int, C.POINTER(NsrwTrunkPlan)]),
+    "nsrw_heads_plan": (C.c_int, [C.POINTER(NsrwNet), C.c_int, C.POINTER(NsrwHeadsPlan)]),
     "nsrw_debug_bounds_status": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
     "nsrw_range_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "nsrw_sample_pdf": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -87,9 +92,10 @@ SIGNATURES = {
     "nsrw_embed_vjp": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
-FLAG_WHITE_BKGD, FLAG_LINDISP, FLAG_MLP_BF16X3, FLAG_MLP_F16X2, FLAG_TRUNK_ONCHIP = 1, 2, 4, 8, 16
+FLAG_WHITE_BKGD, FLAG_LINDISP, FLAG_MLP_BF16X3, FLAG_MLP_F16X2, FLAG_TRUNK_ONCHIP, FLAG_HEADS_ONCHIP = 1, 2, 4, 8, 16, 32
 MLPS = ("bf16x3", "fp32", "f16x2")
 TRUNKS = ("layers", "onchip")
+HEADS = ("layers", "onchip")
 
 DEFAULT_MLP = "f16x2"           # r06: the fused default kernel's arithmetic; same parity bounds as the fp32 MFMAs and bf16x3 (tests/test_gpu_wide.py
                                 # runs every case on all three), 2.6x / 1.5x their speed; never range-dependent (re-run on bf16x3)
@@ -145,6 +151,21 @@ def trunk_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip"):
         raise _lib.NsrError(lib.nsrw_last_error().decode("utf-8", "replace"))
     if plan.onchip:
         return dict(mode="onchip", nj=int(plan.nj), tile_rows=int(plan.tile_rows), lds_bytes=int(plan.lds_bytes))
+    return dict(mode="layers", reason=plan.reason.decode("utf-8", "replace"))
+
+
+def heads_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", heads="onchip"):
+    """nsrw_heads_plan (diagnostic; no device, no handle): how a handle of arithmetic `mlp` created with trunk=`trunk`,
+    heads=`heads` runs the heads of a network (an NsrwNet or a state dict) behind its pts_linears -- dict(mode="onchip",
+    lds_bytes) for the heads form of the one-launch trunk, or dict(mode="layers", reason=...) for a GEMM launch per head."""
+    lib = load()
+    net = net_or_sd if isinstance(net_or_sd, NsrwNet) else describe(net_or_sd)[0]
+    plan = NsrwHeadsPlan()
+    flags = _mlp_flags(mlp) | (FLAG_TRUNK_ONCHIP if trunk == "onchip" else 0) | (FLAG_HEADS_ONCHIP if heads == "onchip" else 0)
+    if lib.nsrw_heads_plan(C.byref(net), flags, C.byref(plan)) != 0:
+        raise _lib.NsrError(lib.nsrw_last_error().decode("utf-8", "replace"))
+    if plan.onchip:
+        return dict(mode="onchip", lds_bytes=int(plan.lds_bytes))
     return dict(mode="layers", reason=plan.reason.decode("utf-8", "replace"))
 
 
@@ -262,7 +283,7 @@ class WideModel:
     schedule = "layers"
 
     def __init__(self, sd_coarse, sd_fine=None, device=None, n_importance=128, white_bkgd=False, lindisp=False, n_samples=64,
-                 mlp=None, trunk=None):
+                 mlp=None, trunk=None, heads=None):
         """mlp: the arithmetic of the layer GEMMs -- "bf16x3" (bf16 MFMAs on three-way split fp32 operands, fp32-grade results at
         2.67x the matrix-pipe rate: csrc/nsr_wide_gemm.inc), "fp32" (fp32 MFMAs, the strict mode) or "f16x2" (fp16 MFMAs with
         two-piece operands -- the fused default kernel's arithmetic; a network pass that leaves fp16's range is re-run on bf16x3
@@ -270,7 +291,11 @@ class WideModel:
         trunk: "layers" (a GEMM launch per pts_linears layer, activations through HBM) or "onchip" (f16x2 only: a network of
         padded width <= 128 and depth >= 2 runs its pts_linears in ONE launch with the activations in LDS wherever no activation is
         kept for a backward -- the same bits; any other network on the handle runs layer by layer: trunk_plan); default
-        $NSR_WIDE_TRUNK (which handles of the other arithmetics ignore, while an explicit trunk="onchip" there raises), else "layers"."""
+        $NSR_WIDE_TRUNK (which handles of the other arithmetics ignore, while an explicit trunk="onchip" there raises), else "layers".
+        heads: "layers" (a GEMM launch per head behind the trunk) or "onchip" (with trunk="onchip" only: wherever the trunk runs on
+        chip the heads run behind it in the same launch and only the raw outputs reach memory -- the same bits: heads_plan);
+        default $NSR_WIDE_HEADS (which handles that cannot honour it ignore, while an explicit heads="onchip" there raises), else
+        "layers"."""
         mlp = mlp or os.environ.get("NSR_WIDE_MLP") or DEFAULT_MLP
         if mlp not in MLPS:
             raise ValueError("mlp must be one of %s (got %r)" % (MLPS, mlp))
@@ -283,6 +308,16 @@ class WideModel:
         if trunk == "onchip" and mlp != "f16x2":
             raise NotImplementedError("trunk=\"onchip\" exists for mlp=\"f16x2\" only (got mlp=%r)" % (mlp,))
         self.trunk = trunk
+        heads_from_env = not heads
+        heads = heads or os.environ.get("NSR_WIDE_HEADS") or "layers"
+        if heads not in HEADS:
+            raise ValueError("heads must be one of %s (got %r)" % (HEADS, heads))
+        if heads_from_env and (mlp != "f16x2" or trunk != "onchip"):
+            heads = "layers"
+        if heads == "onchip" and (mlp != "f16x2" or trunk != "onchip"):
+            raise NotImplementedError("heads=\"onchip\" runs behind the on-chip trunk: it needs mlp=\"f16x2\" and trunk=\"onchip\" "
+                                      "(got mlp=%r, trunk=%r)" % (mlp, trunk))
+        self.heads = heads
         self.mlp = "layered-" + mlp
         if not torch.cuda.is_available():
             raise _lib.NsrError("no HIP device visible: the render path has no CPU fallback")
@@ -305,7 +340,8 @@ class WideModel:
         self._ws_need = {}                                # (rays, grad) -> bytes one chunk of that many rays needs
         cfg = NsrwConfig(self.device.index, n_samples, n_importance,
                          (FLAG_WHITE_BKGD if white_bkgd else 0) | (FLAG_LINDISP if lindisp else 0) |
-                         _mlp_flags(mlp) | (FLAG_TRUNK_ONCHIP if trunk == "onchip" else 0))
+                         _mlp_flags(mlp) | (FLAG_TRUNK_ONCHIP if trunk == "onchip" else 0) |
+                         (FLAG_HEADS_ONCHIP if heads == "onchip" else 0))
         h = C.c_void_p()
         check(self.lib.nsrw_create(C.byref(cfg), C.byref(h)))
         self.h = h

@@ -46,8 +46,8 @@ def kernel_resources(lib):
         if key.startswith("_ZN4nsrw"):              # the layered renderer's kernels (templates): kw_gemm_h2<4, 1, 4> etc.
             mm = re.match(r"_ZN4nsrw(\d+)", key)
             base = key[len(mm.group(0)):][:int(mm.group(1))]
-            targs = re.match(r"I((?:Li\d+E)+)E", key[len(mm.group(0)) + int(mm.group(1)):])
-            key = base + ("<%s>" % ", ".join(re.findall(r"Li(\d+)E", targs.group(1))) if targs else "")
+            targs = re.match(r"I((?:L[ib]\d+E)+)E", key[len(mm.group(0)) + int(mm.group(1)):])        # int and bool arguments
+            key = base + ("<%s>" % ", ".join(re.findall(r"L[ib](\d+)E", targs.group(1))) if targs else "")
         out[key] = {k: int(get(k).group(1)) for k in (
             "agpr_count", "vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size",
             "group_segment_fixed_size") if get(k)}
