@@ -56,6 +56,12 @@ enum { NSRW_FLAG_HEADS_ONCHIP = 32 };/* opt-in, with NSRW_FLAG_TRUNK_ONCHIP only
                                       * the direction encoding must be at most 96 columns wide (multires_views <= 15 is); otherwise
                                       * the heads stay one launch each behind the trunk launch (nsrw_heads_plan says which). */
 
+enum { NSRW_FLAG_TRUNK_WIDE = 64 }; /* opt-in, with NSRW_FLAG_TRUNK_ONCHIP only (nsrw_create refuses it without): the on-chip trunk also takes
+                                      * networks of padded width 160 .. 256 (the other conditions unchanged), in its wide form -- blocks
+                                      * of 64 points instead of 128, the same arithmetic per output element, so the same bits.  The
+                                      * heads of such a network stay one launch each behind the trunk launch, NSRW_FLAG_HEADS_ONCHIP
+                                      * or not; networks of padded width <= 128 run as without this flag. */
+
 typedef struct NsrwConfig {
   int32_t device;
   int32_t n_samples;                 /* N_samples (RN:439): 3 .. NSRW_MAX_SAMPLES -- sample_pdf needs an interior weight; nsrw_create refuses less */
@@ -209,7 +215,10 @@ int nsrw_gemm_plan(int n_packed_rows, int n_stored_columns, int tile_wm, NsrwGem
 
 /* DIAGNOSTIC; needs no device and no handle.  How a handle created with `flags` runs the pts_linears of `net`: onchip = 1
  * -- one kw_trunk_h2<nj> launch over tiles of tile_rows points with lds_bytes of LDS per workgroup -- or onchip = 0 (layer by layer;
- * nj = tile_rows = lds_bytes = 0) with the reason.  Returns 0, or -1 for an invalid network description (nsrw_last_error says why). */
+ * nj = tile_rows = lds_bytes = 0) with the reason.  nj is the number of 32-column blocks of the output one wave accumulates and
+ * tile_rows says how the eight waves share a tile: tile_rows = 128 is 4 wave rows x 2 wave columns, a tile of 64 nj columns (padded
+ * width <= 128); tile_rows = 64 is the wide form of NSRW_FLAG_TRUNK_WIDE, 2 wave rows x 4 wave columns, nj = 2, a tile of 256
+ * columns (padded width 160 .. 256).  Returns 0, or -1 for an invalid network description (nsrw_last_error says why). */
 typedef struct NsrwTrunkPlan {
   int32_t onchip, nj, tile_rows, lds_bytes;
   char reason[64];
@@ -228,7 +237,7 @@ int nsrw_heads_plan(const NsrwNet* net, int flags, NsrwHeadsPlan* plan_out);
 /* libnsr_debug.so (-DNSR_DEBUG_BOUNDS) checks every global / LDS index of this unit's kernels against its extent; a violation is
  * recorded, not trapped.  built_with_checks: 1 in that build, 0 in the product library; first_bad_line: 0 = clean, else the source
  * line of the (highest) failed check -- nsr_wide.hip's line, 100000 + the line of nsr_wide_gemm.inc, or 200000 + the line of
- * nsr_wide_trunk.inc.  Synchronises the device. */
+ * nsr_wide_trunk.inc (all forms of kw_trunk_h2, the wide one included).  Synchronises the device. */
 int nsrw_debug_bounds_status(int* built_with_checks, unsigned* first_bad_line);
 
 #ifdef __cplusplus

@@ -686,6 +686,7 @@ struct Net {
   size_t img_bytes[kArithSlots] = {};
   std::vector<Mat> fwd;               // pts_linears
   int trunk_nj = 0;                   // trunk_plan: 0 = the trunk runs layer by layer, else the NJ of kw_trunk_h2 that runs it on chip
+  int trunk_tile = 0;                 // ... and its rows per block: 128, or 64 in the wide form (NSRW_FLAG_TRUNK_WIDE)
   TrunkLayer* dTrunk = nullptr;       // device: the per-layer table of kw_trunk_h2 (trunk_nj != 0)
   int trunk_rows = 0;                 // its rows: D, or with heads_onchip the heads behind them (heads_plan)
   bool heads_onchip = false;          // heads_plan: the trunk launch is the heads form, which leaves nothing but k.RAW
@@ -749,7 +750,7 @@ struct GemmCfg {
   int cus = 256;                        // compute units of the handle's device
   Arith arith = kF32;                   // NsrwConfig::flags: NSRW_FLAG_MLP_F16X2 -> kH2, NSRW_FLAG_MLP_BF16X3 -> kB3, neither -> kF32
   int tile_wm = 4;                      // 256-column tiles with 256 rows / 512 threads (4) or 128 rows / 256 threads (2: NSRW_B3_WM = 2)
-  int flags = 0;                        // NsrwConfig::flags (trunk_plan reads NSRW_FLAG_TRUNK_ONCHIP, heads_plan NSRW_FLAG_HEADS_ONCHIP)
+  int flags = 0;                        // NsrwConfig::flags (trunk_plan reads NSRW_FLAG_TRUNK_ONCHIP and _WIDE, heads_plan NSRW_FLAG_HEADS_ONCHIP)
   unsigned* d_range = nullptr;          // device: [0] flag of the f16x2 pass in flight, [1] passes run, [2] passes re-run on bf16x3
 };
 
@@ -1008,7 +1009,8 @@ int gemm(const GemmCfg& cfg, Run run, hipStream_t st, const Net& net, const Mat&
 
 // Whether kw_trunk_h2 runs the pts_linears of `d` on a handle created with `flags` -- pure host arithmetic, no HIP call
 // (nsrw_trunk_plan exposes it).  On chip: an f16x2 handle with NSRW_FLAG_TRUNK_ONCHIP, at least two layers, and a packed width of at
-// most 128, so that the whole N extent is one tile (NJ = 1: <= 64 columns, NJ = 2: 128).  Tiles are 128 rows.
+// most 128, so that the whole N extent is one tile (NJ = 1: <= 64 columns, NJ = 2: 128).  Tiles are 128 rows.  With
+// NSRW_FLAG_TRUNK_WIDE on top, a packed width of 160 .. 256 is on chip too: the wide form, tiles of 64 rows by 256 columns.
 NsrwTrunkPlan trunk_plan(const NsrwNet& d, int flags) {
   NsrwTrunkPlan p{};
   auto no = [&](const char* why) { p.onchip = 0; snprintf(p.reason, sizeof p.reason, "%s", why); return p; };
@@ -1017,12 +1019,13 @@ NsrwTrunkPlan trunk_plan(const NsrwNet& d, int flags) {
   if (!(flags & NSRW_FLAG_TRUNK_ONCHIP)) return no("NSRW_FLAG_TRUNK_ONCHIP not set");
   if (!(flags & NSRW_FLAG_MLP_F16X2)) return no("not an f16x2 handle");
   if (d.D < 2) return no("one layer: nothing to keep on chip");
-  if (pad32(d.W) > 128) return no("padded width above 128");
+  const bool wide = (flags & NSRW_FLAG_TRUNK_WIDE) && pad32(d.W) > 128;
+  if (wide ? pad32(d.W) > 256 : pad32(d.W) > 128) return no(wide ? "padded width above 256" : "padded width above 128");
   if (pad32(3 + 6 * d.multires) > kTrunkCiMax) return no("encoding wider than 96");
   p.onchip = 1;
   p.nj = pad32(d.W) <= 64 ? 1 : 2;
-  p.tile_rows = kTrunkRows;
-  p.lds_bytes = p.nj == 1 ? trunk_lds_bytes<1>() : trunk_lds_bytes<2>();
+  p.tile_rows = wide ? trunk_rows<2>() : trunk_rows<4>();
+  p.lds_bytes = wide ? trunk_lds_bytes<2, 2>() : p.nj == 1 ? trunk_lds_bytes<1>() : trunk_lds_bytes<2>();
   return p;
 }
 
@@ -1036,6 +1039,7 @@ NsrwHeadsPlan heads_plan(const NsrwNet& d, int flags) {
   if (!(flags & NSRW_FLAG_HEADS_ONCHIP)) return no("NSRW_FLAG_HEADS_ONCHIP not set");
   const NsrwTrunkPlan t = trunk_plan(d, flags);
   if (!t.onchip) return no("the trunk is not on chip");
+  if (t.tile_rows != trunk_rows<4>()) return no("padded width above 128: the wide trunk has no heads form");
   if (d.use_viewdirs && pad32(3 + 6 * d.multires_views) > kTrunkCiMax) return no("direction encoding wider than 96");
   p.onchip = 1;
   p.lds_bytes = t.lds_bytes;
@@ -1055,10 +1059,11 @@ void trunk_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk&
   t.RAW = k.RAW;
   t.M = P;
   t.range_flag = cfg.d_range;
-  const long long mblocks = (P + kTrunkRows - 1) / kTrunkRows;
+  const long long mblocks = (P + n.trunk_tile - 1) / n.trunk_tile;
   const unsigned grid = (unsigned)std::min<long long>(mblocks, cfg.cus);
-  auto kernel = n.heads_onchip ? (n.trunk_nj == 1 ? kw_trunk_h2<1, true> : kw_trunk_h2<2, true>)
-                               : (n.trunk_nj == 1 ? kw_trunk_h2<1, false> : kw_trunk_h2<2, false>);
+  auto kernel = n.trunk_tile == trunk_rows<2>() ? kw_trunk_h2<2, false, 2>
+                : n.heads_onchip ? (n.trunk_nj == 1 ? kw_trunk_h2<1, true> : kw_trunk_h2<2, true>)
+                                 : (n.trunk_nj == 1 ? kw_trunk_h2<1, false> : kw_trunk_h2<2, false>);
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), 0, st, t);
 }
 
@@ -1069,7 +1074,7 @@ int net_forward_chain(const GemmCfg& cfg, Run run, hipStream_t st, const Net& n,
   const float* h = nullptr;
   // f16x2 pass of an eligible network on an on-chip handle, no activation kept: the one trunk launch (the conditional bf16x3
   // re-run and every pass that keeps its activations for a backward stay layer by layer)
-  const bool onchip = run.arith == kH2 && !run.run_if && !keep && n.trunk_nj != 0 && P > 0 && P / kTrunkRows < 0x7fffffffll;
+  const bool onchip = run.arith == kH2 && !run.run_if && !keep && n.trunk_nj != 0 && P > 0 && P / n.trunk_tile < 0x7fffffffll;
   if (onchip) {
     trunk_launch(cfg, st, n, k, P);
     if (n.heads_onchip) {             // the heads ran behind the trunk: k.H, k.FA and k.HV are not written
@@ -1360,6 +1365,8 @@ int nsrw_create(const NsrwConfig* cfg, nsrw_handle* out) {
   if (cfg->device < 0 || cfg->device >= count) return fail("nsrw_create: no such device");
   if ((cfg->flags & NSRW_FLAG_TRUNK_ONCHIP) && !(cfg->flags & NSRW_FLAG_MLP_F16X2))
     return fail("nsrw_create: NSRW_FLAG_TRUNK_ONCHIP needs NSRW_FLAG_MLP_F16X2 (the on-chip trunk exists for the f16x2 arithmetic only)");
+  if ((cfg->flags & NSRW_FLAG_TRUNK_WIDE) && !(cfg->flags & NSRW_FLAG_TRUNK_ONCHIP))
+    return fail("nsrw_create: NSRW_FLAG_TRUNK_WIDE needs NSRW_FLAG_TRUNK_ONCHIP (it extends the on-chip trunk to padded widths up to 256)");
   if ((cfg->flags & NSRW_FLAG_HEADS_ONCHIP) && !(cfg->flags & NSRW_FLAG_TRUNK_ONCHIP))
     return fail("nsrw_create: NSRW_FLAG_HEADS_ONCHIP needs NSRW_FLAG_TRUNK_ONCHIP (the on-chip heads run behind the on-chip trunk, in its launch)");
   GemmCfg gc;
@@ -1558,6 +1565,7 @@ int nsrw_upload_network(nsrw_handle hh, int net_id, const NsrwNet* desc, const f
   const NsrwTrunkPlan tp = trunk_plan(*desc, h->gemm_cfg.flags);
   if (tp.onchip) {
     n.trunk_nj = tp.nj;
+    n.trunk_tile = tp.tile_rows;
     n.heads_onchip = heads_plan(*desc, h->gemm_cfg.flags).onchip != 0;
     // a row: the matrix, its K as k16 blocks of the encoding image and of the activation image, and its epilogue
     auto row = [&](const Mat& m, int kbe, int kbh, bool h_first, bool relu, int dest, int ncols = 0, int col0 = 0, int ld = 0) {

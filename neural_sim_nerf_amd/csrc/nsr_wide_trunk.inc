@@ -1,5 +1,5 @@
-// nsr_wide_trunk.inc -- the ON-CHIP trunk of the layered renderer's f16x2 arithmetic: kw_trunk_h2<NJ, HEADS>, ONE persistent launch
-// that runs all D pts_linears layers (RH:99-107) of a network of packed width Wp <= 128 on a block of 128 points, with the activation
+// nsr_wide_trunk.inc -- the ON-CHIP trunk of the layered renderer's f16x2 arithmetic: kw_trunk_h2<NJ, HEADS, WR>, ONE persistent launch
+// that runs all D pts_linears layers (RH:99-107) of a network of packed width Wp <= 128 on a block of 128 points (WR = 2, below: Wp <= 256, 64 points), with the activation
 // between two layers in LDS instead of HBM.  Included inside namespace nsrw (nsr_wide.hip), after nsr_wide_gemm.inc, whose
 // arithmetic it restates per output element and must reproduce BIT FOR BIT (tests/test_gpu_wide_trunk.py, test_gpu_wide_heads.py):
 //   * the accumulator of an output element starts at 0 and takes the k16 blocks of K = [encoding | h] in ascending order, per
@@ -32,6 +32,14 @@
 //
 // LDS (static, one workgroup per CU): weights 2 x 8 NJ KiB, activation 2 pieces x 128 x (128 NJ + 16) B, encoding 2 pieces x
 // 128 x 208 B (Ci <= 96; heads form: Cv <= 96 too) -- 155 648 B at NJ = 2, 106 496 B at NJ = 1, in either form.
+//
+// WR = 2 (NSRW_FLAG_TRUNK_WIDE): the WIDE form, for 128 < Wp <= 256, trunk-only.  The same kernel on a block of 64 points: the eight
+// waves are 2 (rows) x 4 (column quarters), wave w owns rows 32 (w % 2) .. + 31 and the two column blocks of quarter w / 2, so a wave
+// still reads four A and eight B fragments per twelve MFMAs.  A stage is two k16 blocks of EIGHT column blocks (32 KiB; every wave
+// moves both k16 blocks of column block w), the activation image has rows of 528 B (33 slots of 16 bytes: odd, as above).  The weight
+// image of a padded width of 160 or 192 has six column blocks: the two behind them are not moved, and the waves of the last quarter
+// issue no MFMA (their output would be dropped anyway: a column block behind Wp holds zero weights).  LDS: weights 2 x 32 KiB,
+// activation 2 x 64 x 528 B, encoding 2 x 64 x 208 B = 159 744 B.  Per output element nothing differs from WR = 4, hence the same bits.
 #undef NSRW_FILE_TAG
 #define NSRW_FILE_TAG 200000        /* a failed NSRW_CHECK of this file reports 200000 + its line (nsrw_debug_bounds_status) */
 
@@ -69,54 +77,67 @@ struct TrunkArgs {
   unsigned* range_flag;
 };
 
-constexpr int kTrunkRows = 128, kTrunkCiMax = 96;
+// WR wave rows of 32 points by 8 / WR wave columns of NJ column blocks: WR = 4 the 128-row forms, WR = 2 the wide form
+constexpr int kTrunkCiMax = 96;
 constexpr int kTrunkSE = 2 * kTrunkCiMax + 16;                                  // row stride of an encoding piece image (bytes)
-template <int NJ> constexpr int trunk_sh() { return 2 * 64 * NJ + 16; }          // ... of an activation piece image
-template <int NJ> constexpr int trunk_wstage() { return 2 * NJ * 2 * 2048; }     // one stage of weights: 2 NJ col-blocks x 2 k16 blocks
-template <int NJ> constexpr int trunk_lds_bytes() { return 2 * trunk_wstage<NJ>() + 2 * kTrunkRows * trunk_sh<NJ>() + 2 * kTrunkRows * kTrunkSE; }
+template <int WR = 4> constexpr int trunk_rows() { return 32 * WR; }             // points of a block
+template <int NJ, int WR = 4> constexpr int trunk_ncb() { return 8 / WR * NJ; }  // col-blocks of a block's output
+template <int NJ, int WR = 4> constexpr int trunk_sh() { return 64 * trunk_ncb<NJ, WR>() + 16; }          // ... of an activation piece image
+template <int NJ, int WR = 4> constexpr int trunk_wstage() { return trunk_ncb<NJ, WR>() * 2 * 2048; }     // one stage of weights: every col-block x 2 k16 blocks
+template <int NJ, int WR = 4> constexpr int trunk_lds_bytes() {
+  return 2 * trunk_wstage<NJ, WR>() + 2 * trunk_rows<WR>() * trunk_sh<NJ, WR>() + 2 * trunk_rows<WR>() * kTrunkSE;
+}
 
 typedef unsigned short __attribute__((may_alias)) u16a;
 typedef u32x4 __attribute__((may_alias)) u32x4a;
 template <int N> struct TrunkCount { static constexpr int value = N; };          // a compile-time count as a function argument
 
-template <int NJ, bool HEADS>
+template <int NJ, bool HEADS, int WR = 4>
 __global__ void __launch_bounds__(512, 1) kw_trunk_h2(const TrunkArgs g) {
-  constexpr int NCB = 2 * NJ;
-  constexpr int kWStage = trunk_wstage<NJ>(), kSH = trunk_sh<NJ>(), kHPiece = kTrunkRows * kSH, kEPiece = kTrunkRows * kTrunkSE;
-  constexpr int kHOff = 2 * kWStage, kEOff = kHOff + 2 * kHPiece, kLds = trunk_lds_bytes<NJ>();
-  constexpr int kKbeMax = kTrunkCiMax / 16;
+  static_assert((WR == 4 || (WR == 2 && NJ == 2 && !HEADS)), "the wide form is trunk-only, two column blocks a wave");
+  constexpr int WC = 8 / WR, NCB = trunk_ncb<NJ, WR>(), kTrunkRows = trunk_rows<WR>();
+  constexpr int kWStage = trunk_wstage<NJ, WR>(), kSH = trunk_sh<NJ, WR>(), kHPiece = kTrunkRows * kSH, kEPiece = kTrunkRows * kTrunkSE;
+  constexpr int kHOff = 2 * kWStage, kEOff = kHOff + 2 * kHPiece, kLds = trunk_lds_bytes<NJ, WR>();
+  constexpr int kKbeMax = kTrunkCiMax / 16, kEncIt = (kKbeMax + WC - 1) / WC;
+  constexpr bool kNcbVaries = HEADS || WR != 4;       // a row's weight image may have fewer than NCB col-blocks (TrunkLayer::form)
   __shared__ __attribute__((aligned(1024))) char smem[kLds];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wave & 3, wc = wave >> 2;
+  const int wr = wave & (WR - 1), wc = wave >> (WR == 4 ? 2 : 1);
   const int lrow = lane & 31, lh = lane >> 5;
   // accumulator j of this wave is column block cb_of(j).  Trunk-only form: the NJ blocks of the wave's half.  Heads form: the two
   // halves take the blocks in turn, so that a head of two column blocks (views_linears.0 of a wide network) occupies all eight waves
   auto cb_of = [&](int j) { return HEADS ? 2 * j + wc : wc * NJ + j; };
+  static_assert(!HEADS || WC == 2, "the heads form deals the column blocks to two halves");
   const int mblocks = (int)((g.M + kTrunkRows - 1) / kTrunkRows);      // (the host refuses more than 2^31 - 1 blocks)
   if ((int)blockIdx.x >= mblocks) return;
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)g.img, 0, (int)g.img_bytes, 0x00020000);
   const int KBE = g.ldE >> 4, KBH = g.Wp >> 4, ncbr = g.Wp >> 5;
-  NSRW_CHECK(KBE >= 2 && KBE <= kKbeMax && KBH >= 2 && KBH <= 8 * NJ && g.D >= 1);
+  NSRW_CHECK(KBE >= 2 && KBE <= kKbeMax && KBH >= 2 && KBH <= 2 * NCB && g.D >= 1);
   if constexpr (HEADS) NSRW_CHECK(g.Dt >= 1 && g.Dt < g.D && (!g.ED || ((g.ldED >> 4) >= 2 && (g.ldED >> 4) <= kKbeMax)));
 
   // weights of the stage (k16 blocks kb0, kb0 + 1 of a layer with KB blocks) -> LDS buffer `buf`: 4 NJ chunks of 2 KiB, each
   // [piece 2][64 lanes][8 fp16] as the image holds it; wave w moves chunk w % (4 NJ) (NJ = 1: every chunk twice, the same bytes to
-  // the same place, so that one wait serves all waves).  Heads form: the image of a head may have fewer than 2 NJ col-blocks
-  // (`ncb`); the chunks behind them are not moved, and no MFMA reads them.
+  // the same place, so that one wait serves all waves; wide form: 16 chunks, wave w moves w and w + 8, the two k16 blocks of
+  // col-block w).  Heads and wide form: the image of a row may have fewer than NCB col-blocks (`ncb`); the chunks behind them are not
+  // moved, and no MFMA reads them.
   auto dma = [&](unsigned img_off, int KB, int kb0, int buf, int ncb) {
-    const int u = wave % (2 * NCB), cb = u % NCB, kbl = u / NCB;
-    if constexpr (HEADS) {
-      NSRW_CHECK(ncb >= 1 && ncb <= NCB);
-      if (cb >= ncb) return;
-    }
-    char* l = smem + buf * kWStage + (cb * 2 + kbl) * 2048;
-    const int soff = __builtin_amdgcn_readfirstlane((int)img_off + (cb * KB + kb0 + kbl) * 2048);
-    NSRW_CHECK(kb0 >= 0 && kb0 + kbl < KB && soff >= 0 && (unsigned)soff + 2048u <= g.img_bytes && (buf == 0 || buf == 1));
+#pragma unroll
+    for (int c = 0; c < (2 * NCB + 7) / 8; ++c) {
+      const int u = (wave + 8 * c) % (2 * NCB), cb = u % NCB, kbl = u / NCB;
+      if constexpr (kNcbVaries) {
+        NSRW_CHECK(ncb >= 1 && ncb <= NCB);
+        if (cb >= ncb) continue;
+      }
+      char* l = smem + buf * kWStage + (cb * 2 + kbl) * 2048;
+      const int soff = __builtin_amdgcn_readfirstlane((int)img_off + (cb * KB + kb0 + kbl) * 2048);
+      NSRW_CHECK(kb0 >= 0 && kb0 + kbl < KB && soff >= 0 && (unsigned)soff + 2048u <= g.img_bytes && (buf == 0 || buf == 1) &&
+                 buf * kWStage + (cb * 2 + kbl) * 2048 + 2048 <= kHOff);
 #define NSRW_DMA(P)                                                                                                   \
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)l, 16, lane * 16, soff, \
                                            (P) * 1024, 0) /* the immediate offsets BOTH the source and the LDS address */
-    NSRW_DMA(0); NSRW_DMA(1);
+      NSRW_DMA(0); NSRW_DMA(1);
 #undef NSRW_DMA
+    }
   };
   // this wave's LDS-DMA has landed and its LDS reads and writes are done; the barrier makes that true for the workgroup
   auto sync = [&]() {
@@ -132,25 +153,25 @@ __global__ void __launch_bounds__(512, 1) kw_trunk_h2(const TrunkArgs g) {
 
   // the encodings X [M, ld] (KBX k16 blocks) of the block at m0 -> the encoding image, in two steps (the heads form puts a layer
   // between them): lane = (row, k half) loads the 8 consecutive k of its fragment, as gemm_split_body's gload does, for the k16
-  // blocks of its wave's parity; rows behind M are clamped on the way in and never stored.  (Branch-free loads: a block behind KBX
+  // blocks of its wave's column (kb % WC); rows behind M are clamped on the way in and never stored.  (Branch-free loads: a block behind KBX
   // re-reads the last one and is not written.)
-  auto enc_fetch = [&](const float* X, int ld, int KBX, long long m0, f32x4 (&e)[kKbeMax / 2][2]) {
+  auto enc_fetch = [&](const float* X, int ld, int KBX, long long m0, f32x4 (&e)[kEncIt][2]) {
     long long am = m0 + 32 * wr + lrow;
     if (am >= g.M) am = g.M - 1;
     NSRW_CHECK(am >= 0 && am < g.M);
     const float* ep = X + am * ld + 8 * lh;
 #pragma unroll
-    for (int i = 0; i < kKbeMax / 2; ++i) {
-      const int kb = 2 * i + wc, kc = kb < KBX ? kb : KBX - 1;
+    for (int i = 0; i < kEncIt; ++i) {
+      const int kb = WC * i + wc, kc = kb < KBX ? kb : KBX - 1;
       NSRW_CHECK(kc >= 0 && kc * 16 + 8 * lh + 8 <= ld);
       e[i][0] = *reinterpret_cast<const f32x4*>(ep + kc * 16);
       e[i][1] = *reinterpret_cast<const f32x4*>(ep + kc * 16 + 4);
     }
   };
-  auto enc_store = [&](int KBX, const f32x4 (&e)[kKbeMax / 2][2]) {
+  auto enc_store = [&](int KBX, const f32x4 (&e)[kEncIt][2]) {
 #pragma unroll
-    for (int i = 0; i < kKbeMax / 2; ++i) {
-      const int kb = 2 * i + wc;
+    for (int i = 0; i < kEncIt; ++i) {
+      const int kb = WC * i + wc;
       if (kb < KBX) {
         u32x4 p[2];
         split8_h2(e[i][0], e[i][1], p, amax);
@@ -196,7 +217,7 @@ __global__ void __launch_bounds__(512, 1) kw_trunk_h2(const TrunkArgs g) {
   for (int mb = blockIdx.x; mb < mblocks; mb += gridDim.x) {
     const long long m0 = (long long)mb * kTrunkRows;
     {
-      f32x4 e[kKbeMax / 2][2];
+      f32x4 e[kEncIt][2];
       enc_fetch(g.E, g.ldE, KBE, m0, e);
       enc_store(KBE, e);
     }
@@ -206,7 +227,7 @@ __global__ void __launch_bounds__(512, 1) kw_trunk_h2(const TrunkArgs g) {
       const int ln = li + 1 < g.D ? li + 1 : 0;                       // behind the last row: layer 0 of the next block
       const unsigned img_next = g.layers[ln].img_off;
       const int kb_next = g.layers[ln].kbe + g.layers[ln].kbh;
-      const int ncb_next = HEADS ? (g.layers[ln].form & 15) : NCB;
+      const int ncb_next = kNcbVaries ? (g.layers[ln].form & 15) : NCB;
       const int KB = L.kbe + L.kbh, nst = KB >> 1;
       const int L_ncb = L.form & 15, L_ncbo = L.form >> 4 & 15;
       const bool L_h_first = L.form >> 8 & 1, L_relu = L.form >> 9 & 1;
@@ -214,11 +235,12 @@ __global__ void __launch_bounds__(512, 1) kw_trunk_h2(const TrunkArgs g) {
         NSRW_CHECK(L.kbe >= 0 && L.kbe <= kKbeMax && (L.kbe & 1) == 0 && L.kbh >= 0 && L.kbh <= KBH && (L.kbh & 1) == 0 && KB >= 2 &&
                    L_ncb >= 1 && L_ncb <= NCB && L_ncbo >= 1 && L_ncbo <= L_ncb);
       else
-        NSRW_CHECK((L.kbe == 0 || L.kbe == KBE) && (L.kbh == 0 || L.kbh == KBH) && KB >= 2 && (KB & 1) == 0);
+        NSRW_CHECK((L.kbe == 0 || L.kbe == KBE) && (L.kbh == 0 || L.kbh == KBH) && KB >= 2 && (KB & 1) == 0 &&
+                   (!kNcbVaries || (L_ncb >= ncbr && L_ncb <= NCB && (L_ncb & 1) == 0)));
       // heads form: the accumulators of this wave that a column block of the row's output stands behind (cb_of(j) < ncbo: j < na)
       const int na = HEADS ? ((L_ncbo - wc + 1) >> 1 > NJ ? NJ : (L_ncbo - wc + 1) >> 1) : NJ;
       // heads form: the block's direction encodings are fetched in front of the last pts_linears layer and stored behind it
-      f32x4 ed[kKbeMax / 2][2];
+      f32x4 ed[kEncIt][2];
       const bool ed_here = HEADS && li + 1 == g.Dt && g.ED;
       if constexpr (HEADS) {
         if (ed_here) enc_fetch(g.ED, g.ldED, g.ldED >> 4, m0, ed);
@@ -244,6 +266,8 @@ __global__ void __launch_bounds__(512, 1) kw_trunk_h2(const TrunkArgs g) {
         if constexpr (HEADS) {
           if (na >= NJ) stage(TrunkCount<NJ>(), acc, aoff, pstride);
           else if (NJ > 1 && na == 1) stage(TrunkCount<1>(), acc, aoff, pstride);
+        } else if constexpr (WR != 4) {
+          if (wc * NJ < L_ncb) stage(TrunkCount<NJ>(), acc, aoff, pstride);      // (the image holds both of the wave's col-blocks or neither)
         } else {
           stage(TrunkCount<NJ>(), acc, aoff, pstride);
         }
@@ -290,7 +314,7 @@ __global__ void __launch_bounds__(512, 1) kw_trunk_h2(const TrunkArgs g) {
             const long long mt = m0 + 32 * wr + 4 * lh;
             float* cp = g.C + mt * g.Wp + n;
             if (inside) {
-              NSRW_CHECK(mt + 27 < g.M);
+              NSRW_CHECK(mt + 27 < g.M && n < g.Wp);
 #pragma unroll
               for (int r = 0; r < 16; ++r) cp[(8 * (r >> 2) + (r & 3)) * g.Wp] = v[r >> 2][r & 3];
             } else {

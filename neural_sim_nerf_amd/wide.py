@@ -93,9 +93,11 @@ SIGNATURES = {
 }
 
 FLAG_WHITE_BKGD, FLAG_LINDISP, FLAG_MLP_BF16X3, FLAG_MLP_F16X2, FLAG_TRUNK_ONCHIP, FLAG_HEADS_ONCHIP = 1, 2, 4, 8, 16, 32
+FLAG_TRUNK_WIDE = 64
 MLPS = ("bf16x3", "fp32", "f16x2")
 TRUNKS = ("layers", "onchip")
 HEADS = ("layers", "onchip")
+TRUNK_WIDTHS = (128, 256)       # the largest padded width trunk="onchip" takes: 256 adds the wide form (FLAG_TRUNK_WIDE)
 
 DEFAULT_MLP = "f16x2"           # r06: the fused default kernel's arithmetic; same parity bounds as the fp32 MFMAs and bf16x3 (tests/test_gpu_wide.py
                                 # runs every case on all three), 2.6x / 1.5x their speed; never range-dependent (re-run on bf16x3)
@@ -139,14 +141,23 @@ def _mlp_flags(mlp):
     return (FLAG_MLP_BF16X3 if mlp == "bf16x3" else 0) | (FLAG_MLP_F16X2 if mlp == "f16x2" else 0)
 
 
-def trunk_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip"):
-    """nsrw_trunk_plan (diagnostic; no device, no handle): how a handle of arithmetic `mlp` created with trunk=`trunk` runs the
-    pts_linears of a network (an NsrwNet or a state dict) -- dict(mode="onchip", nj, tile_rows, lds_bytes) for the one-launch
-    trunk of csrc/nsr_wide_trunk.inc, or dict(mode="layers", reason=...) for a GEMM launch per layer."""
+def _trunk_flags(trunk, trunk_width=128, heads="layers"):
+    if trunk_width not in TRUNK_WIDTHS:
+        raise ValueError("trunk_width must be one of %s (got %r)" % (TRUNK_WIDTHS, trunk_width))
+    on = trunk == "onchip"
+    return ((FLAG_TRUNK_ONCHIP if on else 0) | (FLAG_TRUNK_WIDE if on and trunk_width == 256 else 0) |
+            (FLAG_HEADS_ONCHIP if heads == "onchip" else 0))
+
+
+def trunk_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", trunk_width=128):
+    """nsrw_trunk_plan (diagnostic; no device, no handle): how a handle of arithmetic `mlp` created with trunk=`trunk`,
+    trunk_width=`trunk_width` runs the pts_linears of a network (an NsrwNet or a state dict) -- dict(mode="onchip", nj, tile_rows,
+    lds_bytes) for the one-launch trunk of csrc/nsr_wide_trunk.inc (tile_rows = 64: its wide form), or dict(mode="layers",
+    reason=...) for a GEMM launch per layer."""
     lib = load()
     net = net_or_sd if isinstance(net_or_sd, NsrwNet) else describe(net_or_sd)[0]
     plan = NsrwTrunkPlan()
-    flags = _mlp_flags(mlp) | (FLAG_TRUNK_ONCHIP if trunk == "onchip" else 0)
+    flags = _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width)
     if lib.nsrw_trunk_plan(C.byref(net), flags, C.byref(plan)) != 0:
         raise _lib.NsrError(lib.nsrw_last_error().decode("utf-8", "replace"))
     if plan.onchip:
@@ -154,14 +165,14 @@ def trunk_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip"):
     return dict(mode="layers", reason=plan.reason.decode("utf-8", "replace"))
 
 
-def heads_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", heads="onchip"):
+def heads_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", heads="onchip", trunk_width=128):
     """nsrw_heads_plan (diagnostic; no device, no handle): how a handle of arithmetic `mlp` created with trunk=`trunk`,
-    heads=`heads` runs the heads of a network (an NsrwNet or a state dict) behind its pts_linears -- dict(mode="onchip",
+    heads=`heads`, trunk_width=`trunk_width` runs the heads of a network (an NsrwNet or a state dict) behind its pts_linears -- dict(mode="onchip",
     lds_bytes) for the heads form of the one-launch trunk, or dict(mode="layers", reason=...) for a GEMM launch per head."""
     lib = load()
     net = net_or_sd if isinstance(net_or_sd, NsrwNet) else describe(net_or_sd)[0]
     plan = NsrwHeadsPlan()
-    flags = _mlp_flags(mlp) | (FLAG_TRUNK_ONCHIP if trunk == "onchip" else 0) | (FLAG_HEADS_ONCHIP if heads == "onchip" else 0)
+    flags = _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width, heads)
     if lib.nsrw_heads_plan(C.byref(net), flags, C.byref(plan)) != 0:
         raise _lib.NsrError(lib.nsrw_last_error().decode("utf-8", "replace"))
     if plan.onchip:
@@ -283,7 +294,7 @@ class WideModel:
     schedule = "layers"
 
     def __init__(self, sd_coarse, sd_fine=None, device=None, n_importance=128, white_bkgd=False, lindisp=False, n_samples=64,
-                 mlp=None, trunk=None, heads=None):
+                 mlp=None, trunk=None, heads=None, trunk_width=None):
         """mlp: the arithmetic of the layer GEMMs -- "bf16x3" (bf16 MFMAs on three-way split fp32 operands, fp32-grade results at
         2.67x the matrix-pipe rate: csrc/nsr_wide_gemm.inc), "fp32" (fp32 MFMAs, the strict mode) or "f16x2" (fp16 MFMAs with
         two-piece operands -- the fused default kernel's arithmetic; a network pass that leaves fp16's range is re-run on bf16x3
@@ -295,7 +306,11 @@ class WideModel:
         heads: "layers" (a GEMM launch per head behind the trunk) or "onchip" (with trunk="onchip" only: wherever the trunk runs on
         chip the heads run behind it in the same launch and only the raw outputs reach memory -- the same bits: heads_plan);
         default $NSR_WIDE_HEADS (which handles that cannot honour it ignore, while an explicit heads="onchip" there raises), else
-        "layers"."""
+        "layers".
+        trunk_width: the largest padded width trunk="onchip" takes -- 128, or 256 (with trunk="onchip" only: networks of padded
+        width 160 .. 256 run their pts_linears in one launch too, on blocks of 64 points instead of 128 -- the same bits; their
+        heads stay a launch each, whatever `heads` says); default $NSR_WIDE_TRUNK_WIDTH (which handles that cannot honour it ignore,
+        while an explicit trunk_width=256 there raises), else 128."""
         mlp = mlp or os.environ.get("NSR_WIDE_MLP") or DEFAULT_MLP
         if mlp not in MLPS:
             raise ValueError("mlp must be one of %s (got %r)" % (MLPS, mlp))
@@ -318,6 +333,19 @@ class WideModel:
             raise NotImplementedError("heads=\"onchip\" runs behind the on-chip trunk: it needs mlp=\"f16x2\" and trunk=\"onchip\" "
                                       "(got mlp=%r, trunk=%r)" % (mlp, trunk))
         self.heads = heads
+        width_from_env = trunk_width is None
+        if width_from_env:
+            env = os.environ.get("NSR_WIDE_TRUNK_WIDTH") or "128"
+            trunk_width = int(env) if env.isdigit() else env
+        if trunk_width not in TRUNK_WIDTHS:
+            raise ValueError("trunk_width must be one of %s (got %r)" % (TRUNK_WIDTHS, trunk_width))
+        trunk_width = int(trunk_width)
+        if width_from_env and (mlp != "f16x2" or trunk != "onchip"):
+            trunk_width = 128
+        if trunk_width == 256 and (mlp != "f16x2" or trunk != "onchip"):
+            raise NotImplementedError("trunk_width=256 widens the on-chip trunk: it needs mlp=\"f16x2\" and trunk=\"onchip\" "
+                                      "(got mlp=%r, trunk=%r)" % (mlp, trunk))
+        self.trunk_width = trunk_width
         self.mlp = "layered-" + mlp
         if not torch.cuda.is_available():
             raise _lib.NsrError("no HIP device visible: the render path has no CPU fallback")
@@ -340,8 +368,7 @@ class WideModel:
         self._ws_need = {}                                # (rays, grad) -> bytes one chunk of that many rays needs
         cfg = NsrwConfig(self.device.index, n_samples, n_importance,
                          (FLAG_WHITE_BKGD if white_bkgd else 0) | (FLAG_LINDISP if lindisp else 0) |
-                         _mlp_flags(mlp) | (FLAG_TRUNK_ONCHIP if trunk == "onchip" else 0) |
-                         (FLAG_HEADS_ONCHIP if heads == "onchip" else 0))
+                         _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width, heads))
         h = C.c_void_p()
         check(self.lib.nsrw_create(C.byref(cfg), C.byref(h)))
         self.h = h

@@ -4,11 +4,12 @@ roofline of its strict mode (kw_gemm_f32: v_mfma_f32_32x32x2_f32) and the yardst
 quoted against; for those the issued fraction of the fp16 / bf16 peak is reported as well.
 
     python tools/bench_wide.py [--hw 400] [--cases ycbv,w512,d10w384,small] [--steps 3] [--trunk layers|onchip|both]
-                                  [--heads layers|onchip|both]
+                                  [--heads layers|onchip|both] [--trunk-width 128|256|both]
 
 --trunk (f16x2): the pts_linears layer by layer (the default), in the one-launch on-chip trunk (csrc/nsr_wide_trunk.inc), or both in
 turn on the same rays in one process -- the comparison DESIGN.md 8 quotes.  --heads (with the on-chip trunk): the heads one launch
-each behind the trunk (the default), inside the trunk's launch, or both in turn.
+each behind the trunk (the default), inside the trunk's launch, or both in turn.  --trunk-width (with the on-chip trunk): the largest
+padded width it takes, 128 (the default), 256 (the wide form: the 8 x 160 .. 8 x 256 cases run their trunk on chip) or both in turn.
 """
 import argparse
 import json
@@ -37,6 +38,9 @@ CASES = {
     "d8w128": (8, 128, 10, 4, [4], 64, 128),
     "d8w192": (8, 192, 10, 4, [4], 64, 128),
     "d4w256": (4, 256, 10, 4, [], 64, 128),
+    # the widths the wide on-chip trunk adds (--trunk-width 256), next to ycbv (8 x 256 at 64 + 128) and d8w192
+    "ycbv48": (8, 256, 10, 4, [4], 48, 100),       # sample counts without a fused kernel
+    "d8w160": (8, 160, 10, 4, [4], 64, 128),
 }
 
 
@@ -74,19 +78,23 @@ def main():
     ap.add_argument("--mlp", default=None, help="bf16x3 | fp32 | f16x2 (default: the library's)")
     ap.add_argument("--trunk", default="layers", choices=("layers", "onchip", "both"))
     ap.add_argument("--heads", default="layers", choices=("layers", "onchip", "both"))
+    ap.add_argument("--trunk-width", default="128", choices=("128", "256", "both"))
     a = ap.parse_args()
     trunks = ("layers", "onchip") if a.trunk == "both" else (a.trunk,)
-    # (trunk, heads): the heads run on chip behind the on-chip trunk only
-    modes = [(t, h) for t in trunks for h in (("layers", "onchip") if a.heads == "both" else (a.heads,)) if t == "onchip" or h == "layers"]
-    if not modes:
-        ap.error("--heads onchip needs --trunk onchip or both")
+    widths = (128, 256) if a.trunk_width == "both" else (int(a.trunk_width),)
+    # (trunk, heads, trunk width): the heads run on chip, and the trunk takes widths up to 256, behind the on-chip trunk only
+    modes = [(t, h, w) for t in trunks for h in (("layers", "onchip") if a.heads == "both" else (a.heads,)) for w in widths
+             if t == "onchip" or (h == "layers" and w == widths[0])]
+    if not modes or (a.trunk == "layers" and a.trunk_width != "128"):
+        ap.error("--heads onchip and --trunk-width 256 need --trunk onchip or both")
     K = S.scaled_K(400.0 / a.hw)
     pose = S.sweep_poses(1, seed=0)[0]
     out = {}
-    for name, trunk, heads in [(c, t, h) for c in a.cases.split(",") for t, h in modes]:
+    for name, trunk, heads, width in [(c, t, h, w) for c in a.cases.split(",") for t, h, w in modes]:
         D, W, L, Lv, skips, ns, ni = CASES[name]
         sd = net_sd(D, W, L, Lv, skips, 1)
-        m = WideModel(sd, sd, n_samples=ns, n_importance=ni, mlp=a.mlp, trunk=trunk, heads=heads)
+        m = WideModel(sd, sd, n_samples=ns, n_importance=ni, mlp=a.mlp, trunk=trunk, heads=heads,
+                      trunk_width=width if trunk == "onchip" else None)
         n = a.hw * a.hw
         evals = n * (ns + ns + ni)
         flop = evals * flop_per_point(sd)
@@ -94,7 +102,8 @@ def main():
         ro, rd = ro.reshape(-1, 3), rd.reshape(-1, 3)
         cot = torch.randn(n, 3, device=m.device)
         res = {"network": "%d x %d, skips %s, %d + %d samples" % (D, W, skips, ns, ni), "rays": n,
-               "flop_per_point": flop_per_point(sd), "mlp": m.mlp, "trunk": m.trunk, "heads": m.heads}
+               "flop_per_point": flop_per_point(sd), "mlp": m.mlp, "trunk": m.trunk, "heads": m.heads,
+               "trunk_width": m.trunk_width}
         for what in ("forward",) + (() if a.no_grad else ("forward+input-gradient",)):
             ms = []
             ps = None
@@ -123,7 +132,8 @@ def main():
                 res[what]["Mray_samples_per_s"] = round(n * (ns + ni) / t / 1e3, 2)
         if m.mlp.endswith("f16x2"):
             res["range_status"] = m.range_status()
-        key = name + (":" + trunk if a.trunk == "both" else "") + (":heads-" + heads if a.heads == "both" else "")
+        key = name + (":" + trunk if a.trunk == "both" else "") + (":heads-" + heads if a.heads == "both" else "") + \
+            (":width-%d" % width if a.trunk_width == "both" and trunk == "onchip" else "")
         out[key] = res
         print(key, json.dumps(res), flush=True)
         m.close()
