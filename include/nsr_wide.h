@@ -62,6 +62,14 @@ enum { NSRW_FLAG_TRUNK_WIDE = 64 }; /* opt-in, with NSRW_FLAG_TRUNK_ONCHIP only 
                                       * heads of such a network stay one launch each behind the trunk launch, NSRW_FLAG_HEADS_ONCHIP
                                       * or not; networks of padded width <= 128 run as without this flag. */
 
+enum { NSRW_FLAG_TRUNK_BWD = 128 }; /* opt-in, with NSRW_FLAG_TRUNK_ONCHIP only (nsrw_create refuses it without, hence without NSRW_FLAG_MLP_F16X2):
+                                      * the gradient calls run the input-gradient chain of a network the on-chip trunk serves in its
+                                      * 128-row form -- per pts layer the products with the transposed weights, the relu masks read from
+                                      * the kept activations -- in one launch behind the backward's head launches, the gradient between
+                                      * two layers in LDS (kw_trunk_bwd_h2); the same arithmetic per output element, so the same bits.
+                                      * The kept forward pass, the bf16x3 re-runs and the networks of the wide form stay layer by layer
+                                      * (nsrw_trunk_bwd_plan says which). */
+
 typedef struct NsrwConfig {
   int32_t device;
   int32_t n_samples;                 /* N_samples (RN:439): 3 .. NSRW_MAX_SAMPLES -- sample_pdf needs an interior weight; nsrw_create refuses less */
@@ -225,6 +233,12 @@ typedef struct NsrwTrunkPlan {
 } NsrwTrunkPlan;
 int nsrw_trunk_plan(const NsrwNet* net, int flags, NsrwTrunkPlan* plan_out);
 
+/* DIAGNOSTIC; needs no device and no handle.  How a handle created with `flags` runs the input-gradient chain of `net` in its gradient
+ * calls: onchip = 1 -- one kw_trunk_bwd_h2<nj> launch over tiles of tile_rows = 128 points with lds_bytes of LDS per
+ * workgroup, nj covering the wider of the padded width and the padded encoding (<= 64 columns: 1, else 2) -- or onchip = 0 (a GEMM
+ * launch per product; nj = tile_rows = lds_bytes = 0) with the reason.  Returns 0, or -1 for an invalid network description. */
+int nsrw_trunk_bwd_plan(const NsrwNet* net, int flags, NsrwTrunkPlan* plan_out);
+
 /* DIAGNOSTIC; needs no device and no handle.  How a handle created with `flags` runs the heads of `net` behind its pts_linears
  * (DESIGN.md 8): onchip = 1 -- inside the trunk's one launch, kw_trunk_h2<nj, true>, with lds_bytes of LDS per workgroup -- or
  * onchip = 0 (a GEMM launch per head; lds_bytes = 0) with the reason.  Returns 0, or -1 for an invalid network description. */
@@ -237,7 +251,7 @@ int nsrw_heads_plan(const NsrwNet* net, int flags, NsrwHeadsPlan* plan_out);
 /* libnsr_debug.so (-DNSR_DEBUG_BOUNDS) checks every global / LDS index of this unit's kernels against its extent; a violation is
  * recorded, not trapped.  built_with_checks: 1 in that build, 0 in the product library; first_bad_line: 0 = clean, else the source
  * line of the (highest) failed check -- nsr_wide.hip's line, 100000 + the line of nsr_wide_gemm.inc, or 200000 + the line of
- * nsr_wide_trunk.inc (all forms of kw_trunk_h2, the wide one included).  Synchronises the device. */
+ * nsr_wide_trunk.inc (all forms of kw_trunk_h2, the wide one included, and kw_trunk_bwd_h2).  Synchronises the device. */
 int nsrw_debug_bounds_status(int* built_with_checks, unsigned* first_bad_line);
 
 #ifdef __cplusplus

@@ -690,6 +690,8 @@ struct Net {
   TrunkLayer* dTrunk = nullptr;       // device: the per-layer table of kw_trunk_h2 (trunk_nj != 0)
   int trunk_rows = 0;                 // its rows: D, or with heads_onchip the heads behind them (heads_plan)
   bool heads_onchip = false;          // heads_plan: the trunk launch is the heads form, which leaves nothing but k.RAW
+  int trunk_bwd_nj = 0;               // trunk_bwd_plan: 0 = net_backward_chain's layer loop, else the NJ of kw_trunk_bwd_h2 that replaces it
+  int trunk_bwd_at = 0, trunk_bwd_rows = 0;       // ... and its rows of dTrunk, behind the forward's
   Mat fa, al, hv, rgb, out;           // feature_linear, alpha_linear, views_linears.0, rgb_linear / output_linear
   std::vector<Mat> bwd_h, bwd_e;      // per pts layer: G W_i[:, hidden part] (i >= 1), G W_i[:, encoding part] (layer 0, skip layers)
   Mat b_rgb, b_feat, b_ed, b_head;
@@ -750,7 +752,7 @@ struct GemmCfg {
   int cus = 256;                        // compute units of the handle's device
   Arith arith = kF32;                   // NsrwConfig::flags: NSRW_FLAG_MLP_F16X2 -> kH2, NSRW_FLAG_MLP_BF16X3 -> kB3, neither -> kF32
   int tile_wm = 4;                      // 256-column tiles with 256 rows / 512 threads (4) or 128 rows / 256 threads (2: NSRW_B3_WM = 2)
-  int flags = 0;                        // NsrwConfig::flags (trunk_plan reads NSRW_FLAG_TRUNK_ONCHIP and _WIDE, heads_plan NSRW_FLAG_HEADS_ONCHIP)
+  int flags = 0;                        // NsrwConfig::flags (trunk_plan reads NSRW_FLAG_TRUNK_ONCHIP and _WIDE, heads_plan NSRW_FLAG_HEADS_ONCHIP, trunk_bwd_plan NSRW_FLAG_TRUNK_BWD)
   unsigned* d_range = nullptr;          // device: [0] flag of the f16x2 pass in flight, [1] passes run, [2] passes re-run on bf16x3
 };
 
@@ -1046,6 +1048,24 @@ NsrwHeadsPlan heads_plan(const NsrwNet& d, int flags) {
   return p;
 }
 
+// Whether kw_trunk_bwd_h2 runs the input-gradient chain of `d` behind the backward's head launches -- pure host arithmetic, no HIP
+// call (nsrw_trunk_bwd_plan exposes it).  On chip: NSRW_FLAG_TRUNK_BWD and a trunk that trunk_plan puts on chip in its 128-row form
+// (hence f16x2 and at least two layers).  nj covers the wider of the two outputs: the hidden width and the encoding.
+NsrwTrunkPlan trunk_bwd_plan(const NsrwNet& d, int flags) {
+  NsrwTrunkPlan p{};
+  auto no = [&](const char* why) { p.onchip = 0; snprintf(p.reason, sizeof p.reason, "%s", why); return p; };
+  if (!check_net(d).empty()) return no("invalid network");
+  if (!(flags & NSRW_FLAG_TRUNK_BWD)) return no("NSRW_FLAG_TRUNK_BWD not set");
+  const NsrwTrunkPlan t = trunk_plan(d, flags);
+  if (!t.onchip) return no("the trunk is not on chip");
+  if (t.tile_rows != trunk_rows<4>()) return no("padded width above 128: the wide trunk has no backward form");
+  p.onchip = 1;                     // (trunk_plan has asked for two layers: there is a hidden row)
+  p.nj = std::max(pad32(d.W) <= 64 ? 1 : 2, pad32(3 + 6 * d.multires) <= 64 ? 1 : 2);
+  p.tile_rows = trunk_rows<4>();
+  p.lds_bytes = p.nj == 1 ? trunk_bwd_lds_bytes<1>() : trunk_bwd_lds_bytes<2>();
+  return p;
+}
+
 // all D pts_linears layers over P points in ONE launch: k.E -> k.H[(D - 1) & 1], where net_forward_chain's layer loop leaves them;
 // or (Net::heads_onchip) the heads too: k.E, k.ED -> k.RAW, where net_forward_chain's head launches leave them
 void trunk_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P) {
@@ -1126,6 +1146,27 @@ int net_forward(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k
   return 0;
 }
 
+// net_backward_chain's layer loop over P points in ONE launch: k.G0 (what b_head left there) and the kept k.H[0 .. D - 2] -> k.GEP
+int trunk_bwd_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P) {
+  const int D = n.d.D;
+  // the kernel addresses the kept activations as one array of D - 1 matrices: carve_chunk lays them out at one stride
+  const long long ldH = k.H[1] - k.H[0];
+  for (int i = 0; i + 1 < D; ++i)
+    if (k.H[i] != k.H[0] + i * ldH) return fail("nsrw: internal error: the kept activations are not equally spaced");
+  TrunkBwdArgs t{};
+  t.G = k.G0; t.Wp = n.Wp;
+  t.img = n.dImg[kH2]; t.img_bytes = (unsigned)n.img_bytes[kH2];
+  t.rows = n.dTrunk + n.trunk_bwd_at; t.R = n.trunk_bwd_rows;
+  t.H0 = k.H[0]; t.ldH = ldH; t.n_masks = D - 1;
+  t.GEP = k.GEP; t.Ci = n.Ci;
+  t.M = P;
+  t.range_flag = cfg.d_range;
+  const long long mblocks = (P + trunk_rows<4>() - 1) / trunk_rows<4>();
+  const unsigned grid = (unsigned)std::min<long long>(mblocks, cfg.cus);
+  hipLaunchKernelGGL(n.trunk_bwd_nj == 1 ? kw_trunk_bwd_h2<1> : kw_trunk_bwd_h2<2>, dim3(grid), dim3(512), 0, st, t);
+  return 0;
+}
+
 // Input-side backward of net_forward (activations kept): k.DRAW [P,32] = dL/d(rgb logits, sigma) -> k.GEP [P,Ci], k.GED [P,Cv].
 int net_backward_chain(const GemmCfg& cfg, Run run, hipStream_t st, const Net& n, const Chunk& k, long long P) {
   float* g = k.G0;
@@ -1139,6 +1180,10 @@ int net_backward_chain(const GemmCfg& cfg, Run run, hipStream_t st, const Net& n
   } else {
     if (gemm(cfg, run, st, n, n.b_head, k.DRAW, 32, nullptr, 0, g, n.Wp, n.Wp, P, 0, k.H[D - 1], n.Wp)) return 1;
   }
+  // f16x2 pass of a network whose backward trunk is on chip (trunk_bwd_plan): the one launch instead of the layer loop (the conditional
+  // bf16x3 re-run stays layer by layer)
+  if (run.arith == kH2 && !run.run_if && n.trunk_bwd_nj != 0 && P > 0 && P / trunk_rows<4>() < 0x7fffffffll)
+    return trunk_bwd_launch(cfg, st, n, k, P);
   bool first_e = true;
   for (int i = D - 1; i >= 0; --i) {          // g = dL/d pre-activation of layer i
     if (i == 0 || n.skip_in[i]) {
@@ -1369,6 +1414,8 @@ int nsrw_create(const NsrwConfig* cfg, nsrw_handle* out) {
     return fail("nsrw_create: NSRW_FLAG_TRUNK_WIDE needs NSRW_FLAG_TRUNK_ONCHIP (it extends the on-chip trunk to padded widths up to 256)");
   if ((cfg->flags & NSRW_FLAG_HEADS_ONCHIP) && !(cfg->flags & NSRW_FLAG_TRUNK_ONCHIP))
     return fail("nsrw_create: NSRW_FLAG_HEADS_ONCHIP needs NSRW_FLAG_TRUNK_ONCHIP (the on-chip heads run behind the on-chip trunk, in its launch)");
+  if ((cfg->flags & NSRW_FLAG_TRUNK_BWD) && !(cfg->flags & NSRW_FLAG_TRUNK_ONCHIP))
+    return fail("nsrw_create: NSRW_FLAG_TRUNK_BWD needs NSRW_FLAG_TRUNK_ONCHIP (the on-chip backward trunk serves the networks the on-chip trunk serves)");
   GemmCfg gc;
   {
     hipDeviceProp_t prop;
@@ -1588,6 +1635,30 @@ int nsrw_upload_network(nsrw_handle hh, int net_id, const NsrwNet* desc, const f
       row(n.out, 0, Wp / 16, false, false, kTrunkToRaw, desc->output_ch, 0, 32);
     }
     n.trunk_rows = (int)trunk.size();
+    // the backward trunk's rows behind them, in the order net_backward_chain issues its launches: per layer i = D - 1 .. 0 the
+    // encoding product (layer 0 and the skip layers; every one but the first adds) and, i > 0, the hidden product masked by h_{i-1}
+    const NsrwTrunkPlan bp = trunk_bwd_plan(*desc, h->gemm_cfg.flags);
+    if (bp.onchip) {
+      n.trunk_bwd_nj = bp.nj;
+      n.trunk_bwd_at = (int)trunk.size();
+      auto brow = [&](const Mat& m, int dest, bool accum, int mask_layer) {
+        TrunkLayer t{};
+        t.img_off = (unsigned)m.img[kH2];
+        t.kbh = Wp / 16;
+        t.cscale = m.cscale;
+        t.form = trunk_bwd_form(m.Np / 32, dest, accum); t.store = mask_layer;
+        trunk.push_back(t);
+      };
+      bool first_e = true;
+      for (int i = D - 1; i >= 0; --i) {
+        if (i == 0 || n.skip_in[i]) {                // (its mask is the one the hidden row behind it reads: fetched, not used)
+          brow(n.bwd_e[i], kTrunkToGep, !first_e, i > 0 ? i - 1 : 0);
+          first_e = false;
+        }
+        if (i > 0) brow(n.bwd_h[i], kTrunkToLds, false, i - 1);
+      }
+      n.trunk_bwd_rows = (int)trunk.size() - n.trunk_bwd_at;
+    }
   }
   n.bias_floats = (unsigned)bias.size();
   NSRW_DEVICE(h);
@@ -1737,6 +1808,14 @@ int nsrw_heads_plan(const NsrwNet* net, int flags, NsrwHeadsPlan* plan_out) {
   const std::string why = check_net(*net);
   if (!why.empty()) { fail("nsrw_heads_plan: " + why); return -1; }
   *plan_out = heads_plan(*net, flags);
+  return 0;
+}
+
+int nsrw_trunk_bwd_plan(const NsrwNet* net, int flags, NsrwTrunkPlan* plan_out) {
+  if (!net || !plan_out) { fail("nsrw_trunk_bwd_plan: null argument"); return -1; }
+  const std::string why = check_net(*net);
+  if (!why.empty()) { fail("nsrw_trunk_bwd_plan: " + why); return -1; }
+  *plan_out = trunk_bwd_plan(*net, flags);
   return 0;
 }
 

@@ -40,6 +40,11 @@
 // image of a padded width of 160 or 192 has six column blocks: the two behind them are not moved, and the waves of the last quarter
 // issue no MFMA (their output would be dropped anyway: a column block behind Wp holds zero weights).  LDS: weights 2 x 32 KiB,
 // activation 2 x 64 x 528 B, encoding 2 x 64 x 208 B = 159 744 B.  Per output element nothing differs from WR = 4, hence the same bits.
+//
+// kw_trunk_bwd_h2<NJ> (NSRW_FLAG_TRUNK_BWD; at the end of this file, with its own description): the BACKWARD sibling, a second
+// __global__ that shares split8_h2, mfma_h2w, the layout constants and the row type with the forms above and leaves them as they
+// were -- the input-gradient chain of net_backward_chain (the masked products with the transposed hidden weights, the summed products
+// with the transposed encoding weights) in one persistent launch over blocks of 128 points, the gradient between two layers in LDS.
 #undef NSRW_FILE_TAG
 #define NSRW_FILE_TAG 200000        /* a failed NSRW_CHECK of this file reports 200000 + its line (nsrw_debug_bounds_status) */
 
@@ -346,6 +351,277 @@ __global__ void __launch_bounds__(512, 1) kw_trunk_h2(const TrunkArgs g) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
+      }
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       // no LDS-DMA may outlive the workgroup
+  if (__builtin_amdgcn_ballot_w64(!(amax < 65504.0f)) != 0ull && lane == 0) atomicOr(g.range_flag, 1u);
+}
+
+// ---- the BACKWARD trunk (NSRW_FLAG_TRUNK_BWD): kw_trunk_bwd_h2<NJ>, the input-gradient chain of net_backward_chain behind its head
+// launches -- per pts layer i = D - 1 .. 0 the product g W_i[:, encoding part] (layer 0 and the skip layers; summed into GEP) and the
+// product g W_i[:, hidden part] masked by relu'(h_{i-1}) (i > 0; the next g) -- in ONE persistent launch over blocks of 128 points,
+// with g in the activation image instead of HBM.  A sibling of kw_trunk_h2<NJ, true>: the same 4 x 2 waves with the column blocks
+// dealt to the two halves in turn, the same weight stages (the transposed images Net::bwd_h / bwd_e inside the same dImg[kH2]), the
+// same piece images, written in place.  No encoding image: 2 x 8 NJ KiB of weights + 2 pieces x 128 x (128 NJ + 16) B = 102 400 B at
+// NJ = 2, 53 248 B at NJ = 1.  Per output element it restates the chain's launches (gemm_split_body<.., NP = 2>) bit for bit
+// (tests/test_gpu_wide_trunk_bwd.py): accumulator from 0, k16 blocks ascending, per block (1,0) (0,1) (0,0), acc * cscale + 0.0f (no
+// bias: the addition turns -0 into +0 as the chain's does), then
+//   * a hidden row (kTrunkToLds): x where the fp32 mask H[i-1][row, n] > 0 and 0 elsewhere (NaN mask: 0), as kMaskEpi; split in place
+//     by split8_h2 and fed to amax -- with the block's incoming g (what b_head left in G0) every value the chain would load as an A
+//     operand, so the range flag rises exactly when the chain would raise it;
+//   * an encoding row (kTrunkToGep): the lane that owns (row, n) owns it in every such row, so the sum lives in registers -- the
+//     first row sets it, every later one computes old + new (old on the left, as kAccum), and behind the last row (layer 0) it is stored:
+//     ((e_first + e_next) + ...) in fp32, the chain's association.  GEP is not an A operand and is not fed to amax.
+// The mask of a row is fetched in front of its stages (an encoding row fetches the mask of the hidden row behind it: branch-free,
+// and the lines are in L2 when that row asks again).  Rows >= M: g is clamped on the way in, their masks read 0 (the mask and GEP go
+// through buffer descriptors of the block's rows inside M), so they add nothing to amax, and their GEP stores are dropped.
+enum { kTrunkToGep = 3 };           // TrunkLayer::form bits 10-11 of a backward row; bit 12: the encoding row adds to the sum
+inline int trunk_bwd_form(int ncbo, int dest, bool accum) { return trunk_form(ncbo, ncbo, false, false, dest) | (int)accum << 12; }
+
+struct TrunkBwdArgs {
+  const float* G; int Wp;           // dL/d pre-activation of the last pts layer [M, Wp] (Chunk::G0)
+  const char* img; unsigned img_bytes;
+  const TrunkLayer* rows; int R;    // the backward rows of the table: kbe = 0, kbh = Wp / 16, store = the index of the mask's layer
+  const float* H0; long long ldH;   // the kept activations: layer l at H0 + l * ldH, [M, Wp] each; n_masks = D - 1 of them are read
+  int n_masks;
+  float* GEP; int Ci;               // dL/d encoding [M, Ci]
+  long long M;
+  unsigned* range_flag;
+};
+
+template <int NJ> constexpr int trunk_bwd_lds_bytes() { return 2 * trunk_wstage<NJ>() + 2 * trunk_rows<4>() * trunk_sh<NJ>(); }
+
+template <int NJ>
+__global__ void __launch_bounds__(512, 1) kw_trunk_bwd_h2(const TrunkBwdArgs g) {
+  constexpr int NCB = trunk_ncb<NJ>(), kTrunkRows = trunk_rows<4>();
+  constexpr int kWStage = trunk_wstage<NJ>(), kSH = trunk_sh<NJ>(), kHPiece = kTrunkRows * kSH;
+  constexpr int kHOff = 2 * kWStage, kLds = trunk_bwd_lds_bytes<NJ>();
+  constexpr int kGIt = NCB;         // k16 blocks of g one wave column splits: kb = 2 i + wc < 2 NCB
+  __shared__ __attribute__((aligned(1024))) char smem[kLds];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wr = wave & 3, wc = wave >> 2;
+  const int lrow = lane & 31, lh = lane >> 5;
+  auto cb_of = [&](int j) { return 2 * j + wc; };                      // the two halves take the column blocks in turn (heads form)
+  const int mblocks = (int)((g.M + kTrunkRows - 1) / kTrunkRows);      // (the host refuses more than 2^31 - 1 blocks)
+  if ((int)blockIdx.x >= mblocks) return;
+  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)g.img, 0, (int)g.img_bytes, 0x00020000);
+  const int KBH = g.Wp >> 4, ncbh = g.Wp >> 5, ncbe = g.Ci >> 5;
+  NSRW_CHECK(KBH >= 2 && KBH <= 2 * NCB && (KBH & 1) == 0 && ncbe >= 1 && ncbe <= NCB && g.R >= 2 && g.n_masks >= 1);
+
+  // kw_trunk_h2's stage of weights, of a row whose image has its first `ncb` col-blocks moved
+  auto dma = [&](unsigned img_off, int kb0, int buf, int ncb) {
+#pragma unroll
+    for (int c = 0; c < (2 * NCB + 7) / 8; ++c) {
+      const int u = (wave + 8 * c) % (2 * NCB), cb = u % NCB, kbl = u / NCB;
+      NSRW_CHECK(ncb >= 1 && ncb <= NCB);
+      if (cb >= ncb) continue;
+      char* l = smem + buf * kWStage + (cb * 2 + kbl) * 2048;
+      const int soff = __builtin_amdgcn_readfirstlane((int)img_off + (cb * KBH + kb0 + kbl) * 2048);
+      NSRW_CHECK(kb0 >= 0 && kb0 + kbl < KBH && soff >= 0 && (unsigned)soff + 2048u <= g.img_bytes && (buf == 0 || buf == 1) &&
+                 buf * kWStage + (cb * 2 + kbl) * 2048 + 2048 <= kHOff);
+#define NSRW_DMA(P)                                                                                                   \
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)l, 16, lane * 16, soff, \
+                                           (P) * 1024, 0) /* the immediate offsets BOTH the source and the LDS address */
+      NSRW_DMA(0); NSRW_DMA(1);
+#undef NSRW_DMA
+    }
+  };
+  // this wave's LDS-DMA and global loads have landed and its LDS reads and writes are done; the barrier makes that true for the workgroup
+  auto sync = [&]() {
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+  };
+
+  float amax = 0.0f;                // largest magnitude this lane has split (the incoming g and every masked g2)
+  int buf = 0;
+  const int row_h = kHOff + (32 * wr + lrow) * kSH + lh * 16;          // this lane's A fragment of k16 block 0, piece 0
+
+  // the block's g -> the activation image, as enc_fetch / enc_store put the encodings into theirs: lane = (row, k half) loads the 8
+  // consecutive k of its fragment for the k16 blocks of its wave's column (kb % 2)
+  auto g_fetch = [&](long long m0, f32x4 (&e)[kGIt][2]) {
+    long long am = m0 + 32 * wr + lrow;
+    if (am >= g.M) am = g.M - 1;
+    NSRW_CHECK(am >= 0 && am < g.M);
+    const float* gp = g.G + am * g.Wp + 8 * lh;
+#pragma unroll
+    for (int i = 0; i < kGIt; ++i) {
+      const int kb = 2 * i + wc, kc = kb < KBH ? kb : KBH - 1;
+      NSRW_CHECK(kc >= 0 && kc * 16 + 8 * lh + 8 <= g.Wp);
+      e[i][0] = *reinterpret_cast<const f32x4*>(gp + kc * 16);
+      e[i][1] = *reinterpret_cast<const f32x4*>(gp + kc * 16 + 4);
+    }
+  };
+  auto g_store = [&](const f32x4 (&e)[kGIt][2]) {
+#pragma unroll
+    for (int i = 0; i < kGIt; ++i) {
+      const int kb = 2 * i + wc;
+      if (kb < KBH) {
+        u32x4 p[2];
+        split8_h2(e[i][0], e[i][1], p, amax);
+        NSRW_CHECK(kb * 32 + lh * 16 + 16 <= kSH - 16 && row_h + kHPiece + kb * 32 + 16 <= kLds);
+        *reinterpret_cast<u32x4a*>(smem + row_h + kb * 32) = p[0];
+        *reinterpret_cast<u32x4a*>(smem + row_h + kHPiece + kb * 32) = p[1];
+      }
+    }
+  };
+
+  // kw_trunk_h2's stage: this wave's first NA accumulators, the A fragments at aoff, the weights of buffer `buf`
+  auto stage = [&](auto na, f32x16 (&acc)[NJ], int aoff) {
+    constexpr int NA = decltype(na)::value;
+    const char* pb = smem + buf * kWStage + lane * 16;
+    u32x4 fa[2][2], fb[2][NA][2];
+#pragma unroll
+    for (int kbl = 0; kbl < 2; ++kbl) {
+#pragma unroll
+      for (int q = 0; q < 2; ++q) fa[kbl][q] = *reinterpret_cast<const u32x4a*>(smem + aoff + q * kHPiece + kbl * 32);
+#pragma unroll
+      for (int j = 0; j < NA; ++j)
+#pragma unroll
+        for (int q = 0; q < 2; ++q) fb[kbl][j][q] = *reinterpret_cast<const u32x4a*>(pb + (cb_of(j) * 2 + kbl) * 2048 + q * 1024);
+    }
+    // per accumulator the order of gemm_split_body: k16 blocks ascending, per block (1,0) (0,1) (0,0); the column blocks alternate
+#pragma unroll
+    for (int kbl = 0; kbl < 2; ++kbl) {
+#pragma unroll
+      for (int j = 0; j < NA; ++j) acc[j] = mfma_h2w(fa[kbl][1], fb[kbl][j][0], acc[j]);
+#pragma unroll
+      for (int j = 0; j < NA; ++j) acc[j] = mfma_h2w(fa[kbl][0], fb[kbl][j][1], acc[j]);
+#pragma unroll
+      for (int j = 0; j < NA; ++j) acc[j] = mfma_h2w(fa[kbl][0], fb[kbl][j][0], acc[j]);
+    }
+    NSRW_SGB(NSRW_MASK_DSRD, 4 + 4 * NA);                                // every fragment read of the stage ahead of its MFMAs
+    NSRW_SGB(NSRW_MASK_MFMA, 6 * NA);
+  };
+
+  // the table through the constant address space: scalar loads, so that a row's fields do not wait in the vector memory queue
+  // behind the masks (the host wrote the table before the launch)
+  const auto rows = (const __attribute__((address_space(4))) TrunkLayer*)(uintptr_t)g.rows;
+  dma(rows[0].img_off, 0, 0, rows[0].form & 15);
+  for (int mb = blockIdx.x; mb < mblocks; mb += gridDim.x) {
+    const long long m0 = (long long)mb * kTrunkRows;
+    const int rows_in = g.M - m0 < kTrunkRows ? (int)(g.M - m0) : kTrunkRows;      // the block's rows inside M
+    const int voff_m = (32 * wr + 4 * lh) * g.Wp + lrow;                // this lane's first element in a block of masks ...
+    const int voff_e = (32 * wr + 4 * lh) * g.Ci + lrow;                // ... and of GEP, from column block 0 (floats)
+    {
+      f32x4 e[kGIt][2];
+      g_fetch(m0, e);
+      g_store(e);
+    }
+    sync();                         // g is written (and, in the first block, the first stage of weights has landed)
+    float gep[NJ][16];              // dL/d encoding of this lane's elements: the sum over the encoding rows so far
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) gep[j][r] = 0.0f;
+    for (int li = 0; li < g.R; ++li) {
+      TrunkLayer L{};
+      L.img_off = rows[li].img_off; L.kbe = rows[li].kbe; L.kbh = rows[li].kbh; L.cscale = rows[li].cscale;
+      L.form = rows[li].form; L.store = rows[li].store;
+      const int ln = li + 1 < g.R ? li + 1 : 0;                       // behind the last row: row 0 of the next block
+      const unsigned img_next = rows[ln].img_off;
+      const int ncb_next = rows[ln].form & 15;
+      const int nst = KBH >> 1;
+      const int L_ncb = L.form & 15, L_ncbo = L.form >> 4 & 15, dest = L.form >> 10 & 3;
+      const bool accum = L.form >> 12 & 1;
+      NSRW_CHECK(L.kbe == 0 && L.kbh == KBH && L_ncb >= 1 && L_ncb <= NCB && L_ncbo == L_ncb && L.store >= 0 && L.store < g.n_masks &&
+                 (dest == kTrunkToLds ? L_ncbo == ncbh : (dest == kTrunkToGep && L_ncbo == ncbe)));
+      // the accumulators of this wave that a column block of the row's output stands behind (cb_of(j) < ncbo: j < na)
+      const int na = (L_ncbo - wc + 1) >> 1 > NJ ? NJ : (L_ncbo - wc + 1) >> 1;
+      // the relu mask of layer L.store at this lane's elements, through a descriptor of the block's rows inside M: branch-free, one
+      // vector offset per lane and a scalar one per element; a row >= M lies behind the extent and reads 0 (its g2 is then 0 and
+      // adds nothing to amax), a column block behind Wp re-reads block 0 (unused)
+      float mk[NJ][16];
+      {
+        const __amdgpu_buffer_rsrc_t mrs =
+            __builtin_amdgcn_make_buffer_rsrc((void*)(g.H0 + L.store * g.ldH + m0 * g.Wp), 0, rows_in * g.Wp * 4, 0x00020000);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          const int cbm = cb_of(j) < ncbh ? cb_of(j) : 0;
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int ro = 8 * (r >> 2) + (r & 3);
+            NSRW_CHECK(rows_in >= 1 && m0 + rows_in <= g.M && 32 * wr + 4 * lh + ro < kTrunkRows && cbm * 32 + lrow < g.Wp);
+            mk[j][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(mrs, voff_m * 4, (ro * g.Wp + cbm * 32) * 4, 0));
+          }
+        }
+      }
+      f32x16 acc[NJ];
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
+      for (int s = 0; s < nst; ++s) {
+        const bool last = s + 1 >= nst;
+        dma(last ? img_next : L.img_off, last ? 0 : 2 * s + 2, buf ^ 1, last ? ncb_next : L_ncb);
+        const int aoff = row_h + 2 * s * 32;
+        NSRW_CHECK(2 * s + 1 < KBH && aoff >= kHOff && aoff + kHPiece + 32 + 16 <= kLds);
+        if (na >= NJ) stage(TrunkCount<NJ>(), acc, aoff);
+        else if (NJ > 1 && na == 1) stage(TrunkCount<1>(), acc, aoff);
+        sync();
+        buf ^= 1;
+      }
+      // epilogue: lane owns column n, rows 8 (r / 4) + 4 (lane / 32) + r % 4 of its wave's 32
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const int cb = cb_of(j);
+        if (cb < L_ncbo) {
+          if (dest == kTrunkToLds) {
+            const int n = cb * 32 + lrow;
+            f32x4 v[4];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const float x = acc[j][r] * L.cscale + 0.0f;
+              v[r >> 2][r & 3] = (mk[j][r] > 0.0f) ? x : 0.0f;
+            }
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {                             // registers 8 hf .. 8 hf + 7 -> pieces, packed pairs (r, r + 1)
+              u32x4 p[2];
+              split8_h2(v[2 * hf], v[2 * hf + 1], p, amax);
+#pragma unroll
+              for (int jj = 0; jj < 4; ++jj) {
+                const int r = 8 * hf + 2 * jj;
+                const int row = 32 * wr + 8 * (r >> 2) + 4 * lh + (r & 3);
+                const int off = kHOff + row * kSH + n * 2;
+                NSRW_CHECK(row + 1 < kTrunkRows && n * 2 + 2 <= kSH - 16 && off + kSH + kHPiece + 2 <= kLds);
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                  *reinterpret_cast<u16a*>(smem + off + q * kHPiece) = (unsigned short)(p[q][jj] & 0xffffu);
+                  *reinterpret_cast<u16a*>(smem + off + q * kHPiece + kSH) = (unsigned short)(p[q][jj] >> 16);
+                }
+              }
+            }
+          } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const float x = acc[j][r] * L.cscale + 0.0f;
+              gep[j][r] = accum ? gep[j][r] + x : x;
+            }
+          }
+        }
+      }
+      if (dest == kTrunkToLds) {                                         // the next row reads what every wave of its rows has written
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+      }
+    }
+    // behind layer 0's row the sum is complete: GEP through a descriptor of the block's rows inside M, as the masks (a row >= M
+    // lies behind the extent: its store is dropped)
+    {
+      const __amdgpu_buffer_rsrc_t ers = __builtin_amdgcn_make_buffer_rsrc((void*)(g.GEP + m0 * g.Ci), 0, rows_in * g.Ci * 4, 0x00020000);
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const int cb = cb_of(j);
+        if (cb < ncbe) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int ro = 8 * (r >> 2) + (r & 3);
+            NSRW_CHECK(rows_in >= 1 && m0 + rows_in <= g.M && 32 * wr + 4 * lh + ro < kTrunkRows && cb * 32 + lrow < g.Ci);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, gep[j][r]), ers, voff_e * 4, (ro * g.Ci + cb * 32) * 4, 0);
+          }
+        }
       }
     }
   }

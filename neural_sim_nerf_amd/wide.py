@@ -85,6 +85,7 @@ SIGNATURES = {
     "nsrw_gemm_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(NsrwGemmPart), C.c_int]),
     "nsrw_trunk_plan": (C.c_int, [C.POINTER(NsrwNet), C.c_int, C.POINTER(NsrwTrunkPlan)]),
     "nsrw_heads_plan": (C.c_int, [C.POINTER(NsrwNet), C.c_int, C.POINTER(NsrwHeadsPlan)]),
+    "nsrw_trunk_bwd_plan": (C.c_int, [C.POINTER(NsrwNet), C.c_int, C.POINTER(NsrwTrunkPlan)]),
     "nsrw_debug_bounds_status": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
     "nsrw_range_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "nsrw_sample_pdf": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -94,9 +95,11 @@ SIGNATURES = {
 
 FLAG_WHITE_BKGD, FLAG_LINDISP, FLAG_MLP_BF16X3, FLAG_MLP_F16X2, FLAG_TRUNK_ONCHIP, FLAG_HEADS_ONCHIP = 1, 2, 4, 8, 16, 32
 FLAG_TRUNK_WIDE = 64
+FLAG_TRUNK_BWD = 128
 MLPS = ("bf16x3", "fp32", "f16x2")
 TRUNKS = ("layers", "onchip")
 HEADS = ("layers", "onchip")
+TRUNK_BWDS = ("layers", "onchip")
 TRUNK_WIDTHS = (128, 256)       # the largest padded width trunk="onchip" takes: 256 adds the wide form (FLAG_TRUNK_WIDE)
 
 DEFAULT_MLP = "f16x2"           # r06: the fused default kernel's arithmetic; same parity bounds as the fp32 MFMAs and bf16x3 (tests/test_gpu_wide.py
@@ -141,12 +144,12 @@ def _mlp_flags(mlp):
     return (FLAG_MLP_BF16X3 if mlp == "bf16x3" else 0) | (FLAG_MLP_F16X2 if mlp == "f16x2" else 0)
 
 
-def _trunk_flags(trunk, trunk_width=128, heads="layers"):
+def _trunk_flags(trunk, trunk_width=128, heads="layers", trunk_bwd="layers"):
     if trunk_width not in TRUNK_WIDTHS:
         raise ValueError("trunk_width must be one of %s (got %r)" % (TRUNK_WIDTHS, trunk_width))
     on = trunk == "onchip"
     return ((FLAG_TRUNK_ONCHIP if on else 0) | (FLAG_TRUNK_WIDE if on and trunk_width == 256 else 0) |
-            (FLAG_HEADS_ONCHIP if heads == "onchip" else 0))
+            (FLAG_HEADS_ONCHIP if heads == "onchip" else 0) | (FLAG_TRUNK_BWD if trunk_bwd == "onchip" else 0))
 
 
 def trunk_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", trunk_width=128):
@@ -177,6 +180,22 @@ def heads_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", heads="onchip", trunk
         raise _lib.NsrError(lib.nsrw_last_error().decode("utf-8", "replace"))
     if plan.onchip:
         return dict(mode="onchip", lds_bytes=int(plan.lds_bytes))
+    return dict(mode="layers", reason=plan.reason.decode("utf-8", "replace"))
+
+
+def trunk_bwd_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", trunk_bwd="onchip", trunk_width=128):
+    """nsrw_trunk_bwd_plan (diagnostic; no device, no handle): how a handle of arithmetic `mlp` created with trunk=`trunk`,
+    trunk_bwd=`trunk_bwd`, trunk_width=`trunk_width` runs the input-gradient chain of a network (an NsrwNet or a state dict) in its
+    gradient calls -- dict(mode="onchip", nj, tile_rows, lds_bytes) for the one-launch backward trunk of csrc/nsr_wide_trunk.inc, or
+    dict(mode="layers", reason=...) for a GEMM launch per product."""
+    lib = load()
+    net = net_or_sd if isinstance(net_or_sd, NsrwNet) else describe(net_or_sd)[0]
+    plan = NsrwTrunkPlan()
+    flags = _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width, trunk_bwd=trunk_bwd)
+    if lib.nsrw_trunk_bwd_plan(C.byref(net), flags, C.byref(plan)) != 0:
+        raise _lib.NsrError(lib.nsrw_last_error().decode("utf-8", "replace"))
+    if plan.onchip:
+        return dict(mode="onchip", nj=int(plan.nj), tile_rows=int(plan.tile_rows), lds_bytes=int(plan.lds_bytes))
     return dict(mode="layers", reason=plan.reason.decode("utf-8", "replace"))
 
 
@@ -294,7 +313,7 @@ class WideModel:
     schedule = "layers"
 
     def __init__(self, sd_coarse, sd_fine=None, device=None, n_importance=128, white_bkgd=False, lindisp=False, n_samples=64,
-                 mlp=None, trunk=None, heads=None, trunk_width=None):
+                 mlp=None, trunk=None, heads=None, trunk_width=None, trunk_bwd=None):
         """mlp: the arithmetic of the layer GEMMs -- "bf16x3" (bf16 MFMAs on three-way split fp32 operands, fp32-grade results at
         2.67x the matrix-pipe rate: csrc/nsr_wide_gemm.inc), "fp32" (fp32 MFMAs, the strict mode) or "f16x2" (fp16 MFMAs with
         two-piece operands -- the fused default kernel's arithmetic; a network pass that leaves fp16's range is re-run on bf16x3
@@ -310,7 +329,12 @@ class WideModel:
         trunk_width: the largest padded width trunk="onchip" takes -- 128, or 256 (with trunk="onchip" only: networks of padded
         width 160 .. 256 run their pts_linears in one launch too, on blocks of 64 points instead of 128 -- the same bits; their
         heads stay a launch each, whatever `heads` says); default $NSR_WIDE_TRUNK_WIDTH (which handles that cannot honour it ignore,
-        while an explicit trunk_width=256 there raises), else 128."""
+        while an explicit trunk_width=256 there raises), else 128.
+        trunk_bwd: "layers" (the gradient calls run a GEMM launch per product of the input-gradient chain) or "onchip" (with
+        trunk="onchip" only: a network the on-chip trunk takes in its 128-row form runs that chain in ONE launch behind the
+        backward's head launches, the gradient between two layers in LDS -- the same bits; the kept forward pass and any other
+        network stay layer by layer: trunk_bwd_plan); default $NSR_WIDE_TRUNK_BWD (which handles that cannot honour it ignore, while
+        an explicit trunk_bwd="onchip" there raises), else "layers"."""
         mlp = mlp or os.environ.get("NSR_WIDE_MLP") or DEFAULT_MLP
         if mlp not in MLPS:
             raise ValueError("mlp must be one of %s (got %r)" % (MLPS, mlp))
@@ -346,6 +370,16 @@ class WideModel:
             raise NotImplementedError("trunk_width=256 widens the on-chip trunk: it needs mlp=\"f16x2\" and trunk=\"onchip\" "
                                       "(got mlp=%r, trunk=%r)" % (mlp, trunk))
         self.trunk_width = trunk_width
+        bwd_from_env = not trunk_bwd
+        trunk_bwd = trunk_bwd or os.environ.get("NSR_WIDE_TRUNK_BWD") or "layers"
+        if trunk_bwd not in TRUNK_BWDS:
+            raise ValueError("trunk_bwd must be one of %s (got %r)" % (TRUNK_BWDS, trunk_bwd))
+        if bwd_from_env and (mlp != "f16x2" or trunk != "onchip"):
+            trunk_bwd = "layers"
+        if trunk_bwd == "onchip" and (mlp != "f16x2" or trunk != "onchip"):
+            raise NotImplementedError("trunk_bwd=\"onchip\" serves the networks the on-chip trunk serves: it needs mlp=\"f16x2\" and "
+                                      "trunk=\"onchip\" (got mlp=%r, trunk=%r)" % (mlp, trunk))
+        self.trunk_bwd = trunk_bwd
         self.mlp = "layered-" + mlp
         if not torch.cuda.is_available():
             raise _lib.NsrError("no HIP device visible: the render path has no CPU fallback")
@@ -368,7 +402,7 @@ class WideModel:
         self._ws_need = {}                                # (rays, grad) -> bytes one chunk of that many rays needs
         cfg = NsrwConfig(self.device.index, n_samples, n_importance,
                          (FLAG_WHITE_BKGD if white_bkgd else 0) | (FLAG_LINDISP if lindisp else 0) |
-                         _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width, heads))
+                         _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width, heads, trunk_bwd))
         h = C.c_void_p()
         check(self.lib.nsrw_create(C.byref(cfg), C.byref(h)))
         self.h = h
