@@ -220,14 +220,14 @@ def dir_norm(rays_d):
     return np.sqrt(_add(_add(sq[..., 0], sq[..., 1]), sq[..., 2])).astype(f32)
 
 
-def embed(x, n_freqs):
-    """RH:18-48: [x, sin(2^0 x), cos(2^0 x), ..., sin(2^(L-1) x), cos(2^(L-1) x)], 3 channels each."""
-    x = x.astype(f32)
+def embed(x, n_freqs, dt=f32):
+    """RH:18-48: [x, sin(2^0 x), cos(2^0 x), ..., sin(2^(L-1) x), cos(2^(L-1) x)], 3 channels each (dt: the arithmetic)."""
+    x = x.astype(dt)
     out = [x]
     for l in range(n_freqs):
-        xs = (x * f32(2.0 ** l)).astype(f32)
-        out.append(np.sin(xs).astype(f32))
-        out.append(np.cos(xs).astype(f32))
+        xs = (x * dt(2.0 ** l)).astype(dt)
+        out.append(np.sin(xs).astype(dt))
+        out.append(np.cos(xs).astype(dt))
     return np.concatenate(out, -1)
 
 
@@ -578,12 +578,12 @@ def sweep_poses(n_views, seed=0):
 # ----------------------------------------------------------------------------------------------
 # network backward (inputs only)
 # ----------------------------------------------------------------------------------------------
-def _network_forward64(sd, pts, dirs):
-    """fp64 forward of RH:99-122 (any shape: net_shape) on fp32 encodings, keeping what the backward needs."""
+def _network_forward64(sd, pts, dirs, dt=f32):
+    """fp64 forward of RH:99-122 (any shape: net_shape) on fp32 encodings (dt=f64: on exact ones), keeping what the backward needs."""
     W = lambda k: sd[k + ".weight"].astype(f64)
     B = lambda k: sd[k + ".bias"].astype(f64)
     D, _, input_ch, input_ch_views, skips, use_viewdirs = net_shape(sd)
-    e_p = embed(pts, (input_ch - 3) // 6).astype(f64)
+    e_p = embed(pts, (input_ch - 3) // 6, dt).astype(f64)
     pre = []
     h = e_p
     for i in range(D):
@@ -595,7 +595,7 @@ def _network_forward64(sd, pts, dirs):
     if not use_viewdirs:                                # RH:119-120
         out = h @ W("output_linear").T + B("output_linear")
         return dict(pre=pre, av=None, sigma=out[:, 3], rgb_raw=out[:, :3])
-    e_d = embed(dirs, (input_ch_views - 3) // 6).astype(f64)
+    e_d = embed(dirs, (input_ch_views - 3) // 6, dt).astype(f64)
     sigma = (h @ W("alpha_linear").T + B("alpha_linear"))[:, 0]
     feat = h @ W("feature_linear").T + B("feature_linear")
     av = np.concatenate([feat, e_d], -1) @ W("views_linears.0").T + B("views_linears.0")
@@ -649,7 +649,7 @@ def network_vjp(sd, pts, dirs, g_raw, fwd=None, relu_on=None):
 # ----------------------------------------------------------------------------------------------
 def render_rays_vjp(sd_coarse, sd_fine, rays_o, rays_d, near, far, grad_rgb,
                     n_samples=N_SAMPLES, n_importance=N_IMPORTANCE, z_fine=None, white_bkgd=False, lindisp=False,
-                    viewdirs=None, noise1=None, randoms=None, relu_on=None, sigma_on=None, parts=None):
+                    viewdirs=None, noise1=None, randoms=None, relu_on=None, sigma_on=None, parts=None, exact=False):
     """d(sum(rgb_map * grad_rgb)) / d(rays_o, rays_d), the quantity torch.autograd.grad(rgb_p, batch_rays,
     grad_outputs=patch_grad_E) returns at RN:177.  Network weights are constants and z_samples is detached
     (RN:475), so gradient reaches the rays only through the FINE pass: pts = o + d*z (RN:478), the view
@@ -657,7 +657,10 @@ def render_rays_vjp(sd_coarse, sd_fine, rays_o, rays_d, near, far, grad_rgb,
     activations pattern.  Returns grad_o [N,3], grad_d [N,3] (float32) and the forward rgb_map.
     viewdirs [N,3]: view directions that are an input of their own (c2w_staticcam RN:91-96, ndc RN:101-103) -- the
     return value then has a fourth entry, dL/d viewdirs, and grad_d holds no view-direction term.  noise1 [N,S]: the fine
-    pass's density noise (RN:365-374); randoms: the forward's draws when z_fine is to be recomputed here."""
+    pass's density noise (RN:365-374); randoms: the forward's draws when z_fine is to be recomputed here.
+    exact (with z_fine given): the points, the view directions, |d| and the encodings in float64 as well -- the function of the fp32
+    inputs itself, not the fp32 forward's rounding of it -- and `parts` also takes the unrounded grad_o / grad_d / grad_v (what
+    oracle/grad_oracle.py's autograd is compared with, to float64 rounding)."""
     rays_o = rays_o.astype(f32)
     rays_d = rays_d.astype(f32)
     N = rays_o.shape[0]
@@ -671,16 +674,24 @@ def render_rays_vjp(sd_coarse, sd_fine, rays_o, rays_d, near, far, grad_rgb,
     S = z_fine.shape[1]
     z = z_fine.astype(f32)
     pts = _add(rays_o[:, None, :], (rays_d[:, None, :] * z[:, :, None]).astype(f32)).reshape(-1, 3)
+    nrm = dir_norm(rays_d).astype(f64)
+    v = normalize_dirs(rays_d).astype(f64)
+    if exact:
+        d64 = rays_d.astype(f64)
+        nrm = np.sqrt((d64 * d64).sum(-1))
+        v = d64 / nrm[:, None]
+        if viewdirs is None:
+            vd = v
+        pts = (rays_o.astype(f64)[:, None, :] + d64[:, None, :] * z.astype(f64)[:, :, None]).reshape(-1, 3)
     dirs = np.broadcast_to(vd[:, None, :], (N, S, 3)).reshape(-1, 3)
     # ---- forward, keeping pre-activations ----
-    fwd = _network_forward64(sd, pts, dirs)
+    fwd = _network_forward64(sd, pts, dirs, f64 if exact else f32)
     sigma, rgb_raw = fwd["sigma"], fwd["rgb_raw"]
     # ---- compositing forward (float64) ----
     sigma = sigma.reshape(N, S)
     if noise1 is not None:
         sigma = _add(sigma.astype(f32), np.asarray(noise1, f32)).astype(f64)     # RN:374: the relu sees raw + noise
     c = 1.0 / (1.0 + np.exp(-rgb_raw.reshape(N, S, 3)))
-    nrm = dir_norm(rays_d).astype(f64)
     dz = np.concatenate([np.diff(z.astype(f64), axis=1), np.full((N, 1), 1e10)], 1)
     delta = dz * nrm[:, None]
     rs = np.maximum(sigma, 0)
@@ -712,10 +723,13 @@ def render_rays_vjp(sd_coarse, sd_fine, rays_o, rays_d, near, far, grad_rgb,
     G_pts = G_pts.reshape(N, S, 3)
     G_v = G_dirs.reshape(N, S, 3).sum(1)
     grad_o = G_pts.sum(1)
-    v = normalize_dirs(rays_d).astype(f64)
     grad_d = (G_pts * z.astype(f64)[:, :, None]).sum(1)
     grad_d += d_nrm[:, None] * v                                                 # d|d|/dd = d/|d|
     if viewdirs is not None:
+        if parts is not None:
+            parts.update(grad_o=grad_o, grad_d=grad_d, grad_v=G_v)
         return grad_o.astype(f32), grad_d.astype(f32), rgb_map.astype(f32), G_v.astype(f32)
     grad_d += (G_v - v * (G_v * v).sum(-1, keepdims=True)) / nrm[:, None]        # d(d/|d|)
+    if parts is not None:
+        parts.update(grad_o=grad_o, grad_d=grad_d)
     return grad_o.astype(f32), grad_d.astype(f32), rgb_map.astype(f32)

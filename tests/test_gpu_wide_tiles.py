@@ -65,7 +65,9 @@ def _nets(oracle, W):
     scales the density row by 50 * 256 / W for sample spacings of ~0.01; at 3 + 2 samples the spacing is ~0.5, a ray would be empty
     (disp = 0 / 0, a NaN gradient: NaN == NaN compares nothing) or opaque at its first sample (a zero gradient).  The row is scaled
     to an eighth of its nn.Linear size and the density bias set to +0.5: densities of 0.5 +- 0.25 on the rays used here, so every
-    ray is translucent in both passes -- weights spread over its samples, finite disp and disp0, gradients through every layer."""
+    ray is translucent in both passes -- weights spread over its samples, finite disp and disp0, gradients through every layer.
+    The last sample is dense too and its distance 1e10, so acc = 1 on every ray and the gradient of acc (and of white_bkgd's
+    1 - acc) is rounding noise here: test_gpu_wide_trunk_bwd._signed_nets is the variant on which it is a gradient."""
     i = WIDTHS.index(W)
     nets = []
     for s in (300, 400):

@@ -36,7 +36,9 @@ SEEDS = {"3x24": (301, 305)}
 @functools.lru_cache(maxsize=None)
 def _nets(oracle, name):
     """(coarse, fine) of NETS[name], with the density scaling of test_gpu_wide_tiles._nets: the density row at an eighth of its
-    nn.Linear size and its bias +0.5, so that every ray is translucent at 3 + 2 samples (finite disp, gradients through every layer)"""
+    nn.Linear size and its bias +0.5, so that every ray is translucent at 3 + 2 samples (finite disp, gradients through every layer).
+    acc = 1 on every ray there (the last sample is dense, its distance 1e10), so acc's gradient is rounding noise on these networks:
+    test_gpu_wide_trunk_bwd._signed_nets is the variant on which it is a gradient."""
     D, W, skips, views = NETS[name]
     nets = []
     for s in SEEDS.get(name, (300 + sorted(NETS).index(name), 400 + sorted(NETS).index(name))):

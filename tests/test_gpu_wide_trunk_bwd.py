@@ -26,13 +26,24 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # alone: its transposed image has three column blocks of weights, the hidden ones two) and the identity encoding (one column block,
 # so that the second wave column computes nothing in an encoding row)
 EXTRA = {"3x40-L15": (3, 40, [1], 15), "3x100-L0": (3, 100, [0], 0)}
+# name -> (scale, bias) of the coarse and of the fine network's density row in the SIGNED-density variant (_signed_nets), searched on
+# the CPU per network so that many rays of the image have, in both passes, a last sample of negative density behind two that count
+# (tests/test_grad_oracle_host.py chooses its rays among them and holds the result to its caps).  SIGNED_ROWS: the seed of a density
+# row drawn anew, N(0, 1 / W), where no scaling of the network's own row gives such rays (2 x 128's coarse density falls or rises
+# along every ray) or only one so large that the density is a badly conditioned multiple of a cancelling dot product (3x40-L15)
+SIGNED = {"2x128": (1.4, 1.2, -27.0, -2.3), "3x100": (28.0, 0.69, -4.1, 0.2), "3x128": (-95.0, -3.6, -6.6, -0.018),
+          "3x24": (-7.7, 2.7, 6.1, -0.4), "3x40": (-8.7, -0.094, 5.8, 0.19), "3x40-noviews": (-5.5, -0.45, -8.4, -0.41),
+          "5x100": (-3.8, -0.26, 23.0, -0.3), "3x100-L0": (-76.0, 0.099, 6.1, 0.29), "3x40-L15": (0.34, 0.23, 0.31, -0.17)}
+SIGNED_ROWS = {"2x128": (1004, None), "3x40-L15": (3002, 4001)}
 RANGE_LOG2 = 14             # log2 of the weight that sends one gradient out of fp16's range (_range_nets)
 
 
 @functools.lru_cache(maxsize=None)
 def _nets(oracle, name):
     """(coarse, fine) of NETS[name] or EXTRA[name], with the density scaling of test_gpu_wide_trunk._nets (every ray translucent at
-    3 + 2 samples: finite disp, gradients through every layer)"""
+    3 + 2 samples: finite disp, gradients through every layer).  Every sample's density is positive here, the last one's too, and
+    the last distance is 1e10: acc = 1 on every ray and its gradient is rounding noise -- acc, acc0 and white_bkgd's 1 - acc are
+    gradients on _signed_nets only."""
     if name in NETS:
         return _trunk_nets(oracle, name)
     D, W, skips, multires = EXTRA[name]
@@ -41,6 +52,27 @@ def _nets(oracle, name):
         sd = oracle.synth_weights_shape(s, D, W, multires, L_VIEWS, list(skips), True)
         sd["alpha_linear.weight"] = (sd["alpha_linear.weight"] * np.float32(W / (400.0 * 256.0))).astype(np.float32)
         sd["alpha_linear.bias"] = np.full_like(sd["alpha_linear.bias"], 0.5)
+        nets.append(sd)
+    return tuple(nets)
+
+
+@functools.lru_cache(maxsize=None)
+def _signed_nets(oracle, name):
+    """_nets(name) with the density rows rescaled and re-biased by SIGNED[name]: densities of either sign, of order 1, so that a ray
+    whose last sample is empty behind a translucent one has 0 < acc < 1 (some rays are empty: disp = 0 / 0 there, in the reference
+    as well).  The path cot_acc -> d sigma -> network backward carries a gradient on these, not a cancellation."""
+    nets = []
+    for sd, scale, bias, row in zip(_nets(oracle, name), SIGNED[name][0::2], SIGNED[name][1::2], SIGNED_ROWS.get(name, (None, None))):
+        sd = {k: v.copy() for k, v in sd.items()}
+        if row is not None:
+            w = sd["alpha_linear.weight"]
+            w[:] = np.random.RandomState(row).standard_normal(w.shape) / np.sqrt(w.shape[1])
+        if "alpha_linear.weight" in sd:
+            sd["alpha_linear.weight"] *= np.float32(scale)
+            sd["alpha_linear.bias"][:] = np.float32(bias)
+        else:
+            sd["output_linear.weight"][3] *= np.float32(scale)
+            sd["output_linear.bias"][3] = np.float32(bias)
         nets.append(sd)
     return tuple(nets)
 
@@ -111,6 +143,32 @@ def test_onchip_backward_trunk_equals_the_per_layer_chain_bit_for_bit(name, orac
                 assert np.isfinite(g).all() and np.abs(g).max() > 0, (what, i, n)      # (so that NaN == NaN proves nothing by accident)
     st = [m.range_status() for m in ms]
     assert st[0] == st[1] == st[2] and st[2]["passes"] > 0 and st[2]["passes_rerun"] == 0, st
+    for m in ms:
+        m.close()
+    if name != "3x40":
+        return
+    # once more on the signed-density variant: acc = 1 on every ray above, so the acc cotangents compared there differentiate a
+    # constant; here acc and acc0 vary from ray to ray
+    ms = _trio(*_signed_nets(oracle, name), 3, 2)
+    ro, rd = ro_all[:171], rd_all[:171]
+    rs = [m.render_rays(ro, rd, near, far, debug=True) for m in ms]
+    for k in TAPS:
+        assert _same(rs[0][k], rs[2][k]) and _same(rs[1][k], rs[2][k]), ("signed", k)
+    for k in ("acc_map", "acc0"):
+        acc = cpu(rs[2][k])
+        assert ((acc > 0.05) & (acc < 0.95)).sum() >= 171 // 4, ("signed", k)
+    zf = cpu(rs[0]["z_fine"])
+    cots = _cots(171, 33)
+    for what, cot in (("acc and acc0", {k: cots[k] for k in ("acc_map", "acc0")}), ("all six", cots)):
+        gs = [m.render_rays_vjp(ro, rd, near, far, cotangents=cot, z_fine=zf) for m in ms]
+        for i in range(2):
+            assert _bits_equal(gs[0][i], gs[2][i]) and _bits_equal(gs[1][i], gs[2][i]), ("signed", what, i)
+            g = cpu(gs[2][i])
+            assert np.isfinite(g).any() and np.nanmax(np.abs(g)) > 0, ("signed", what, i)
+            if what == "acc and acc0":
+                assert np.isfinite(g).all() and (np.abs(g).max(1) > 0).sum() >= 171 // 4, ("signed", what, i)
+    st = [m.range_status() for m in ms]
+    assert st[0] == st[1] == st[2] and st[2]["passes_rerun"] == 0, st
     for m in ms:
         m.close()
 
