@@ -674,6 +674,19 @@ struct Mat {                 // one packed matrix [Np][K1p + K2p] and its (nulla
   float cscale = 1.0f;       // 2^-sw, which undoes the f16x2 image's weight scale in the epilogue
 };
 
+// What a handle runs on chip for one network (onchip_plan): per decision the kernel form that does it -- a row of kTrunkForms -- or
+// why there is none.  trunk: the pts_linears in one launch; heads: the heads behind them in that launch (its form replaces the
+// trunk's); bwd: the layer loop of the input-gradient chain in one launch.
+struct TrunkForm;
+struct Onchip {
+  const TrunkForm* form = nullptr;
+  const char* why = "";
+};
+struct OnchipPlan {
+  Onchip trunk, heads, bwd;
+  const TrunkForm* forward() const { return heads.form ? heads.form : trunk.form; }      // the form of the forward's launch
+};
+
 struct Net {
   NsrwNet d{};
   bool loaded = false;
@@ -685,13 +698,9 @@ struct Net {
   char* dImg[kArithSlots] = {};       // device, per arithmetic the handle has an image of: the weight images of every matrix
   size_t img_bytes[kArithSlots] = {};
   std::vector<Mat> fwd;               // pts_linears
-  int trunk_nj = 0;                   // trunk_plan: 0 = the trunk runs layer by layer, else the NJ of kw_trunk_h2 that runs it on chip
-  int trunk_tile = 0;                 // ... and its rows per block: 128, or 64 in the wide form (NSRW_FLAG_TRUNK_WIDE)
-  TrunkLayer* dTrunk = nullptr;       // device: the per-layer table of kw_trunk_h2 (trunk_nj != 0)
-  int trunk_rows = 0;                 // its rows: D, or with heads_onchip the heads behind them (heads_plan)
-  bool heads_onchip = false;          // heads_plan: the trunk launch is the heads form, which leaves nothing but k.RAW
-  int trunk_bwd_nj = 0;               // trunk_bwd_plan: 0 = net_backward_chain's layer loop, else the NJ of kw_trunk_bwd_h2 that replaces it
-  int trunk_bwd_at = 0, trunk_bwd_rows = 0;       // ... and its rows of dTrunk, behind the forward's
+  OnchipPlan onchip;                  // onchip_plan: which kernels of nsr_wide_trunk.inc run this network's passes, if any
+  TrunkLayer* dTrunk = nullptr;       // device: trunk_table -- the rows of the forward launch, the backward launch's behind them
+  int trunk_rows = 0, trunk_bwd_rows = 0;
   Mat fa, al, hv, rgb, out;           // feature_linear, alpha_linear, views_linears.0, rgb_linear / output_linear
   std::vector<Mat> bwd_h, bwd_e;      // per pts layer: G W_i[:, hidden part] (i >= 1), G W_i[:, encoding part] (layer 0, skip layers)
   Mat b_rgb, b_feat, b_ed, b_head;
@@ -752,7 +761,7 @@ struct GemmCfg {
   int cus = 256;                        // compute units of the handle's device
   Arith arith = kF32;                   // NsrwConfig::flags: NSRW_FLAG_MLP_F16X2 -> kH2, NSRW_FLAG_MLP_BF16X3 -> kB3, neither -> kF32
   int tile_wm = 4;                      // 256-column tiles with 256 rows / 512 threads (4) or 128 rows / 256 threads (2: NSRW_B3_WM = 2)
-  int flags = 0;                        // NsrwConfig::flags (trunk_plan reads NSRW_FLAG_TRUNK_ONCHIP and _WIDE, heads_plan NSRW_FLAG_HEADS_ONCHIP, trunk_bwd_plan NSRW_FLAG_TRUNK_BWD)
+  int flags = 0;                        // NsrwConfig::flags (onchip_plan reads the arithmetic and the four on-chip flags)
   unsigned* d_range = nullptr;          // device: [0] flag of the f16x2 pass in flight, [1] passes run, [2] passes re-run on bf16x3
 };
 
@@ -1009,66 +1018,175 @@ int gemm(const GemmCfg& cfg, Run run, hipStream_t st, const Net& net, const Mat&
   return 0;
 }
 
-// Whether kw_trunk_h2 runs the pts_linears of `d` on a handle created with `flags` -- pure host arithmetic, no HIP call
-// (nsrw_trunk_plan exposes it).  On chip: an f16x2 handle with NSRW_FLAG_TRUNK_ONCHIP, at least two layers, and a packed width of at
-// most 128, so that the whole N extent is one tile (NJ = 1: <= 64 columns, NJ = 2: 128).  Tiles are 128 rows.  With
-// NSRW_FLAG_TRUNK_WIDE on top, a packed width of 160 .. 256 is on chip too: the wide form, tiles of 64 rows by 256 columns.
-NsrwTrunkPlan trunk_plan(const NsrwNet& d, int flags) {
-  NsrwTrunkPlan p{};
-  auto no = [&](const char* why) { p.onchip = 0; snprintf(p.reason, sizeof p.reason, "%s", why); return p; };
-  const std::string why = check_net(d);
-  if (!why.empty()) return no("invalid network");
-  if (!(flags & NSRW_FLAG_TRUNK_ONCHIP)) return no("NSRW_FLAG_TRUNK_ONCHIP not set");
-  if (!(flags & NSRW_FLAG_MLP_F16X2)) return no("not an f16x2 handle");
-  if (d.D < 2) return no("one layer: nothing to keep on chip");
-  const bool wide = (flags & NSRW_FLAG_TRUNK_WIDE) && pad32(d.W) > 128;
-  if (wide ? pad32(d.W) > 256 : pad32(d.W) > 128) return no(wide ? "padded width above 256" : "padded width above 128");
-  if (pad32(3 + 6 * d.multires) > kTrunkCiMax) return no("encoding wider than 96");
-  p.onchip = 1;
-  p.nj = pad32(d.W) <= 64 ? 1 : 2;
-  p.tile_rows = wide ? trunk_rows<2>() : trunk_rows<4>();
-  p.lds_bytes = wide ? trunk_lds_bytes<2, 2>() : p.nj == 1 ? trunk_lds_bytes<1>() : trunk_lds_bytes<2>();
+// The on-chip forms: one row per kernel of nsr_wide_trunk.inc that is instantiated, with the shape it has.  onchip_plan chooses among
+// these rows and the launches run the row they are handed: the kernel, its tile rows and its LDS bytes are stated here and nowhere else.
+typedef void (*TrunkKernel)(TrunkArgs);
+typedef void (*TrunkBwdKernel)(TrunkBwdArgs);
+struct TrunkForm {
+  int nj, tile_rows;                    // 32-column blocks of the output one wave accumulates; points of a block
+  bool heads;                           // forward rows: the heads run behind the trunk in the launch
+  TrunkKernel fwd;                      // kw_trunk_h2, or
+  TrunkBwdKernel bwd;                   // kw_trunk_bwd_h2: exactly one of the two
+  int lds_bytes;                        // the kernel's own (static) LDS
+};
+template <int NJ, bool HEADS, int WR = 4>
+TrunkForm trunk_fwd_form() { return {NJ, trunk_rows<WR>(), HEADS, kw_trunk_h2<NJ, HEADS, WR>, nullptr, trunk_lds_bytes<NJ, WR>()}; }
+template <int NJ>
+TrunkForm trunk_bwd_form_row() { return {NJ, trunk_rows<4>(), false, nullptr, kw_trunk_bwd_h2<NJ>, trunk_bwd_lds_bytes<NJ>()}; }
+// (in this order: the order of instantiation is the order of the kernels in the code object)
+const TrunkForm kTrunkForms[] = {trunk_fwd_form<1, true>(), trunk_fwd_form<2, true>(), trunk_fwd_form<1, false>(), trunk_fwd_form<2, false>(),
+                                 trunk_fwd_form<2, false, 2>(), trunk_bwd_form_row<1>(), trunk_bwd_form_row<2>()};
+constexpr int kTrunkThreads = 512;
+
+const TrunkForm* find_trunk_form(bool bwd, int nj, int tile_rows, bool heads) {
+  for (const TrunkForm& f : kTrunkForms)
+    if ((f.bwd != nullptr) == bwd && f.nj == nj && f.tile_rows == tile_rows && f.heads == heads) return &f;
+  return nullptr;
+}
+
+// What a handle created with `flags` runs on chip for the network `d` -- pure host arithmetic, no HIP call (nsrw_trunk_plan,
+// nsrw_heads_plan and nsrw_trunk_bwd_plan expose its three decisions; nsrw_upload_network keeps it).  DESIGN.md 8 has the table.
+//   trunk: an f16x2 handle with NSRW_FLAG_TRUNK_ONCHIP, at least two layers, and a packed width of at most 128, so that the whole N
+//     extent is one tile of 128 rows (NJ = 1: <= 64 columns, NJ = 2: 128); with NSRW_FLAG_TRUNK_WIDE on top a packed width of
+//     160 .. 256 too: the wide form, tiles of 64 rows by 256 columns.
+//   heads: NSRW_FLAG_HEADS_ONCHIP, a trunk on chip in its 128-row form, and, with view directions, a direction encoding that fits
+//     the encoding image it takes over.  The kernel's LDS is the trunk's.
+//   bwd: NSRW_FLAG_TRUNK_BWD and a trunk on chip in its 128-row form (hence f16x2 and at least two layers: there is a hidden row).
+//     NJ covers the wider of the two outputs: the hidden width and the encoding.
+OnchipPlan onchip_plan(const NsrwNet& d, int flags) {
+  OnchipPlan p;
+  auto decide = [](Onchip& c, const char* why, bool bwd, int nj, int tile_rows, bool heads) {
+    if (!why && !(c.form = find_trunk_form(bwd, nj, tile_rows, heads))) why = "internal error: form not compiled";
+    c.why = why ? why : "";
+  };
+  if (!check_net(d).empty()) {
+    p.trunk.why = p.heads.why = p.bwd.why = "invalid network";
+    return p;
+  }
+  const int Wp = pad32(d.W), Ci = pad32(3 + 6 * d.multires), narrow = trunk_rows<4>();
+  const bool wide = (flags & NSRW_FLAG_TRUNK_WIDE) && Wp > 128;
+  const int nj = Wp <= 64 ? 1 : 2;
+  decide(p.trunk,
+         !(flags & NSRW_FLAG_TRUNK_ONCHIP) ? "NSRW_FLAG_TRUNK_ONCHIP not set"
+         : !(flags & NSRW_FLAG_MLP_F16X2)  ? "not an f16x2 handle"
+         : d.D < 2                         ? "one layer: nothing to keep on chip"
+         : wide && Wp > 256                ? "padded width above 256"
+         : !wide && Wp > 128               ? "padded width above 128"
+         : Ci > kTrunkCiMax                ? "encoding wider than 96"
+                                           : nullptr,
+         false, nj, wide ? trunk_rows<2>() : narrow, false);
+  const bool narrow_trunk = p.trunk.form && p.trunk.form->tile_rows == narrow;
+  decide(p.heads,
+         !(flags & NSRW_FLAG_HEADS_ONCHIP) ? "NSRW_FLAG_HEADS_ONCHIP not set"
+         : !p.trunk.form                   ? "the trunk is not on chip"
+         : !narrow_trunk                   ? "padded width above 128: the wide trunk has no heads form"
+         : d.use_viewdirs && pad32(3 + 6 * d.multires_views) > kTrunkCiMax ? "direction encoding wider than 96"
+                                           : nullptr,
+         false, nj, narrow, true);
+  decide(p.bwd,
+         !(flags & NSRW_FLAG_TRUNK_BWD) ? "NSRW_FLAG_TRUNK_BWD not set"
+         : !p.trunk.form                ? "the trunk is not on chip"
+         : !narrow_trunk                ? "padded width above 128: the wide trunk has no backward form"
+                                        : nullptr,
+         true, std::max(nj, Ci <= 64 ? 1 : 2), narrow, false);
   return p;
 }
 
-// Whether the heads run behind the on-chip trunk in its launch (kw_trunk_h2<NJ, true>) -- pure host arithmetic, no HIP call
-// (nsrw_heads_plan exposes it).  On chip: NSRW_FLAG_HEADS_ONCHIP, a trunk that trunk_plan puts on chip, and, with view directions,
-// a direction encoding that fits the encoding image it takes over.  The kernel's LDS is the trunk's.
-NsrwHeadsPlan heads_plan(const NsrwNet& d, int flags) {
+// the opt-in flags of the on-chip forms and the flag each needs beside it: nsrw_create refuses the first row that is not met
+struct FlagNeeds {
+  int flag, needs;
+  const char* refusal;
+};
+constexpr FlagNeeds kFlagNeeds[] = {
+    {NSRW_FLAG_TRUNK_ONCHIP, NSRW_FLAG_MLP_F16X2,
+     "nsrw_create: NSRW_FLAG_TRUNK_ONCHIP needs NSRW_FLAG_MLP_F16X2 (the on-chip trunk exists for the f16x2 arithmetic only)"},
+    {NSRW_FLAG_TRUNK_WIDE, NSRW_FLAG_TRUNK_ONCHIP,
+     "nsrw_create: NSRW_FLAG_TRUNK_WIDE needs NSRW_FLAG_TRUNK_ONCHIP (it extends the on-chip trunk to padded widths up to 256)"},
+    {NSRW_FLAG_HEADS_ONCHIP, NSRW_FLAG_TRUNK_ONCHIP,
+     "nsrw_create: NSRW_FLAG_HEADS_ONCHIP needs NSRW_FLAG_TRUNK_ONCHIP (the on-chip heads run behind the on-chip trunk, in its launch)"},
+    {NSRW_FLAG_TRUNK_BWD, NSRW_FLAG_TRUNK_ONCHIP,
+     "nsrw_create: NSRW_FLAG_TRUNK_BWD needs NSRW_FLAG_TRUNK_ONCHIP (the on-chip backward trunk serves the networks the on-chip trunk serves)"},
+};
+
+// the decisions as the diagnostic entries report them (no form: every figure 0, and the reason)
+NsrwTrunkPlan as_trunk_plan(const Onchip& c) {
+  NsrwTrunkPlan p{};
+  if (c.form) { p.onchip = 1; p.nj = c.form->nj; p.tile_rows = c.form->tile_rows; p.lds_bytes = c.form->lds_bytes; }
+  else snprintf(p.reason, sizeof p.reason, "%s", c.why);
+  return p;
+}
+NsrwHeadsPlan as_heads_plan(const Onchip& c) {
   NsrwHeadsPlan p{};
-  auto no = [&](const char* why) { p.onchip = 0; snprintf(p.reason, sizeof p.reason, "%s", why); return p; };
-  if (!check_net(d).empty()) return no("invalid network");
-  if (!(flags & NSRW_FLAG_HEADS_ONCHIP)) return no("NSRW_FLAG_HEADS_ONCHIP not set");
-  const NsrwTrunkPlan t = trunk_plan(d, flags);
-  if (!t.onchip) return no("the trunk is not on chip");
-  if (t.tile_rows != trunk_rows<4>()) return no("padded width above 128: the wide trunk has no heads form");
-  if (d.use_viewdirs && pad32(3 + 6 * d.multires_views) > kTrunkCiMax) return no("direction encoding wider than 96");
-  p.onchip = 1;
-  p.lds_bytes = t.lds_bytes;
+  if (c.form) { p.onchip = 1; p.lds_bytes = c.form->lds_bytes; }
+  else snprintf(p.reason, sizeof p.reason, "%s", c.why);
   return p;
 }
 
-// Whether kw_trunk_bwd_h2 runs the input-gradient chain of `d` behind the backward's head launches -- pure host arithmetic, no HIP
-// call (nsrw_trunk_bwd_plan exposes it).  On chip: NSRW_FLAG_TRUNK_BWD and a trunk that trunk_plan puts on chip in its 128-row form
-// (hence f16x2 and at least two layers).  nj covers the wider of the two outputs: the hidden width and the encoding.
-NsrwTrunkPlan trunk_bwd_plan(const NsrwNet& d, int flags) {
-  NsrwTrunkPlan p{};
-  auto no = [&](const char* why) { p.onchip = 0; snprintf(p.reason, sizeof p.reason, "%s", why); return p; };
-  if (!check_net(d).empty()) return no("invalid network");
-  if (!(flags & NSRW_FLAG_TRUNK_BWD)) return no("NSRW_FLAG_TRUNK_BWD not set");
-  const NsrwTrunkPlan t = trunk_plan(d, flags);
-  if (!t.onchip) return no("the trunk is not on chip");
-  if (t.tile_rows != trunk_rows<4>()) return no("padded width above 128: the wide trunk has no backward form");
-  p.onchip = 1;                     // (trunk_plan has asked for two layers: there is a hidden row)
-  p.nj = std::max(pad32(d.W) <= 64 ? 1 : 2, pad32(3 + 6 * d.multires) <= 64 ? 1 : 2);
-  p.tile_rows = trunk_rows<4>();
-  p.lds_bytes = p.nj == 1 ? trunk_bwd_lds_bytes<1>() : trunk_bwd_lds_bytes<2>();
-  return p;
+// Whether the one launch of form `f` (nullable) runs a pass over P points: the f16x2 pass proper -- the conditional bf16x3 re-run
+// stays layer by layer -- over a number of blocks that the grid arithmetic holds.  Its grid: a block per tile, at most one per CU.
+bool onchip_pass(Run run, const TrunkForm* f, long long P) {
+  return f && run.arith == kH2 && !run.run_if && P > 0 && P / f->tile_rows < 0x7fffffffll;
+}
+dim3 trunk_grid(const GemmCfg& cfg, const TrunkForm& f, long long P) {
+  const long long mblocks = (P + f.tile_rows - 1) / f.tile_rows;
+  return dim3((unsigned)std::min<long long>(mblocks, cfg.cus));
+}
+
+// The per-row table of the on-chip launches of `n` (Net::dTrunk; launch calls only enqueue): the rows of the forward launch -- the D
+// layers, with the heads behind them where n.onchip says so -- then the backward launch's.  Empty when the trunk is not on chip.
+std::vector<TrunkLayer> trunk_table(const Net& n, int* fwd_rows, int* bwd_rows) {
+  std::vector<TrunkLayer> trunk;
+  *fwd_rows = *bwd_rows = 0;
+  if (!n.onchip.trunk.form) return trunk;
+  const int D = n.d.D, Ci = n.Ci, Wp = n.Wp;
+  const bool heads = n.onchip.heads.form != nullptr;
+  // a row: the matrix, its K as k16 blocks of the encoding image and of the activation image, and its epilogue
+  auto row = [&](const Mat& m, int kbe, int kbh, bool h_first, bool relu, int dest, int ncols = 0, int col0 = 0, int ld = 0) {
+    TrunkLayer t{};
+    t.img_off = (unsigned)m.img[kH2]; t.bias_off = (unsigned)m.b;
+    t.kbe = kbe; t.kbh = kbh;
+    t.cscale = m.cscale;
+    t.form = trunk_form(m.ncb, m.Np / 32, h_first, relu, dest); t.store = trunk_store(ncols, col0, ld);
+    trunk.push_back(t);
+  };
+  for (int i = 0; i < D; ++i)
+    row(n.fwd[i], (i == 0 || n.skip_in[i]) ? Ci / 16 : 0, i == 0 ? 0 : Wp / 16, false, true, (i + 1 < D || heads) ? kTrunkToLds : kTrunkToC);
+  if (heads && n.d.use_viewdirs) {                 // net_forward_chain's four head launches, alpha_linear first: it reads the h
+    row(n.al, 0, Wp / 16, false, false, kTrunkToRaw, 1, 3, n.ldraw);                 // that feature_linear overwrites
+    row(n.fa, 0, Wp / 16, false, false, kTrunkToLds);
+    row(n.hv, n.Cv / 16, Wp / 16, true, true, kTrunkToLds);
+    row(n.rgb, 0, n.W2p / 16, false, false, kTrunkToRaw, 3, 0, n.ldraw);
+  } else if (heads) {
+    row(n.out, 0, Wp / 16, false, false, kTrunkToRaw, n.d.output_ch, 0, 32);
+  }
+  *fwd_rows = (int)trunk.size();
+  if (!n.onchip.bwd.form) return trunk;
+  // the backward trunk's rows, in the order net_backward_chain issues its launches: per layer i = D - 1 .. 0 the encoding product
+  // (layer 0 and the skip layers; every one but the first adds) and, i > 0, the hidden product masked by h_{i-1}
+  auto brow = [&](const Mat& m, int dest, bool accum, int mask_layer) {
+    TrunkLayer t{};
+    t.img_off = (unsigned)m.img[kH2];
+    t.kbh = Wp / 16;
+    t.cscale = m.cscale;
+    t.form = trunk_bwd_form(m.Np / 32, dest, accum); t.store = mask_layer;
+    trunk.push_back(t);
+  };
+  bool first_e = true;
+  for (int i = D - 1; i >= 0; --i) {
+    if (i == 0 || n.skip_in[i]) {                  // (its mask is the one the hidden row behind it reads: fetched, not used)
+      brow(n.bwd_e[i], kTrunkToGep, !first_e, i > 0 ? i - 1 : 0);
+      first_e = false;
+    }
+    if (i > 0) brow(n.bwd_h[i], kTrunkToLds, false, i - 1);
+  }
+  *bwd_rows = (int)trunk.size() - *fwd_rows;
+  return trunk;
 }
 
 // all D pts_linears layers over P points in ONE launch: k.E -> k.H[(D - 1) & 1], where net_forward_chain's layer loop leaves them;
-// or (Net::heads_onchip) the heads too: k.E, k.ED -> k.RAW, where net_forward_chain's head launches leave them
+// or (the heads form) the heads too: k.E, k.ED -> k.RAW, where net_forward_chain's head launches leave them
 void trunk_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P) {
+  const TrunkForm& f = *n.onchip.forward();
   TrunkArgs t{};
   t.E = k.E; t.ldE = n.Ci;
   t.img = n.dImg[kH2]; t.img_bytes = (unsigned)n.img_bytes[kH2];
@@ -1079,12 +1197,7 @@ void trunk_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk&
   t.RAW = k.RAW;
   t.M = P;
   t.range_flag = cfg.d_range;
-  const long long mblocks = (P + n.trunk_tile - 1) / n.trunk_tile;
-  const unsigned grid = (unsigned)std::min<long long>(mblocks, cfg.cus);
-  auto kernel = n.trunk_tile == trunk_rows<2>() ? kw_trunk_h2<2, false, 2>
-                : n.heads_onchip ? (n.trunk_nj == 1 ? kw_trunk_h2<1, true> : kw_trunk_h2<2, true>)
-                                 : (n.trunk_nj == 1 ? kw_trunk_h2<1, false> : kw_trunk_h2<2, false>);
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), 0, st, t);
+  hipLaunchKernelGGL(f.fwd, trunk_grid(cfg, f, P), dim3(kTrunkThreads), 0, st, t);
 }
 
 // RH:99-122 over P points whose encodings are in k.E / k.ED: leaves the rgb logits in k.RAW (ld 32; all output_linear rows
@@ -1094,10 +1207,10 @@ int net_forward_chain(const GemmCfg& cfg, Run run, hipStream_t st, const Net& n,
   const float* h = nullptr;
   // f16x2 pass of an eligible network on an on-chip handle, no activation kept: the one trunk launch (the conditional bf16x3
   // re-run and every pass that keeps its activations for a backward stay layer by layer)
-  const bool onchip = run.arith == kH2 && !run.run_if && !keep && n.trunk_nj != 0 && P > 0 && P / n.trunk_tile < 0x7fffffffll;
+  const bool onchip = !keep && onchip_pass(run, n.onchip.forward(), P);
   if (onchip) {
     trunk_launch(cfg, st, n, k, P);
-    if (n.heads_onchip) {             // the heads ran behind the trunk: k.H, k.FA and k.HV are not written
+    if (n.onchip.heads.form) {        // the heads ran behind the trunk: k.H, k.FA and k.HV are not written
       *sigma = k.RAW + 3; *ld_sigma = n.ldraw;
       return 0;
     }
@@ -1149,6 +1262,7 @@ int net_forward(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k
 // net_backward_chain's layer loop over P points in ONE launch: k.G0 (what b_head left there) and the kept k.H[0 .. D - 2] -> k.GEP
 int trunk_bwd_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P) {
   const int D = n.d.D;
+  const TrunkForm& f = *n.onchip.bwd.form;
   // the kernel addresses the kept activations as one array of D - 1 matrices: carve_chunk lays them out at one stride
   const long long ldH = k.H[1] - k.H[0];
   for (int i = 0; i + 1 < D; ++i)
@@ -1156,14 +1270,12 @@ int trunk_bwd_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chu
   TrunkBwdArgs t{};
   t.G = k.G0; t.Wp = n.Wp;
   t.img = n.dImg[kH2]; t.img_bytes = (unsigned)n.img_bytes[kH2];
-  t.rows = n.dTrunk + n.trunk_bwd_at; t.R = n.trunk_bwd_rows;
+  t.rows = n.dTrunk + n.trunk_rows; t.R = n.trunk_bwd_rows;
   t.H0 = k.H[0]; t.ldH = ldH; t.n_masks = D - 1;
   t.GEP = k.GEP; t.Ci = n.Ci;
   t.M = P;
   t.range_flag = cfg.d_range;
-  const long long mblocks = (P + trunk_rows<4>() - 1) / trunk_rows<4>();
-  const unsigned grid = (unsigned)std::min<long long>(mblocks, cfg.cus);
-  hipLaunchKernelGGL(n.trunk_bwd_nj == 1 ? kw_trunk_bwd_h2<1> : kw_trunk_bwd_h2<2>, dim3(grid), dim3(512), 0, st, t);
+  hipLaunchKernelGGL(f.bwd, trunk_grid(cfg, f, P), dim3(kTrunkThreads), 0, st, t);
   return 0;
 }
 
@@ -1180,10 +1292,8 @@ int net_backward_chain(const GemmCfg& cfg, Run run, hipStream_t st, const Net& n
   } else {
     if (gemm(cfg, run, st, n, n.b_head, k.DRAW, 32, nullptr, 0, g, n.Wp, n.Wp, P, 0, k.H[D - 1], n.Wp)) return 1;
   }
-  // f16x2 pass of a network whose backward trunk is on chip (trunk_bwd_plan): the one launch instead of the layer loop (the conditional
-  // bf16x3 re-run stays layer by layer)
-  if (run.arith == kH2 && !run.run_if && n.trunk_bwd_nj != 0 && P > 0 && P / trunk_rows<4>() < 0x7fffffffll)
-    return trunk_bwd_launch(cfg, st, n, k, P);
+  // f16x2 pass of a network whose backward trunk is on chip: the one launch instead of the layer loop
+  if (onchip_pass(run, n.onchip.bwd.form, P)) return trunk_bwd_launch(cfg, st, n, k, P);
   bool first_e = true;
   for (int i = D - 1; i >= 0; --i) {          // g = dL/d pre-activation of layer i
     if (i == 0 || n.skip_in[i]) {
@@ -1408,14 +1518,8 @@ int nsrw_create(const NsrwConfig* cfg, nsrw_handle* out) {
   int count = 0;
   NSRW_HIP(hipGetDeviceCount(&count));
   if (cfg->device < 0 || cfg->device >= count) return fail("nsrw_create: no such device");
-  if ((cfg->flags & NSRW_FLAG_TRUNK_ONCHIP) && !(cfg->flags & NSRW_FLAG_MLP_F16X2))
-    return fail("nsrw_create: NSRW_FLAG_TRUNK_ONCHIP needs NSRW_FLAG_MLP_F16X2 (the on-chip trunk exists for the f16x2 arithmetic only)");
-  if ((cfg->flags & NSRW_FLAG_TRUNK_WIDE) && !(cfg->flags & NSRW_FLAG_TRUNK_ONCHIP))
-    return fail("nsrw_create: NSRW_FLAG_TRUNK_WIDE needs NSRW_FLAG_TRUNK_ONCHIP (it extends the on-chip trunk to padded widths up to 256)");
-  if ((cfg->flags & NSRW_FLAG_HEADS_ONCHIP) && !(cfg->flags & NSRW_FLAG_TRUNK_ONCHIP))
-    return fail("nsrw_create: NSRW_FLAG_HEADS_ONCHIP needs NSRW_FLAG_TRUNK_ONCHIP (the on-chip heads run behind the on-chip trunk, in its launch)");
-  if ((cfg->flags & NSRW_FLAG_TRUNK_BWD) && !(cfg->flags & NSRW_FLAG_TRUNK_ONCHIP))
-    return fail("nsrw_create: NSRW_FLAG_TRUNK_BWD needs NSRW_FLAG_TRUNK_ONCHIP (the on-chip backward trunk serves the networks the on-chip trunk serves)");
+  for (const FlagNeeds& r : kFlagNeeds)
+    if ((cfg->flags & r.flag) && !(cfg->flags & r.needs)) return fail(r.refusal);
   GemmCfg gc;
   {
     hipDeviceProp_t prop;
@@ -1607,59 +1711,8 @@ int nsrw_upload_network(nsrw_handle hh, int net_id, const NsrwNet* desc, const f
     });
     if (image[a].size() >= 0x7fffffffull) return fail(std::string("nsrw_upload_network: network too large for the ") + arith_name(a) + " image");
   }
-  // the on-chip trunk's per-layer table (launch calls only enqueue), with the heads behind the layers where heads_plan says so
-  std::vector<TrunkLayer> trunk;
-  const NsrwTrunkPlan tp = trunk_plan(*desc, h->gemm_cfg.flags);
-  if (tp.onchip) {
-    n.trunk_nj = tp.nj;
-    n.trunk_tile = tp.tile_rows;
-    n.heads_onchip = heads_plan(*desc, h->gemm_cfg.flags).onchip != 0;
-    // a row: the matrix, its K as k16 blocks of the encoding image and of the activation image, and its epilogue
-    auto row = [&](const Mat& m, int kbe, int kbh, bool h_first, bool relu, int dest, int ncols = 0, int col0 = 0, int ld = 0) {
-      TrunkLayer t{};
-      t.img_off = (unsigned)m.img[kH2]; t.bias_off = (unsigned)m.b;
-      t.kbe = kbe; t.kbh = kbh;
-      t.cscale = m.cscale;
-      t.form = trunk_form(m.ncb, m.Np / 32, h_first, relu, dest); t.store = trunk_store(ncols, col0, ld);
-      trunk.push_back(t);
-    };
-    for (int i = 0; i < D; ++i)
-      row(n.fwd[i], (i == 0 || n.skip_in[i]) ? Ci / 16 : 0, i == 0 ? 0 : Wp / 16, false, true,
-          (i + 1 < D || n.heads_onchip) ? kTrunkToLds : kTrunkToC);
-    if (n.heads_onchip && desc->use_viewdirs) {      // net_forward_chain's four head launches, alpha_linear first: it reads the h
-      row(n.al, 0, Wp / 16, false, false, kTrunkToRaw, 1, 3, n.ldraw);                 // that feature_linear overwrites
-      row(n.fa, 0, Wp / 16, false, false, kTrunkToLds);
-      row(n.hv, n.Cv / 16, Wp / 16, true, true, kTrunkToLds);
-      row(n.rgb, 0, n.W2p / 16, false, false, kTrunkToRaw, 3, 0, n.ldraw);
-    } else if (n.heads_onchip) {
-      row(n.out, 0, Wp / 16, false, false, kTrunkToRaw, desc->output_ch, 0, 32);
-    }
-    n.trunk_rows = (int)trunk.size();
-    // the backward trunk's rows behind them, in the order net_backward_chain issues its launches: per layer i = D - 1 .. 0 the
-    // encoding product (layer 0 and the skip layers; every one but the first adds) and, i > 0, the hidden product masked by h_{i-1}
-    const NsrwTrunkPlan bp = trunk_bwd_plan(*desc, h->gemm_cfg.flags);
-    if (bp.onchip) {
-      n.trunk_bwd_nj = bp.nj;
-      n.trunk_bwd_at = (int)trunk.size();
-      auto brow = [&](const Mat& m, int dest, bool accum, int mask_layer) {
-        TrunkLayer t{};
-        t.img_off = (unsigned)m.img[kH2];
-        t.kbh = Wp / 16;
-        t.cscale = m.cscale;
-        t.form = trunk_bwd_form(m.Np / 32, dest, accum); t.store = mask_layer;
-        trunk.push_back(t);
-      };
-      bool first_e = true;
-      for (int i = D - 1; i >= 0; --i) {
-        if (i == 0 || n.skip_in[i]) {                // (its mask is the one the hidden row behind it reads: fetched, not used)
-          brow(n.bwd_e[i], kTrunkToGep, !first_e, i > 0 ? i - 1 : 0);
-          first_e = false;
-        }
-        if (i > 0) brow(n.bwd_h[i], kTrunkToLds, false, i - 1);
-      }
-      n.trunk_bwd_rows = (int)trunk.size() - n.trunk_bwd_at;
-    }
-  }
+  n.onchip = onchip_plan(*desc, h->gemm_cfg.flags);
+  const std::vector<TrunkLayer> trunk = trunk_table(n, &n.trunk_rows, &n.trunk_bwd_rows);
   n.bias_floats = (unsigned)bias.size();
   NSRW_DEVICE(h);
   // (every failure path below frees what this call allocated: ADVICE r05)
@@ -1795,27 +1848,33 @@ int nsrw_gemm_plan(int n_packed_rows, int n_stored_columns, int tile_wm, NsrwGem
   return count;
 }
 
-int nsrw_trunk_plan(const NsrwNet* net, int flags, NsrwTrunkPlan* plan_out) {
-  if (!net || !plan_out) { fail("nsrw_trunk_plan: null argument"); return -1; }
+// the three views of onchip_plan: 0 and the decision, or -1 for an invalid description (nsrw_last_error says why)
+static int plan_entry(const char* name, const NsrwNet* net, const void* plan_out, int flags, OnchipPlan* p) {
+  if (!net || !plan_out) { fail(std::string(name) + ": null argument"); return -1; }
   const std::string why = check_net(*net);
-  if (!why.empty()) { fail("nsrw_trunk_plan: " + why); return -1; }
-  *plan_out = trunk_plan(*net, flags);
+  if (!why.empty()) { fail(std::string(name) + ": " + why); return -1; }
+  *p = onchip_plan(*net, flags);
+  return 0;
+}
+
+int nsrw_trunk_plan(const NsrwNet* net, int flags, NsrwTrunkPlan* plan_out) {
+  OnchipPlan p;
+  if (plan_entry("nsrw_trunk_plan", net, plan_out, flags, &p)) return -1;
+  *plan_out = as_trunk_plan(p.trunk);
   return 0;
 }
 
 int nsrw_heads_plan(const NsrwNet* net, int flags, NsrwHeadsPlan* plan_out) {
-  if (!net || !plan_out) { fail("nsrw_heads_plan: null argument"); return -1; }
-  const std::string why = check_net(*net);
-  if (!why.empty()) { fail("nsrw_heads_plan: " + why); return -1; }
-  *plan_out = heads_plan(*net, flags);
+  OnchipPlan p;
+  if (plan_entry("nsrw_heads_plan", net, plan_out, flags, &p)) return -1;
+  *plan_out = as_heads_plan(p.heads);
   return 0;
 }
 
 int nsrw_trunk_bwd_plan(const NsrwNet* net, int flags, NsrwTrunkPlan* plan_out) {
-  if (!net || !plan_out) { fail("nsrw_trunk_bwd_plan: null argument"); return -1; }
-  const std::string why = check_net(*net);
-  if (!why.empty()) { fail("nsrw_trunk_bwd_plan: " + why); return -1; }
-  *plan_out = trunk_bwd_plan(*net, flags);
+  OnchipPlan p;
+  if (plan_entry("nsrw_trunk_bwd_plan", net, plan_out, flags, &p)) return -1;
+  *plan_out = as_trunk_plan(p.bwd);
   return 0;
 }
 

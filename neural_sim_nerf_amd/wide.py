@@ -5,6 +5,7 @@ list, any N_samples / N_importance (RN:439, RN:474).  Same interface as engine.N
 
 One MFMA GEMM kernel per layer over a chunk of rays (f16x2, bf16x3 or fp32 MFMAs: `mlp`), activations resident in HBM between the layers; torch owns the
 buffers (including the workspace) and the stream, nothing else.  No fallback: without the library or a GPU every call raises."""
+import collections
 import ctypes as C
 import os
 
@@ -144,12 +145,70 @@ def _mlp_flags(mlp):
     return (FLAG_MLP_BF16X3 if mlp == "bf16x3" else 0) | (FLAG_MLP_F16X2 if mlp == "f16x2" else 0)
 
 
+# The opt-in knobs of the on-chip forms, in the order they are resolved -- a knob may need the ones before it.  name: WideModel's
+# argument and attribute; env: where the wish comes from when the argument is not given; values: what it may be, values[0] the
+# default; on: the value that asks for something; flag: what `on` sets in NsrwConfig.flags; needs: what `on` takes of mlp and of the
+# knobs before it; refusal: NotImplementedError's words for an explicit `on` that cannot be honoured (% the resolved options).
+_Knob = collections.namedtuple("_Knob", "name env values on flag needs refusal")
+_ONCHIP = {"mlp": "f16x2", "trunk": "onchip"}
+KNOBS = (
+    _Knob("trunk", "NSR_WIDE_TRUNK", TRUNKS, "onchip", FLAG_TRUNK_ONCHIP, {"mlp": "f16x2"},
+          "trunk=\"onchip\" exists for mlp=\"f16x2\" only (got mlp=%(mlp)r)"),
+    _Knob("heads", "NSR_WIDE_HEADS", HEADS, "onchip", FLAG_HEADS_ONCHIP, _ONCHIP,
+          "heads=\"onchip\" runs behind the on-chip trunk: it needs mlp=\"f16x2\" and trunk=\"onchip\" (got mlp=%(mlp)r, trunk=%(trunk)r)"),
+    _Knob("trunk_width", "NSR_WIDE_TRUNK_WIDTH", TRUNK_WIDTHS, 256, FLAG_TRUNK_WIDE, _ONCHIP,
+          "trunk_width=256 widens the on-chip trunk: it needs mlp=\"f16x2\" and trunk=\"onchip\" (got mlp=%(mlp)r, trunk=%(trunk)r)"),
+    _Knob("trunk_bwd", "NSR_WIDE_TRUNK_BWD", TRUNK_BWDS, "onchip", FLAG_TRUNK_BWD, _ONCHIP,
+          "trunk_bwd=\"onchip\" serves the networks the on-chip trunk serves: it needs mlp=\"f16x2\" and "
+          "trunk=\"onchip\" (got mlp=%(mlp)r, trunk=%(trunk)r)"),
+)
+
+
+def resolve_knobs(mlp, wishes, environ):
+    """{knob: value} for a handle of arithmetic `mlp`: the caller's wish (`wishes`: {knob: argument or None}), else the
+    environment's, else the default.  A value that is not one of the knob's raises ValueError.  The environment's wish is dropped where
+    the handle cannot honour it (the drop-in API also builds bf16x3 / fp32 handles); an explicit one raises NotImplementedError.  Pure:
+    no device, no library."""
+    got = {"mlp": mlp}
+    for k in KNOBS:
+        v = wishes.get(k.name)
+        number = not isinstance(k.on, str)
+        from_env = v is None if number else not v               # (trunk_width=0 is a wish, and a bad one)
+        if from_env:
+            v = environ.get(k.env) or k.values[0]
+            if number and isinstance(v, str) and v.isdigit():
+                v = int(v)
+        if v not in k.values:
+            raise ValueError("%s must be one of %s (got %r)" % (k.name, k.values, v))
+        v = k.values[k.values.index(v)]
+        can = all(got[n] == need for n, need in k.needs.items())
+        if from_env and not can:
+            v = k.values[0]
+        if v == k.on and not can:
+            raise NotImplementedError(k.refusal % got)
+        got[k.name] = v
+    del got["mlp"]
+    return got
+
+
 def _trunk_flags(trunk, trunk_width=128, heads="layers", trunk_bwd="layers"):
+    """the NsrwConfig.flags of the knobs (a trunk_width of 256 says nothing without trunk="onchip")"""
     if trunk_width not in TRUNK_WIDTHS:
         raise ValueError("trunk_width must be one of %s (got %r)" % (TRUNK_WIDTHS, trunk_width))
-    on = trunk == "onchip"
-    return ((FLAG_TRUNK_ONCHIP if on else 0) | (FLAG_TRUNK_WIDE if on and trunk_width == 256 else 0) |
-            (FLAG_HEADS_ONCHIP if heads == "onchip" else 0) | (FLAG_TRUNK_BWD if trunk_bwd == "onchip" else 0))
+    got = dict(trunk=trunk, heads=heads, trunk_width=trunk_width if trunk == "onchip" else 128, trunk_bwd=trunk_bwd)
+    return sum(k.flag for k in KNOBS if got[k.name] == k.on)
+
+
+def _plan(entry, struct, fields, net_or_sd, flags):
+    """one of the library's three plan entries (diagnostic; no device, no handle) on a network -- an NsrwNet or a state dict"""
+    lib = load()
+    net = net_or_sd if isinstance(net_or_sd, NsrwNet) else describe(net_or_sd)[0]
+    plan = struct()
+    if getattr(lib, entry)(C.byref(net), flags, C.byref(plan)) != 0:
+        raise _lib.NsrError(lib.nsrw_last_error().decode("utf-8", "replace"))
+    if plan.onchip:
+        return dict(mode="onchip", **{f: int(getattr(plan, f)) for f in fields})
+    return dict(mode="layers", reason=plan.reason.decode("utf-8", "replace"))
 
 
 def trunk_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", trunk_width=128):
@@ -157,30 +216,15 @@ def trunk_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", trunk_width=128):
     trunk_width=`trunk_width` runs the pts_linears of a network (an NsrwNet or a state dict) -- dict(mode="onchip", nj, tile_rows,
     lds_bytes) for the one-launch trunk of csrc/nsr_wide_trunk.inc (tile_rows = 64: its wide form), or dict(mode="layers",
     reason=...) for a GEMM launch per layer."""
-    lib = load()
-    net = net_or_sd if isinstance(net_or_sd, NsrwNet) else describe(net_or_sd)[0]
-    plan = NsrwTrunkPlan()
-    flags = _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width)
-    if lib.nsrw_trunk_plan(C.byref(net), flags, C.byref(plan)) != 0:
-        raise _lib.NsrError(lib.nsrw_last_error().decode("utf-8", "replace"))
-    if plan.onchip:
-        return dict(mode="onchip", nj=int(plan.nj), tile_rows=int(plan.tile_rows), lds_bytes=int(plan.lds_bytes))
-    return dict(mode="layers", reason=plan.reason.decode("utf-8", "replace"))
+    return _plan("nsrw_trunk_plan", NsrwTrunkPlan, ("nj", "tile_rows", "lds_bytes"), net_or_sd,
+                 _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width))
 
 
 def heads_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", heads="onchip", trunk_width=128):
     """nsrw_heads_plan (diagnostic; no device, no handle): how a handle of arithmetic `mlp` created with trunk=`trunk`,
     heads=`heads`, trunk_width=`trunk_width` runs the heads of a network (an NsrwNet or a state dict) behind its pts_linears -- dict(mode="onchip",
     lds_bytes) for the heads form of the one-launch trunk, or dict(mode="layers", reason=...) for a GEMM launch per head."""
-    lib = load()
-    net = net_or_sd if isinstance(net_or_sd, NsrwNet) else describe(net_or_sd)[0]
-    plan = NsrwHeadsPlan()
-    flags = _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width, heads)
-    if lib.nsrw_heads_plan(C.byref(net), flags, C.byref(plan)) != 0:
-        raise _lib.NsrError(lib.nsrw_last_error().decode("utf-8", "replace"))
-    if plan.onchip:
-        return dict(mode="onchip", lds_bytes=int(plan.lds_bytes))
-    return dict(mode="layers", reason=plan.reason.decode("utf-8", "replace"))
+    return _plan("nsrw_heads_plan", NsrwHeadsPlan, ("lds_bytes",), net_or_sd, _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width, heads))
 
 
 def trunk_bwd_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", trunk_bwd="onchip", trunk_width=128):
@@ -188,15 +232,8 @@ def trunk_bwd_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", trunk_bwd="onchip
     trunk_bwd=`trunk_bwd`, trunk_width=`trunk_width` runs the input-gradient chain of a network (an NsrwNet or a state dict) in its
     gradient calls -- dict(mode="onchip", nj, tile_rows, lds_bytes) for the one-launch backward trunk of csrc/nsr_wide_trunk.inc, or
     dict(mode="layers", reason=...) for a GEMM launch per product."""
-    lib = load()
-    net = net_or_sd if isinstance(net_or_sd, NsrwNet) else describe(net_or_sd)[0]
-    plan = NsrwTrunkPlan()
-    flags = _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width, trunk_bwd=trunk_bwd)
-    if lib.nsrw_trunk_bwd_plan(C.byref(net), flags, C.byref(plan)) != 0:
-        raise _lib.NsrError(lib.nsrw_last_error().decode("utf-8", "replace"))
-    if plan.onchip:
-        return dict(mode="onchip", nj=int(plan.nj), tile_rows=int(plan.tile_rows), lds_bytes=int(plan.lds_bytes))
-    return dict(mode="layers", reason=plan.reason.decode("utf-8", "replace"))
+    return _plan("nsrw_trunk_bwd_plan", NsrwTrunkPlan, ("nj", "tile_rows", "lds_bytes"), net_or_sd,
+                 _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width, trunk_bwd=trunk_bwd))
 
 
 def _np(v):
@@ -338,48 +375,8 @@ class WideModel:
         mlp = mlp or os.environ.get("NSR_WIDE_MLP") or DEFAULT_MLP
         if mlp not in MLPS:
             raise ValueError("mlp must be one of %s (got %r)" % (MLPS, mlp))
-        from_env = not trunk
-        trunk = trunk or os.environ.get("NSR_WIDE_TRUNK") or "layers"
-        if trunk not in TRUNKS:
-            raise ValueError("trunk must be one of %s (got %r)" % (TRUNKS, trunk))
-        if from_env and mlp != "f16x2":       # the environment's wish applies where it can: the drop-in API also builds bf16x3 / fp32 handles
-            trunk = "layers"
-        if trunk == "onchip" and mlp != "f16x2":
-            raise NotImplementedError("trunk=\"onchip\" exists for mlp=\"f16x2\" only (got mlp=%r)" % (mlp,))
-        self.trunk = trunk
-        heads_from_env = not heads
-        heads = heads or os.environ.get("NSR_WIDE_HEADS") or "layers"
-        if heads not in HEADS:
-            raise ValueError("heads must be one of %s (got %r)" % (HEADS, heads))
-        if heads_from_env and (mlp != "f16x2" or trunk != "onchip"):
-            heads = "layers"
-        if heads == "onchip" and (mlp != "f16x2" or trunk != "onchip"):
-            raise NotImplementedError("heads=\"onchip\" runs behind the on-chip trunk: it needs mlp=\"f16x2\" and trunk=\"onchip\" "
-                                      "(got mlp=%r, trunk=%r)" % (mlp, trunk))
-        self.heads = heads
-        width_from_env = trunk_width is None
-        if width_from_env:
-            env = os.environ.get("NSR_WIDE_TRUNK_WIDTH") or "128"
-            trunk_width = int(env) if env.isdigit() else env
-        if trunk_width not in TRUNK_WIDTHS:
-            raise ValueError("trunk_width must be one of %s (got %r)" % (TRUNK_WIDTHS, trunk_width))
-        trunk_width = int(trunk_width)
-        if width_from_env and (mlp != "f16x2" or trunk != "onchip"):
-            trunk_width = 128
-        if trunk_width == 256 and (mlp != "f16x2" or trunk != "onchip"):
-            raise NotImplementedError("trunk_width=256 widens the on-chip trunk: it needs mlp=\"f16x2\" and trunk=\"onchip\" "
-                                      "(got mlp=%r, trunk=%r)" % (mlp, trunk))
-        self.trunk_width = trunk_width
-        bwd_from_env = not trunk_bwd
-        trunk_bwd = trunk_bwd or os.environ.get("NSR_WIDE_TRUNK_BWD") or "layers"
-        if trunk_bwd not in TRUNK_BWDS:
-            raise ValueError("trunk_bwd must be one of %s (got %r)" % (TRUNK_BWDS, trunk_bwd))
-        if bwd_from_env and (mlp != "f16x2" or trunk != "onchip"):
-            trunk_bwd = "layers"
-        if trunk_bwd == "onchip" and (mlp != "f16x2" or trunk != "onchip"):
-            raise NotImplementedError("trunk_bwd=\"onchip\" serves the networks the on-chip trunk serves: it needs mlp=\"f16x2\" and "
-                                      "trunk=\"onchip\" (got mlp=%r, trunk=%r)" % (mlp, trunk))
-        self.trunk_bwd = trunk_bwd
+        knobs = resolve_knobs(mlp, dict(trunk=trunk, heads=heads, trunk_width=trunk_width, trunk_bwd=trunk_bwd), os.environ)
+        self.trunk, self.heads, self.trunk_width, self.trunk_bwd = (knobs[k.name] for k in KNOBS)
         self.mlp = "layered-" + mlp
         if not torch.cuda.is_available():
             raise _lib.NsrError("no HIP device visible: the render path has no CPU fallback")
@@ -402,7 +399,7 @@ class WideModel:
         self._ws_need = {}                                # (rays, grad) -> bytes one chunk of that many rays needs
         cfg = NsrwConfig(self.device.index, n_samples, n_importance,
                          (FLAG_WHITE_BKGD if white_bkgd else 0) | (FLAG_LINDISP if lindisp else 0) |
-                         _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width, heads, trunk_bwd))
+                         _mlp_flags(mlp) | _trunk_flags(self.trunk, self.trunk_width, self.heads, self.trunk_bwd))
         h = C.c_void_p()
         check(self.lib.nsrw_create(C.byref(cfg), C.byref(h)))
         self.h = h

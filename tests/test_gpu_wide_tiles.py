@@ -67,7 +67,7 @@ def _nets(oracle, W):
     to an eighth of its nn.Linear size and the density bias set to +0.5: densities of 0.5 +- 0.25 on the rays used here, so every
     ray is translucent in both passes -- weights spread over its samples, finite disp and disp0, gradients through every layer.
     The last sample is dense too and its distance 1e10, so acc = 1 on every ray and the gradient of acc (and of white_bkgd's
-    1 - acc) is rounding noise here: test_gpu_wide_trunk_bwd._signed_nets is the variant on which it is a gradient."""
+    1 - acc) is rounding noise here: wide_onchip_cases.signed_nets is the variant on which it is a gradient."""
     i = WIDTHS.index(W)
     nets = []
     for s in (300, 400):

@@ -5,72 +5,34 @@ products in a fixed order, one epilogue expression, the next layer's operand pie
 the bits of a trunk="layers" handle everywhere: every tap of the forward, the network outputs on ragged point counts, the gradients
 (whose kept passes run layer by layer on both), the range safety net's counters and re-runs, hostile rays, any company of rays,
 under capture, and in the bounds-checked build.  No tolerance anywhere but the one check against the oracle."""
-import functools
 import os
-import sys
 
 import numpy as np
 import pytest
 
 from conftest import assert_close
-from test_gpu_wide_tiles import OUTS, TAPS, _cots, _rays, _same, cpu
+from test_gpu_wide_tiles import _cots, _rays, cpu
+from wide_onchip_cases import NARROW
+from wide_onchip_cases import WIDE_NETS as NETS
+from wide_onchip_cases import (bounds_checked_build, bounds_clean_and_equal, grads_equal, hostile_case, models, replay_equals_eager,
+                               small_chunks, taps_equal, trunk_range_nets)
+from wide_onchip_cases import hostile as _hostile
+from wide_onchip_cases import scaled as _scaled
+from wide_onchip_cases import wide_nets as _nets
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-L_PTS, L_VIEWS = 4, 2
 POINTS = (1, 63, 64, 65, 127, 128, 129, 257)        # around one and two blocks of either form, and past four
-# name -> (D, W, skips, use_viewdirs).  Padded widths 160 (five column blocks computed, six in the weight image: the last quarter of
-# the workgroup idles), 192 (six and six), 224 (seven of eight) and 256; the skip after layer 0 or 1, two skips, none; a network
-# without view directions (output_linear behind the trunk)
-NETS = {"3x136": (3, 136, [1], True), "3x192": (3, 192, [0], True), "3x200": (3, 200, [1], True), "3x256": (3, 256, [1], True),
-        "5x256": (5, 256, [0, 2], True), "2x256": (2, 256, [], True), "3x160-noviews": (3, 160, [], False)}
-NARROW = (3, 40, [1], True)                          # the coarse network of the mixed handle
-
-
-def _scaled(oracle, seed, D, W, skips, views):
-    """a synthetic network with the density scaling of test_gpu_wide_trunk._nets: the density row at an eighth of its nn.Linear size
-    and its bias +0.5, so that every ray is translucent at 3 + 2 samples"""
-    sd = oracle.synth_weights_shape(seed, D, W, L_PTS, L_VIEWS, list(skips), views)
-    f = np.float32(W / (400.0 * 256.0))
-    if views:
-        sd["alpha_linear.weight"] = (sd["alpha_linear.weight"] * f).astype(np.float32)
-        sd["alpha_linear.bias"] = np.full_like(sd["alpha_linear.bias"], 0.5)
-    else:
-        sd["output_linear.weight"][3] *= f
-        sd["output_linear.bias"][3] = np.float32(0.5)
-    return sd
-
-
-@functools.lru_cache(maxsize=None)
-def _nets(oracle, name):
-    """(coarse, fine) of NETS[name]"""
-    i = sorted(NETS).index(name)
-    return tuple(_scaled(oracle, s + i, *NETS[name]) for s in (500, 600))
 
 
 def _pair(sd_c, sd_f, ns=3, ni=2):
     """(trunk="layers" handle, trunk="onchip" handle that takes padded widths up to 256)"""
-    from neural_sim_nerf_amd.wide import WideModel
-    return (WideModel(sd_c, sd_f, n_samples=ns, n_importance=ni, mlp="f16x2", trunk="layers"),
-            WideModel(sd_c, sd_f, n_samples=ns, n_importance=ni, mlp="f16x2", trunk="onchip", trunk_width=256))
+    return models(sd_c, sd_f, ns, ni, (dict(trunk="layers"), dict(trunk="onchip", trunk_width=256)))
 
 
 def _range_nets(oracle, layer):
-    """3 x 200 coarse network whose pts_linears.<layer> bias sends hidden unit 5 to 7e4 on every point -- layer 1: the value leaves
-    fp16's range INSIDE the trunk (split for layer 2 in LDS); layer 2: on the trunk's last layer, split by the heads behind it"""
-    sd_c, sd_f = _nets(oracle, "3x200")
-    sd_c = {k: v.copy() for k, v in sd_c.items()}
-    sd_c["pts_linears.%d.bias" % layer][5] += 7.0e4
-    return sd_c, sd_f
-
-
-def _hostile(oracle, n=100):
-    ro, rd = (x.copy() for x in _rays(oracle, n, 24))
-    ro[3] = np.nan
-    rd[5] = 0.0
-    rd[7] = np.inf
-    return ro, rd
+    """trunk_range_nets on the 3 x 200 network"""
+    return trunk_range_nets(oracle, layer, _nets(oracle, "3x200"))
 
 
 @pytest.mark.parametrize("name", sorted(NETS))
@@ -92,15 +54,14 @@ def test_wide_onchip_trunk_equals_the_per_layer_path_bit_for_bit(name, oracle):
         ro, rd = ro_all[lo:hi], rd_all[lo:hi]
         n = len(ro)
         rl, rc = (m.render_rays(ro, rd, near, far, debug=True) for m in (ml, mo))
-        for k in TAPS:
-            assert _same(rl[k], rc[k]), (k, n)
+        taps_equal(rl, rc, n)
         assert np.isfinite(cpu(rc["rgb_map"])).all() and np.isfinite(cpu(rc["raw"])).all(), n
         zf = cpu(rl["z_fine"])
         cots = _cots(n, 31 + n)
         gl, gc = (m.render_rays_vjp(ro, rd, near, far, cots["rgb_map"], z_fine=zf) for m in (ml, mo))
         al, ac = (m.render_rays_vjp(ro, rd, near, far, cotangents=cots, z_fine=zf) for m in (ml, mo))
-        for x, y, what in ((gl, gc, "rgb gradient"), (al, ac, "gradient of all six outputs")):
-            assert _same(x[0], y[0]) and _same(x[1], y[1]), (what, n)
+        grads_equal((gl, gc), ("rgb gradient", n))
+        grads_equal((al, ac), ("gradient of all six outputs", n))
         assert np.abs(cpu(gc[0])).max() > 0
     rng = np.random.RandomState(7)
     e_net = 0.0
@@ -140,8 +101,8 @@ def test_a_narrow_and_a_wide_network_on_one_handle(oracle):
     m128 = wide.WideModel(sd_c, sd_f, trunk="onchip", heads="onchip", trunk_width=128, **kw)
     ro, rd = _rays(oracle, 171, 25)
     rl, r256, r128 = (m.render_rays(ro, rd, oracle.YCBV_NEAR, oracle.YCBV_FAR, debug=True) for m in (ml, m256, m128))
-    for k in TAPS:
-        assert _same(rl[k], r256[k]) and _same(rl[k], r128[k]), k
+    taps_equal(rl, r256)
+    taps_equal(rl, r128)
     assert np.isfinite(cpu(r256["rgb_map"])).all()
     assert ml.range_status() == m256.range_status() == m128.range_status() and ml.range_status()["passes_rerun"] == 0
     for m in (ml, m256, m128):
@@ -168,20 +129,16 @@ def test_a_value_that_leaves_the_fp16_range_in_the_wide_trunk_reruns_the_pass(la
     on both handles alike -- equal counters, re-runs counted, the same bits."""
     sd_c, sd_f = _range_nets(oracle, layer)
     ro, rd = _rays(oracle, 256, 26)
-    os.environ["NSR_WIDE_WORKSPACE_GB"] = "0.0001"        # the smallest workspace the library accepts: several chunks
-    try:
+    with small_chunks():
         ml, mo = _pair(sd_c, sd_f)
         rl, rc = (m.render_rays(ro, rd, oracle.YCBV_NEAR, oracle.YCBV_FAR, debug=True) for m in (ml, mo))
         chunks = mo.last_kernel_ms()[1]
         sl, sc = ml.range_status(), mo.range_status()
         assert chunks > 1 and sl == sc and sc["passes"] > 0 and sc["passes_rerun"] > 0, (chunks, sl, sc)
-        for k in TAPS:
-            assert _same(rc[k], rl[k]), k
+        taps_equal(rc, rl)
         assert np.isfinite(cpu(rc["rgb_map"])).all()
         ml.close()
         mo.close()
-    finally:
-        del os.environ["NSR_WIDE_WORKSPACE_GB"]
 
 
 def test_hostile_rays_through_the_wide_trunk(oracle):
@@ -189,17 +146,8 @@ def test_hostile_rays_through_the_wide_trunk(oracle):
     equal the per-layer handle's; the NaN ray stays NaN, the others' colours are finite."""
     sd_c, sd_f = _nets(oracle, "3x256")
     ro, rd = _hostile(oracle)
-    ml, mo = _pair(sd_c, sd_f)
-    rl, rc = (m.render_rays(ro, rd, oracle.YCBV_NEAR, oracle.YCBV_FAR, debug=True) for m in (ml, mo))
-    for k in TAPS:
-        assert _same(rl[k], rc[k]), k
-    ok = np.ones(len(ro), bool)
-    ok[[3, 5, 7]] = False
-    rgb = cpu(rc["rgb_map"])
-    assert np.isfinite(rgb[ok]).all() and np.isnan(rgb[3]).all()
-    assert ml.range_status() == mo.range_status()
-    ml.close()
-    mo.close()
+    rgb = hostile_case(oracle, *_pair(sd_c, sd_f), ro, rd)
+    assert np.isnan(rgb[3]).all()
 
 
 def test_a_rays_result_in_the_wide_trunk_depends_on_nothing_but_the_ray(oracle):
@@ -224,32 +172,11 @@ def test_a_rays_result_in_the_wide_trunk_depends_on_nothing_but_the_ray(oracle):
 
 def test_the_wide_trunk_launch_is_capturable(oracle):
     """One torch.cuda.graph capture of render_rays on the wide on-chip handle; the replay on rewritten input buffers equals the eager call."""
-    import torch
-    from neural_sim_nerf_amd.wide import WideModel
     sd_c, sd_f = _nets(oracle, "3x192")
-    near, far = oracle.YCBV_NEAR, oracle.YCBV_FAR
     ro, rd = _rays(oracle, 171, 27)
-    m = WideModel(sd_c, sd_f, n_samples=3, n_importance=2, mlp="f16x2", trunk="onchip", trunk_width=256)
-    dev = m.device
-    eager = {k: cpu(v) for k, v in m.render_rays(ro, rd, near, far).items()}
-    to, td = (torch.as_tensor(np.ascontiguousarray(x[::-1]), device=dev) for x in (ro, rd))     # other rays while capturing
-    s = torch.cuda.Stream(device=dev)
-    s.wait_stream(torch.cuda.current_stream(dev))
-    with torch.cuda.stream(s):
-        m.render_rays(to, td, near, far)
-        torch.cuda.synchronize(dev)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=s):
-            r = m.render_rays(to, td, near, far)
-    to.copy_(torch.as_tensor(ro, device=dev))
-    td.copy_(torch.as_tensor(rd, device=dev))
-    torch.cuda.synchronize(dev)
-    graph.replay()
-    torch.cuda.synchronize(dev)
-    for k in eager:
-        assert np.array_equal(cpu(r[k]), eager[k], equal_nan=True), k
-    assert np.isfinite(eager["rgb_map"]).all() and m.range_status()["passes_rerun"] == 0
-    m.close()
+    m, = models(sd_c, sd_f, 3, 2, (dict(trunk="onchip", trunk_width=256),))
+    eager = replay_equals_eager(m, ro, rd, lambda o, d: m.render_rays(o, d, oracle.YCBV_NEAR, oracle.YCBV_FAR))
+    assert np.isfinite(eager["rgb_map"]).all()
 
 
 def _bounds_runs(oracle):
@@ -262,38 +189,9 @@ def test_wide_onchip_trunk_in_the_bounds_checked_build(tmp_path):
     """libnsr_debug.so (-DNSR_DEBUG_BOUNDS) checks every LDS and global index of kw_trunk_h2 (tag 200000 + line).  A fresh process
     runs the two cases above on the wide on-chip handle, render_rays and run_network on 129 points; no check may trip, and every
     output equals the release build's."""
-    import subprocess
-    dbg = os.path.join(ROOT, "neural_sim_nerf_amd", "csrc", "libnsr_debug.so")
-    if not os.path.exists(dbg):
+    got = bounds_checked_build(tmp_path, ("test_gpu_wide_trunk256", "_bounds_runs"), dict(trunk="onchip", trunk_width=256), (None,),
+                               ("render", "run_network1"))
+    if got is None:
         pytest.skip("libnsr_debug.so not built (make -C neural_sim_nerf_amd/csrc debug)")
-    code = r'''
-import os, sys, numpy as np
-sys.path.insert(0, %r); sys.path.insert(0, %r); sys.path.insert(0, %r)
-import nerf_oracle as O
-from neural_sim_nerf_amd.wide import WideModel
-from test_gpu_wide_trunk256 import _bounds_runs
-out, res = {}, []
-for tag, c, f, o, d in _bounds_runs(O):
-    m = WideModel(c, f, n_samples=3, n_importance=2, mlp="f16x2", trunk="onchip", trunk_width=256)
-    r = m.render_rays(o, d, O.YCBV_NEAR, O.YCBV_FAR, debug=True)
-    rn = m.run_network(np.zeros((129, 3), np.float32) + 0.01, np.tile(np.float32([0, 0, 1]), (129, 1)), 1)
-    res += [r[k].cpu().numpy() for k in ("rgb_map", "raw", "raw0", "z_fine")] + [rn.cpu().numpy()]
-    out[tag] = m.debug_bounds_status() + (m.range_status()["passes_rerun"],)
-    m.close()
-np.savez(sys.argv[1] + "/res.npz", *res)
-print(out)
-''' % (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests"))
-    res = {}
-    for name, lib in (("debug", dbg), ("release", os.path.join(ROOT, "neural_sim_nerf_amd", "csrc", "libnsr.so"))):
-        d = tmp_path / name
-        d.mkdir()
-        r = subprocess.run([sys.executable, "-c", code, str(d)], env=dict(os.environ, NSR_LIB_PATH=lib), capture_output=True, text=True,
-                           timeout=600)
-        assert r.returncode == 0, r.stderr[-3000:]
-        res[name] = eval(r.stdout.strip().splitlines()[-1])
-    assert len(res["debug"]) == 2 and all(v == (True, 0, 0) for v in res["debug"].values()), res["debug"]
-    assert all(v == (False, 0, 0) for v in res["release"].values()), res["release"]
-    a, b = np.load(tmp_path / "debug" / "res.npz"), np.load(tmp_path / "release" / "res.npz")
-    assert len(a.files) == len(b.files) == 2 * 5
-    for k in a.files:
-        assert np.array_equal(a[k], b[k], equal_nan=True), k
+    bounds_clean_and_equal(got, 2, 5)
+    assert all(v == (False, 0, 0) for v in got[0]["release"].values()), got[0]["release"]

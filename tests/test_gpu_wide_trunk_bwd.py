@@ -8,95 +8,25 @@ is unchanged.  So a trunk_bwd="onchip" handle must give the bits of a trunk="onc
 trunk="layers" handle: every gradient, the range safety net's counters and re-runs, hostile rays, any company of rays, under
 capture, and in the bounds-checked build.  No tolerance anywhere."""
 import ctypes
-import functools
-import os
-import sys
 
 import numpy as np
 import pytest
 
-from test_gpu_wide_tiles import OUTS, TAPS, _cots, _rays, _same, cpu
-from test_gpu_wide_trunk import L_PTS, L_VIEWS, NETS, _hostile
-from test_gpu_wide_trunk import _nets as _trunk_nets
+from test_gpu_wide_tiles import TAPS, _cots, _rays, _same, cpu
+from wide_onchip_cases import EXTRA, L_PTS, RANGE_LOG2
+from wide_onchip_cases import TRUNK_NETS as NETS
+from wide_onchip_cases import bounds_checked_build, bounds_clean_and_equal, fine_3x136, models, replay_equals_eager, small_chunks, taps_equal
+from wide_onchip_cases import bwd_nets as _nets
+from wide_onchip_cases import bwd_range_nets as _range_nets
+from wide_onchip_cases import hostile as _hostile
+from wide_onchip_cases import signed_nets as _signed_nets
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# beside test_gpu_wide_trunk.NETS, name -> (D, W, skips, multires): a 96-column encoding on a narrow network (NJ = 2 by the encoding
-# alone: its transposed image has three column blocks of weights, the hidden ones two) and the identity encoding (one column block,
-# so that the second wave column computes nothing in an encoding row)
-EXTRA = {"3x40-L15": (3, 40, [1], 15), "3x100-L0": (3, 100, [0], 0)}
-# name -> (scale, bias) of the coarse and of the fine network's density row in the SIGNED-density variant (_signed_nets), searched on
-# the CPU per network so that many rays of the image have, in both passes, a last sample of negative density behind two that count
-# (tests/test_grad_oracle_host.py chooses its rays among them and holds the result to its caps).  SIGNED_ROWS: the seed of a density
-# row drawn anew, N(0, 1 / W), where no scaling of the network's own row gives such rays (2 x 128's coarse density falls or rises
-# along every ray) or only one so large that the density is a badly conditioned multiple of a cancelling dot product (3x40-L15)
-SIGNED = {"2x128": (1.4, 1.2, -27.0, -2.3), "3x100": (28.0, 0.69, -4.1, 0.2), "3x128": (-95.0, -3.6, -6.6, -0.018),
-          "3x24": (-7.7, 2.7, 6.1, -0.4), "3x40": (-8.7, -0.094, 5.8, 0.19), "3x40-noviews": (-5.5, -0.45, -8.4, -0.41),
-          "5x100": (-3.8, -0.26, 23.0, -0.3), "3x100-L0": (-76.0, 0.099, 6.1, 0.29), "3x40-L15": (0.34, 0.23, 0.31, -0.17)}
-SIGNED_ROWS = {"2x128": (1004, None), "3x40-L15": (3002, 4001)}
-RANGE_LOG2 = 14             # log2 of the weight that sends one gradient out of fp16's range (_range_nets)
-
-
-@functools.lru_cache(maxsize=None)
-def _nets(oracle, name):
-    """(coarse, fine) of NETS[name] or EXTRA[name], with the density scaling of test_gpu_wide_trunk._nets (every ray translucent at
-    3 + 2 samples: finite disp, gradients through every layer).  Every sample's density is positive here, the last one's too, and
-    the last distance is 1e10: acc = 1 on every ray and its gradient is rounding noise -- acc, acc0 and white_bkgd's 1 - acc are
-    gradients on _signed_nets only."""
-    if name in NETS:
-        return _trunk_nets(oracle, name)
-    D, W, skips, multires = EXTRA[name]
-    nets = []
-    for s in (500 + sorted(EXTRA).index(name), 600 + sorted(EXTRA).index(name)):
-        sd = oracle.synth_weights_shape(s, D, W, multires, L_VIEWS, list(skips), True)
-        sd["alpha_linear.weight"] = (sd["alpha_linear.weight"] * np.float32(W / (400.0 * 256.0))).astype(np.float32)
-        sd["alpha_linear.bias"] = np.full_like(sd["alpha_linear.bias"], 0.5)
-        nets.append(sd)
-    return tuple(nets)
-
-
-@functools.lru_cache(maxsize=None)
-def _signed_nets(oracle, name):
-    """_nets(name) with the density rows rescaled and re-biased by SIGNED[name]: densities of either sign, of order 1, so that a ray
-    whose last sample is empty behind a translucent one has 0 < acc < 1 (some rays are empty: disp = 0 / 0 there, in the reference
-    as well).  The path cot_acc -> d sigma -> network backward carries a gradient on these, not a cancellation."""
-    nets = []
-    for sd, scale, bias, row in zip(_nets(oracle, name), SIGNED[name][0::2], SIGNED[name][1::2], SIGNED_ROWS.get(name, (None, None))):
-        sd = {k: v.copy() for k, v in sd.items()}
-        if row is not None:
-            w = sd["alpha_linear.weight"]
-            w[:] = np.random.RandomState(row).standard_normal(w.shape) / np.sqrt(w.shape[1])
-        if "alpha_linear.weight" in sd:
-            sd["alpha_linear.weight"] *= np.float32(scale)
-            sd["alpha_linear.bias"][:] = np.float32(bias)
-        else:
-            sd["output_linear.weight"][3] *= np.float32(scale)
-            sd["output_linear.bias"][3] = np.float32(bias)
-        nets.append(sd)
-    return tuple(nets)
 
 
 def _trio(sd_c, sd_f, ns, ni):
     """(trunk="layers", trunk="onchip" with trunk_bwd="layers", trunk="onchip" with trunk_bwd="onchip") f16x2 handles"""
-    from neural_sim_nerf_amd.wide import WideModel
-    ms = tuple(WideModel(sd_c, sd_f, n_samples=ns, n_importance=ni, mlp="f16x2", trunk=t, trunk_bwd=b)
-               for t, b in (("layers", "layers"), ("onchip", "layers"), ("onchip", "onchip")))
-    assert [(m.trunk, m.trunk_bwd) for m in ms] == [("layers", "layers"), ("onchip", "layers"), ("onchip", "onchip")]
-    return ms
-
-
-def _range_nets(oracle):
-    """3 x 100 (skip list [0]: layer 2 has plain K = W) whose FINE network sends one gradient out of fp16's range and no activation:
-    hidden unit 5 of layer 1 is 1e-6 on every point (weights 0, bias 1e-6: alive everywhere, negligible forward), and every unit of
-    layer 2 reads it with the weight 2^RANGE_LOG2 -- so dL/d(pre-activation of layer 1)[5] is 2^RANGE_LOG2 times the sum of layer
-    2's gradients, which kw_composite_bwd has normalised to 2^7 .. 2^8 per point"""
-    sd_c, sd_f = _nets(oracle, "3x100")
-    sd_f = {k: v.copy() for k, v in sd_f.items()}
-    sd_f["pts_linears.1.weight"][5, :] = 0.0
-    sd_f["pts_linears.1.bias"][5] = np.float32(1e-6)
-    sd_f["pts_linears.2.weight"][:, 5] = np.float32(2.0 ** RANGE_LOG2)
-    return sd_c, sd_f
+    return models(sd_c, sd_f, ns, ni, [dict(trunk=t, trunk_bwd=b) for t, b in (("layers", "layers"), ("onchip", "layers"), ("onchip", "onchip"))])
 
 
 def _bits_equal(a, b):
@@ -126,8 +56,8 @@ def test_onchip_backward_trunk_equals_the_per_layer_chain_bit_for_bit(name, orac
         ro, rd = ro_all[lo:hi], rd_all[lo:hi]
         n = len(ro)
         rs = [m.render_rays(ro, rd, near, far, debug=True) for m in ms]
-        for k in TAPS:
-            assert _same(rs[0][k], rs[2][k]) and _same(rs[1][k], rs[2][k]), (k, n)
+        taps_equal(rs[0], rs[2], n)
+        taps_equal(rs[1], rs[2], n)
         zf = cpu(rs[0]["z_fine"])
         cots = _cots(n, 31 + n)
         ex = dict(viewdirs=oracle.normalize_dirs(rd)) if views else None
@@ -152,8 +82,8 @@ def test_onchip_backward_trunk_equals_the_per_layer_chain_bit_for_bit(name, orac
     ms = _trio(*_signed_nets(oracle, name), 3, 2)
     ro, rd = ro_all[:171], rd_all[:171]
     rs = [m.render_rays(ro, rd, near, far, debug=True) for m in ms]
-    for k in TAPS:
-        assert _same(rs[0][k], rs[2][k]) and _same(rs[1][k], rs[2][k]), ("signed", k)
+    taps_equal(rs[0], rs[2], "signed")
+    taps_equal(rs[1], rs[2], "signed")
     for k in ("acc_map", "acc0"):
         acc = cpu(rs[2][k])
         assert ((acc > 0.05) & (acc < 0.95)).sum() >= 171 // 4, ("signed", k)
@@ -179,9 +109,7 @@ def test_a_mixed_handle_and_the_refusals(oracle, monkeypatch):
     caller of the C interface -- and $NSR_WIDE_TRUNK_BWD is ignored where it cannot apply, while an explicit wish raises."""
     from neural_sim_nerf_amd import wide
     sd_c = _nets(oracle, "3x40")[0]
-    sd_f = oracle.synth_weights_shape(411, 3, 136, L_PTS, L_VIEWS, [1], True)
-    sd_f["alpha_linear.weight"] = (sd_f["alpha_linear.weight"] * np.float32(136 / (400.0 * 256.0))).astype(np.float32)
-    sd_f["alpha_linear.bias"] = np.full_like(sd_f["alpha_linear.bias"], 0.5)
+    sd_f = fine_3x136(oracle)
     assert wide.trunk_bwd_plan(sd_c, "f16x2")["mode"] == "onchip"
     assert wide.trunk_bwd_plan(sd_f, "f16x2") == dict(mode="layers", reason="the trunk is not on chip")
     near, far = oracle.YCBV_NEAR, oracle.YCBV_FAR
@@ -243,8 +171,7 @@ def test_a_gradient_that_leaves_the_fp16_range_in_the_backward_trunk_reruns_the_
     near, far = oracle.YCBV_NEAR, oracle.YCBV_FAR
     ro, rd = _rays(oracle, 256, 26)
     cot = _cots(256, 41)["rgb_map"]
-    os.environ["NSR_WIDE_WORKSPACE_GB"] = "0.0001"        # the smallest workspace the library accepts: chunks of 64 rays
-    try:
+    with small_chunks():
         ms = _trio(sd_c, sd_f, 3, 2)
         rs = [m.render_rays(ro, rd, near, far, debug=True) for m in ms]
         assert ms[0].last_kernel_ms()[1] == 4
@@ -257,15 +184,12 @@ def test_a_gradient_that_leaves_the_fp16_range_in_the_backward_trunk_reruns_the_
               % (RANGE_LOG2, st[0]["passes_rerun"], st[0]["passes"] - 8))
         assert st[0]["passes_rerun"] >= 1, st[0]
         assert after_forward[0] == after_forward[1] == after_forward[2] and st[0] == st[1] == st[2], (after_forward, st)
-        for k in TAPS:
-            assert _same(rs[0][k], rs[2][k]), k
+        taps_equal(rs[0], rs[2])
         for i in range(2):
             assert _same(gs[0][i], gs[2][i]) and _same(gs[1][i], gs[2][i]), i
             assert np.isfinite(cpu(gs[2][i])).all() and np.abs(cpu(gs[2][i])).max() > 0
         for m in ms:
             m.close()
-    finally:
-        del os.environ["NSR_WIDE_WORKSPACE_GB"]
 
 
 def test_hostile_rays_through_the_backward_trunk(oracle):
@@ -291,12 +215,11 @@ def test_a_rays_gradient_on_chip_depends_on_nothing_but_the_ray(oracle):
     """3 x 128 at (5, 4) samples, 300 rays on the on-chip backward handle: all rays, the same rays reversed, the first 37 alone and all
     of them in 64-ray chunks give every ray's grad_o and grad_d the same bits (a ray's rows share a 128-point block with other
     neighbours each time)."""
-    from neural_sim_nerf_amd.wide import WideModel
     sd_c, sd_f = _nets(oracle, "3x128")
     n, near, far = 300, oracle.YCBV_NEAR, oracle.YCBV_FAR
     ro, rd = _rays(oracle, n, 22)
     cots = _cots(n, 23)
-    m = WideModel(sd_c, sd_f, n_samples=5, n_importance=4, mlp="f16x2", trunk="onchip", trunk_bwd="onchip")
+    m, = models(sd_c, sd_f, 5, 4, (dict(trunk="onchip", trunk_bwd="onchip"),))
 
     def run(sel):
         o, d = (np.ascontiguousarray(x[sel]) for x in (ro, rd))
@@ -307,11 +230,8 @@ def test_a_rays_gradient_on_chip_depends_on_nothing_but_the_ray(oracle):
     assert chunks == 1 and all(np.isfinite(x).all() and np.abs(x).max() > 0 for x in whole)
     rev, _ = run(slice(None, None, -1))
     few, _ = run(slice(0, 37))
-    os.environ["NSR_WIDE_WORKSPACE_GB"] = "0.0001"
-    try:
+    with small_chunks():
         cut, chunks = run(slice(None))
-    finally:
-        del os.environ["NSR_WIDE_WORKSPACE_GB"]
     assert chunks == (n + 63) // 64, chunks
     for k, a, b, c, d in zip(("grad_o", "grad_d"), whole, rev, few, cut):
         assert np.array_equal(a, b[::-1]), (k, "reversed")
@@ -325,33 +245,12 @@ def test_the_backward_trunk_launch_is_capturable(oracle):
     """One torch.cuda.graph capture of render_rays_vjp on the on-chip backward handle; the replay on rewritten input buffers equals the
     eager call."""
     import torch
-    from neural_sim_nerf_amd.wide import WideModel
     sd_c, sd_f = _nets(oracle, "3x100")
-    near, far = oracle.YCBV_NEAR, oracle.YCBV_FAR
     ro, rd = _rays(oracle, 171, 27)
-    cot = _cots(171, 29)["rgb_map"]
-    m = WideModel(sd_c, sd_f, n_samples=3, n_importance=2, mlp="f16x2", trunk="onchip", trunk_bwd="onchip")
-    dev = m.device
-    eager = [cpu(x) for x in m.render_rays_vjp(ro, rd, near, far, cot)]
-    assert all(np.isfinite(x).all() and np.abs(x).max() > 0 for x in eager)
-    to, td = (torch.as_tensor(np.ascontiguousarray(x[::-1]), device=dev) for x in (ro, rd))     # other rays while capturing
-    tc = torch.as_tensor(cot, device=dev)
-    s = torch.cuda.Stream(device=dev)
-    s.wait_stream(torch.cuda.current_stream(dev))
-    with torch.cuda.stream(s):
-        m.render_rays_vjp(to, td, near, far, tc)              # this stream's workspace exists before the capture
-        torch.cuda.synchronize(dev)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=s):
-            go, gd = m.render_rays_vjp(to, td, near, far, tc)
-    to.copy_(torch.as_tensor(ro, device=dev))
-    td.copy_(torch.as_tensor(rd, device=dev))
-    torch.cuda.synchronize(dev)
-    graph.replay()
-    torch.cuda.synchronize(dev)
-    assert np.array_equal(cpu(go), eager[0]) and np.array_equal(cpu(gd), eager[1])
-    assert m.range_status()["passes_rerun"] == 0
-    m.close()
+    m, = models(sd_c, sd_f, 3, 2, (dict(trunk="onchip", trunk_bwd="onchip"),))
+    cot = torch.as_tensor(_cots(171, 29)["rgb_map"], device=m.device)
+    eager = replay_equals_eager(m, ro, rd, lambda o, d: m.render_rays_vjp(o, d, oracle.YCBV_NEAR, oracle.YCBV_FAR, cot))
+    assert all(np.isfinite(x).all() and np.abs(x).max() > 0 for x in eager.values())
 
 
 def _bounds_runs(oracle):
@@ -368,44 +267,9 @@ def test_onchip_backward_trunk_in_the_bounds_checked_build(tmp_path):
     """libnsr_debug.so (-DNSR_DEBUG_BOUNDS) checks every LDS and global index of kw_trunk_bwd_h2 (tag 200000 + line).  A fresh process
     runs the cases above on the on-chip backward handle with a one-chunk and a 64-ray-chunk workspace; no check may trip, and every
     output equals the release build's."""
-    import subprocess
-    dbg = os.path.join(ROOT, "neural_sim_nerf_amd", "csrc", "libnsr_debug.so")
-    if not os.path.exists(dbg):
+    got = bounds_checked_build(tmp_path, ("test_gpu_wide_trunk_bwd", "_bounds_runs"), dict(trunk="onchip", trunk_bwd="onchip"),
+                               ("16", "0.0001"), ("vjp_rgb", "vjp_cots"))
+    if got is None:
         pytest.skip("libnsr_debug.so not built (make -C neural_sim_nerf_amd/csrc debug)")
-    code = r'''
-import os, sys, numpy as np
-sys.path.insert(0, %r); sys.path.insert(0, %r); sys.path.insert(0, %r)
-import nerf_oracle as O
-from neural_sim_nerf_amd.wide import WideModel
-from test_gpu_wide_tiles import _cots
-from test_gpu_wide_trunk_bwd import _bounds_runs
-out, res = {}, []
-for tag, c, f, o, d in _bounds_runs(O):
-    for gb in ("16", "0.0001"):
-        os.environ["NSR_WIDE_WORKSPACE_GB"] = gb
-        m = WideModel(c, f, n_samples=3, n_importance=2, mlp="f16x2", trunk="onchip", trunk_bwd="onchip")
-        cots = _cots(len(o), 51)
-        go, gd = m.render_rays_vjp(o, d, O.YCBV_NEAR, O.YCBV_FAR, cots["rgb_map"])
-        ao, ad = m.render_rays_vjp(o, d, O.YCBV_NEAR, O.YCBV_FAR, cotangents=cots)
-        res += [x.cpu().numpy() for x in (go, gd, ao, ad)]
-        out[tag + "_" + gb] = m.debug_bounds_status() + (m.range_status()["passes_rerun"],)
-        m.close()
-np.savez(sys.argv[1] + "/res.npz", *res)
-print(out)
-''' % (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests"))
-    res = {}
-    for name, lib in (("debug", dbg), ("release", os.path.join(ROOT, "neural_sim_nerf_amd", "csrc", "libnsr.so"))):
-        d = tmp_path / name
-        d.mkdir()
-        r = subprocess.run([sys.executable, "-c", code, str(d)], env=dict(os.environ, NSR_LIB_PATH=lib), capture_output=True, text=True,
-                           timeout=600)
-        assert r.returncode == 0, r.stderr[-3000:]
-        res[name] = eval(r.stdout.strip().splitlines()[-1])
-    assert len(res["debug"]) == 12 and all(v[:2] == (True, 0) for v in res["debug"].values()), res["debug"]
-    assert all(v[:2] == (False, 0) for v in res["release"].values()), res["release"]
-    assert all(v[2] > 0 if tag.startswith("range") else v[2] == 0 for tag, v in res["debug"].items() if not tag.startswith("hostile")), res["debug"]
-    assert {k: v[2] for k, v in res["debug"].items()} == {k: v[2] for k, v in res["release"].items()}
-    a, b = np.load(tmp_path / "debug" / "res.npz"), np.load(tmp_path / "release" / "res.npz")
-    assert len(a.files) == len(b.files) == 12 * 4
-    for k in a.files:
-        assert np.array_equal(a[k], b[k], equal_nan=True), k
+    bounds_clean_and_equal(got, 12, 4)
+    assert {k: v[2] for k, v in got[0]["debug"].items()} == {k: v[2] for k, v in got[0]["release"].items()}

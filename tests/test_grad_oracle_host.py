@@ -25,8 +25,10 @@ import grad_oracle as G
 from conftest import assert_close, load_golden
 from test_gpu_output_grads import FLOOR, _check, _rel_rows
 from test_gpu_wide_tiles import _cots
-from test_gpu_wide_trunk import NETS
-from test_gpu_wide_trunk_bwd import EXTRA, SIGNED, _nets, _signed_nets
+from wide_onchip_cases import EXTRA, SIGNED
+from wide_onchip_cases import TRUNK_NETS as NETS
+from wide_onchip_cases import bwd_nets as _nets
+from wide_onchip_cases import signed_nets as _signed_nets
 from test_output_grads_host import case_nets
 
 NETWORKS = sorted(NETS) + sorted(EXTRA)
@@ -110,7 +112,7 @@ def key(name, fixture, cotname, variant=""):
 
 
 def fixture_nets(oracle, name, fixture):
-    """(coarse, fine) of a fixture: test_gpu_wide_trunk_bwd._nets or ._signed_nets, the density rows x 1 / RAY_SCALE"""
+    """(coarse, fine) of a fixture: wide_onchip_cases.bwd_nets or .signed_nets, the density rows x 1 / RAY_SCALE"""
     nets = (_nets if fixture == "translucent" else _signed_nets)(oracle, name)
     if name not in RAY_SCALE:
         return nets

@@ -5,36 +5,16 @@ import os
 
 import pytest
 
-from test_wide_trunk_host import LDS_LIMIT, lds_bytes, pad32
-from test_wide_trunk_host import rule as trunk_rule
+from wide_onchip_rules import LDS_LIMIT, ROOT, pad32, wide      # (wide: the fixture)
+from wide_onchip_rules import heads_rule as rule
+from wide_onchip_rules import net
+from wide_onchip_rules import trunk_lds as lds_bytes
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WIDTHS, DEPTHS, VIEW_LEVELS = (2, 24, 40, 64, 66, 100, 128, 129, 256), (1, 2, 8), (0, 2, 4, 6, 15)
 
 
-def rule(D, W, multires_views, viewdirs, mlp, trunk, heads):
-    """None = a GEMM launch per head, else the NJ of the kernel that runs them: heads="onchip" on a handle whose trunk rule takes the
-    network, and -- with view directions -- a direction encoding of at most 96 padded columns (it takes the encoding image over)"""
-    if heads != "onchip":
-        return None
-    nj = trunk_rule(D, W, mlp, trunk)
-    if nj is None or (viewdirs and pad32(3 + 6 * multires_views) > 96):
-        return None
-    return nj
-
-
-@pytest.fixture(scope="module")
-def wide():
-    if not os.path.exists(os.path.join(ROOT, "neural_sim_nerf_amd", "csrc", "libnsr.so")):
-        pytest.skip("needs the built library (python -c 'import __graft_entry__ as g; g.build()')")
-    from neural_sim_nerf_amd import wide
-    return wide
-
-
 def _net(wide, D, W, multires_views, viewdirs, multires=10, skips=()):
-    skips = list(skips)
-    return wide.NsrwNet(D, W, multires, multires_views if viewdirs else 0, 1 if viewdirs else 0, 4 if viewdirs else 5, len(skips),
-                        (wide.C.c_int32 * wide.MAX_SKIPS)(*(skips + [0] * (wide.MAX_SKIPS - len(skips)))))
+    return net(wide, D, W, multires, skips, viewdirs, multires_views)
 
 
 def test_heads_plan_is_the_rule(wide):

@@ -5,59 +5,16 @@ import os
 
 import pytest
 
-from test_wide_trunk_host import LDS_LIMIT, pad32
-from test_wide_trunk_host import lds_bytes as lds_bytes_128
-from test_wide_trunk_host import rule as rule_128
+from wide_onchip_rules import LDS_LIMIT, ROOT, pad32, wide      # (wide: the fixture)
+from wide_onchip_rules import net as _net
+from wide_onchip_rules import trunk_lds as lds_bytes
+from wide_onchip_rules import trunk_nj as rule_128
+from wide_onchip_rules import trunk_reason_128 as reason_128
+from wide_onchip_rules import trunk_rule as rule
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WIDTHS = (2, 64, 128, 129, 136, 160, 161, 192, 200, 224, 256, 257, 288, 1024)
 DEPTHS, LEVELS = (1, 2, 3, 8, 64), (0, 4, 10, 15)
-
-
-def rule(D, W, mlp, trunk, trunk_width):
-    """None = layer by layer, else (NJ, rows of a tile): the 128-row forms up to a padded width of 128 as ever; with trunk_width = 256
-    the wide form -- 64 rows, two column blocks a wave -- for padded widths 160 .. 256 under the same other conditions"""
-    nj = rule_128(D, W, mlp, trunk)
-    if nj is not None:
-        return nj, 128
-    if trunk_width == 256 and trunk == "onchip" and mlp == "f16x2" and D >= 2 and 128 < pad32(W) <= 256:
-        return 2, 64
-    return None
-
-
-def reason_128(D, W, mlp, trunk):
-    """why trunk_width = 128 leaves a (valid) network layer by layer, in the library's words and its order of asking"""
-    if trunk != "onchip":
-        return "NSRW_FLAG_TRUNK_ONCHIP not set"
-    if mlp != "f16x2":
-        return "not an f16x2 handle"
-    if D < 2:
-        return "one layer: nothing to keep on chip"
-    assert pad32(W) > 128
-    return "padded width above 128"
-
-
-def lds_bytes(nj, rows):
-    """the wide form: double-buffered weight stages of two k16 blocks x EIGHT column blocks x 2 KiB; two fp16 piece images of the
-    activation, 64 rows of 256 values + 16 bytes; two of the encoding, 64 rows of 96 values + 16 bytes"""
-    if rows == 128:
-        return lds_bytes_128(nj)
-    assert (nj, rows) == (2, 64)
-    return 2 * (2 * 8 * 2048) + 2 * 64 * (2 * 256 + 16) + 2 * 64 * (2 * 96 + 16)
-
-
-@pytest.fixture(scope="module")
-def wide():
-    if not os.path.exists(os.path.join(ROOT, "neural_sim_nerf_amd", "csrc", "libnsr.so")):
-        pytest.skip("needs the built library (python -c 'import __graft_entry__ as g; g.build()')")
-    from neural_sim_nerf_amd import wide
-    return wide
-
-
-def _net(wide, D, W, multires=10, skips=(), viewdirs=True):
-    skips = list(skips)
-    return wide.NsrwNet(D, W, multires, 4 if viewdirs else 0, 1 if viewdirs else 0, 4 if viewdirs else 5, len(skips),
-                        (wide.C.c_int32 * wide.MAX_SKIPS)(*(skips + [0] * (wide.MAX_SKIPS - len(skips)))))
+lds_bytes_128 = lds_bytes
 
 
 def _cases(wide):

@@ -5,56 +5,14 @@ import os
 
 import pytest
 
-from test_wide_trunk256_host import rule as trunk_rule
-from test_wide_trunk_host import LDS_LIMIT, pad32
+from wide_onchip_rules import LDS_LIMIT, ROOT, wide      # (wide: the fixture)
+from wide_onchip_rules import bwd_lds as lds_bytes
+from wide_onchip_rules import bwd_reason as reason
+from wide_onchip_rules import bwd_rule as rule
+from wide_onchip_rules import net as _net
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WIDTHS = (8, 24, 32, 33, 40, 64, 65, 96, 100, 128, 129, 136, 160, 200, 256, 257, 300)
 DEPTHS, LEVELS = (1, 2, 3, 4), (0, 4, 10, 15)
-
-
-def rule(D, W, multires, mlp, trunk, trunk_bwd, trunk_width):
-    """None = a GEMM launch per product, else the NJ of the backward kernel: trunk_bwd="onchip" on a handle whose trunk rule takes the
-    network in its 128-row form (so f16x2, two layers, a padded width of at most 128); NJ covers the wider of the two outputs, the
-    hidden width and the encoding -- one column block a wave up to 64 columns, two up to 128 (a 96-column encoding has an image of
-    four column blocks)"""
-    if trunk_bwd != "onchip":
-        return None
-    t = trunk_rule(D, W, mlp, trunk, trunk_width)
-    if t is None or t[1] != 128 or D < 2:
-        return None
-    return max(1 if pad32(W) <= 64 else 2, 1 if pad32(3 + 6 * multires) <= 64 else 2)
-
-
-def reason(D, W, mlp, trunk, trunk_bwd, trunk_width):
-    """why a (valid) network stays layer by layer, in the library's words and its order of asking"""
-    if trunk_bwd != "onchip":
-        return "NSRW_FLAG_TRUNK_BWD not set"
-    t = trunk_rule(D, W, mlp, trunk, trunk_width)
-    if t is None:
-        return "the trunk is not on chip"
-    assert t[1] == 64
-    return "padded width above 128: the wide trunk has no backward form"
-
-
-def lds_bytes(nj):
-    """double-buffered weight stages of two k16 blocks x 2 NJ column blocks x 2 KiB; two fp16 piece images of the gradient, 128 rows of
-    64 NJ values + 16 bytes; no encoding image"""
-    return 2 * (2 * nj * 2 * 2048) + 2 * 128 * (2 * 64 * nj + 16)
-
-
-@pytest.fixture(scope="module")
-def wide():
-    if not os.path.exists(os.path.join(ROOT, "neural_sim_nerf_amd", "csrc", "libnsr.so")):
-        pytest.skip("needs the built library (python -c 'import __graft_entry__ as g; g.build()')")
-    from neural_sim_nerf_amd import wide
-    return wide
-
-
-def _net(wide, D, W, multires=10, skips=(), viewdirs=True):
-    skips = list(skips)
-    return wide.NsrwNet(D, W, multires, 4 if viewdirs else 0, 1 if viewdirs else 0, 4 if viewdirs else 5, len(skips),
-                        (wide.C.c_int32 * wide.MAX_SKIPS)(*(skips + [0] * (wide.MAX_SKIPS - len(skips)))))
 
 
 def test_trunk_bwd_plan_is_the_rule(wide):

@@ -4,40 +4,10 @@ import os
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LDS_LIMIT = 160 * 1024              # bytes of LDS one workgroup may have on gfx950
-
-
-def pad32(x):
-    return (x + 31) // 32 * 32
-
-
-def rule(D, W, mlp, trunk):
-    """None = layer by layer, else the NJ of the trunk kernel: an f16x2 handle made with trunk="onchip", at least two layers, and
-    a padded width of at most 128 (one tile along N: NJ = 1 up to 64 columns, NJ = 2 for 128)"""
-    if trunk != "onchip" or mlp != "f16x2" or D < 2 or pad32(W) > 128:
-        return None
-    return 1 if pad32(W) <= 64 else 2
-
-
-def lds_bytes(nj):
-    """double-buffered weight stages of two k16 blocks x 2 NJ column blocks x 2 KiB; two fp16 piece images of the activation, 128 rows
-    of 64 NJ values + 16 bytes; two of the encoding, 128 rows of 96 values + 16 bytes"""
-    return 2 * (2 * nj * 2 * 2048) + 2 * 128 * (2 * 64 * nj + 16) + 2 * 128 * (2 * 96 + 16)
-
-
-@pytest.fixture(scope="module")
-def wide():
-    if not os.path.exists(os.path.join(ROOT, "neural_sim_nerf_amd", "csrc", "libnsr.so")):
-        pytest.skip("needs the built library (python -c 'import __graft_entry__ as g; g.build()')")
-    from neural_sim_nerf_amd import wide
-    return wide
-
-
-def _net(wide, D, W, multires=10, skips=(), viewdirs=True):
-    skips = list(skips)
-    return wide.NsrwNet(D, W, multires, 4 if viewdirs else 0, 1 if viewdirs else 0, 4 if viewdirs else 5, len(skips),
-                        (wide.C.c_int32 * wide.MAX_SKIPS)(*(skips + [0] * (wide.MAX_SKIPS - len(skips)))))
+from wide_onchip_rules import LDS_LIMIT, ROOT, pad32, wide      # (wide: the fixture)
+from wide_onchip_rules import net as _net
+from wide_onchip_rules import trunk_lds as lds_bytes
+from wide_onchip_rules import trunk_nj as rule
 
 
 def test_trunk_plan_is_the_rule(wide):
@@ -75,6 +45,36 @@ def test_trunk_plan_reads_state_dicts_and_refuses_invalid_networks(wide, oracle)
     from neural_sim_nerf_amd import _lib
     with pytest.raises(_lib.NsrError, match="netwidth"):
         wide.trunk_plan(_net(wide, 3, 1), "f16x2")
+
+
+def test_the_plans_lds_bytes_are_those_of_the_kernel_they_select(wide):
+    """Every on-chip form: the lds_bytes a plan reports equals the LDS the kernel it selects has in the built library -- the code
+    object's group_segment_fixed_size (tools/kernel_resources.py).  The kernel is named by the plan's own figures: kw_trunk_h2<nj,
+    heads, tile_rows / 32> and kw_trunk_bwd_h2<nj>; the seven named here are all the library instantiates."""
+    import sys
+    lib = os.path.join(ROOT, "neural_sim_nerf_amd", "csrc", "libnsr.so")
+    if not os.path.exists(lib) or not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-readelf"):
+        pytest.skip("needs the built library and the ROCm LLVM tools")
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from kernel_resources import kernel_resources
+    res = kernel_resources(lib)[0]
+    seen = {}
+    for W, width, L in ((40, 128, 4), (128, 128, 4), (256, 256, 4), (40, 128, 15)):      # NJ = 1, 2; the wide form; NJ = 2 by the encoding
+        n = _net(wide, 3, W, L, [0])
+        trunk = wide.trunk_plan(n, "f16x2", "onchip", trunk_width=width)
+        plans = [("kw_trunk_h2<%d, 0, %d>" % (trunk["nj"], trunk["tile_rows"] // 32), trunk)]
+        heads = wide.heads_plan(n, "f16x2", "onchip", "onchip", trunk_width=width)
+        bwd = wide.trunk_bwd_plan(n, "f16x2", "onchip", "onchip", trunk_width=width)
+        assert (heads["mode"], bwd["mode"]) == (("onchip", "onchip") if width == 128 else ("layers", "layers")), (W, heads, bwd)
+        if width == 128:
+            plans += [("kw_trunk_h2<%d, 1, 4>" % trunk["nj"], heads), ("kw_trunk_bwd_h2<%d>" % bwd["nj"], bwd)]
+        for kernel, plan in plans:
+            assert plan["lds_bytes"] == res[kernel]["group_segment_fixed_size"], (W, L, kernel, plan, res[kernel])
+            seen[kernel] = plan["lds_bytes"]
+    assert seen == {"kw_trunk_h2<1, 0, 4>": 106496, "kw_trunk_h2<2, 0, 4>": 155648, "kw_trunk_h2<1, 1, 4>": 106496,
+                    "kw_trunk_h2<2, 1, 4>": 155648, "kw_trunk_h2<2, 0, 2>": 159744, "kw_trunk_bwd_h2<1>": 53248,
+                    "kw_trunk_bwd_h2<2>": 102400}, seen
+    assert sorted(seen) == sorted(k for k in res if k.startswith("kw_trunk")), sorted(res)
 
 
 def test_flag_and_signature_are_declared(wide):
