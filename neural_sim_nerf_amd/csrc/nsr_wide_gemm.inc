@@ -53,6 +53,13 @@ constexpr unsigned kPermHi16 = 0x07060302u;          // V_PERM_B32(y, x): {y.hi1
 #define NSRW_MASK_DSRD 0x100
 #define NSRW_MASK_DSWR 0x200
 
+// the LDS-DMA of piece P of one fragment image chunk (1 KiB a piece: 64 lanes x 16 bytes): from byte `soff` (uniform) of the buffer
+// behind `rsrc` to the LDS address `l`; the immediate offsets BOTH the source and the LDS address.  The weight stages of
+// gemm_split_body and of the on-chip kernels (nsr_wide_trunk.inc) are made of it.
+#define NSRW_DMA(rsrc, l, lane, soff, P)                                                                                  \
+  __builtin_amdgcn_raw_ptr_buffer_load_lds((rsrc), (__attribute__((address_space(3))) void*)(l), 16, (lane) * 16, (soff), \
+                                           (P) * 1024, 0)
+
 // 8 fp32 -> three pieces of 8 bf16 (packed pairs, k ascending); exact: x == p0 + p1 + p2
 __device__ __forceinline__ void split8_b3(const f32x4& lo, const f32x4& hi, u32x4 (&p)[3]) {
 #pragma unroll
@@ -177,14 +184,10 @@ __device__ __forceinline__ void gemm_split_body(const GemmArgs& g, char* const s
       char* l = smem + buf * kStage + kABytes + cbl * kFrag;
       const int soff = __builtin_amdgcn_readfirstlane(tl.wsrc + (cbl * KB + kb) * kFrag);
       NSRW_CHECK(soff >= 0 && (unsigned)soff + (unsigned)kFrag <= g.wb_bytes);
-#define NSRW_DMA(P)                                                                                                   \
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)l, 16, lane * 16, soff, \
-                                           (P) * 1024, 0) /* the immediate offsets BOTH the source and the LDS address */
 #ifndef NSRW_EXP_NODMA
-      NSRW_DMA(0); NSRW_DMA(1);
-      if constexpr (NPC == 3) NSRW_DMA(2);
+      NSRW_DMA(rsrc, l, lane, soff, 0); NSRW_DMA(rsrc, l, lane, soff, 1);
+      if constexpr (NPC == 3) NSRW_DMA(rsrc, l, lane, soff, 2);
 #endif
-#undef NSRW_DMA
     }
   };
   float amax = 0.0f;                                               // f16x2: largest activation magnitude this lane has split
