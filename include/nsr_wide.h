@@ -70,6 +70,18 @@ enum { NSRW_FLAG_TRUNK_BWD = 128 }; /* opt-in, with NSRW_FLAG_TRUNK_ONCHIP only 
                                       * The kept forward pass, the bf16x3 re-runs and the networks of the wide form stay layer by layer
                                       * (nsrw_trunk_bwd_plan says which). */
 
+enum { NSRW_FLAG_TRUNK_KEEP = 256 };/* opt-in, with NSRW_FLAG_TRUNK_BWD only (nsrw_create refuses it without, hence without NSRW_FLAG_TRUNK_ONCHIP and
+                                      * NSRW_FLAG_MLP_F16X2): on a network whose backward trunk is on chip the f16x2 pass of every forward
+                                      * that KEEPS its activations for a backward -- the last network's, and the coarse network's second
+                                      * one under coarse cotangents -- runs as one launch too (kw_keep_h2; with NSRW_FLAG_HEADS_ONCHIP the
+                                      * heads behind it).  It leaves the relu masks of the layers 0 .. D - 2 as one bit per (point, unit)
+                                      * instead of fp32 rows, and the on-chip backward reads those bits (kw_keep_bwd_h2); the last
+                                      * layer's and views_linears.0's fp32 outputs stay, for the backward's head launches.  The same
+                                      * arithmetic per output element, so the same bits; the bf16x3 re-runs stay layer by layer on fp32
+                                      * activations, with a conversion between the two forms in front of or behind them.  The workspace
+                                      * of a gradient call grows by the masks, W / 8 bytes per point and kept layer
+                                      * (nsrw_trunk_keep_plan says which networks; nsrw_keep_status counts the passes). */
+
 typedef struct NsrwConfig {
   int32_t device;
   int32_t n_samples;                 /* N_samples (RN:439): 3 .. NSRW_MAX_SAMPLES -- sample_pdf needs an interior weight; nsrw_create refuses less */
@@ -239,6 +251,17 @@ int nsrw_trunk_plan(const NsrwNet* net, int flags, NsrwTrunkPlan* plan_out);
  * launch per product; nj = tile_rows = lds_bytes = 0) with the reason.  Returns 0, or -1 for an invalid network description. */
 int nsrw_trunk_bwd_plan(const NsrwNet* net, int flags, NsrwTrunkPlan* plan_out);
 
+/* DIAGNOSTIC; needs no device and no handle.  How a handle created with `flags` runs the f16x2 pass of a forward of `net` that keeps
+ * its activations for a backward: onchip = 1 -- one kw_keep_h2<nj, heads> launch over tiles of tile_rows = 128 points
+ * with lds_bytes of LDS per workgroup (the trunk's nj and LDS; heads as nsrw_heads_plan decides), the relu masks kept as bits, and
+ * the backward launch kw_keep_bwd_h2<nj of nsrw_trunk_bwd_plan> in place of kw_trunk_bwd_h2 -- or onchip = 0 (a GEMM launch per
+ * layer, fp32 activations kept; nj = tile_rows = lds_bytes = 0) with the reason.  Returns 0, or -1 for an invalid network description. */
+int nsrw_trunk_keep_plan(const NsrwNet* net, int flags, NsrwTrunkPlan* plan_out);
+
+/* NSRW_FLAG_TRUNK_KEEP handles: kept forward passes launched on chip so far (kw_keep_h2 launches, counted on the host as they are
+ * enqueued; 0 on every other handle).  Does not synchronise. */
+int nsrw_keep_status(nsrw_handle h, unsigned long long* passes_onchip);
+
 /* DIAGNOSTIC; needs no device and no handle.  How a handle created with `flags` runs the heads of `net` behind its pts_linears
  * (DESIGN.md 8): onchip = 1 -- inside the trunk's one launch, kw_trunk_h2<nj, true>, with lds_bytes of LDS per workgroup -- or
  * onchip = 0 (a GEMM launch per head; lds_bytes = 0) with the reason.  Returns 0, or -1 for an invalid network description. */
@@ -251,7 +274,8 @@ int nsrw_heads_plan(const NsrwNet* net, int flags, NsrwHeadsPlan* plan_out);
 /* libnsr_debug.so (-DNSR_DEBUG_BOUNDS) checks every global / LDS index of this unit's kernels against its extent; a violation is
  * recorded, not trapped.  built_with_checks: 1 in that build, 0 in the product library; first_bad_line: 0 = clean, else the source
  * line of the (highest) failed check -- nsr_wide.hip's line, 100000 + the line of nsr_wide_gemm.inc, or 200000 + the line of
- * nsr_wide_trunk.inc (all forms of kw_trunk_h2, the wide one included, and kw_trunk_bwd_h2).  Synchronises the device. */
+ * nsr_wide_trunk.inc (all forms of kw_trunk_h2, the wide one included, kw_trunk_bwd_h2, kw_keep_h2, kw_keep_bwd_h2 and the two mask
+ * kernels).  Synchronises the device. */
 int nsrw_debug_bounds_status(int* built_with_checks, unsigned* first_bad_line);
 
 #ifdef __cplusplus

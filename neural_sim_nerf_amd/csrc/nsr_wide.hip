@@ -676,14 +676,16 @@ struct Mat {                 // one packed matrix [Np][K1p + K2p] and its (nulla
 
 // What a handle runs on chip for one network (onchip_plan): per decision the kernel form that does it -- a row of kTrunkForms -- or
 // why there is none.  trunk: the pts_linears in one launch; heads: the heads behind them in that launch (its form replaces the
-// trunk's); bwd: the layer loop of the input-gradient chain in one launch.
+// trunk's); bwd: the layer loop of the input-gradient chain in one launch; keep: the f16x2 pass of a forward that keeps its
+// activations in one launch (with it, keep_bwd: the backward launch that reads the masks as bits instead of bwd's).
 struct TrunkForm;
 struct Onchip {
   const TrunkForm* form = nullptr;
   const char* why = "";
 };
 struct OnchipPlan {
-  Onchip trunk, heads, bwd;
+  Onchip trunk, heads, bwd, keep;
+  const TrunkForm* keep_bwd = nullptr;
   const TrunkForm* forward() const { return heads.form ? heads.form : trunk.form; }      // the form of the forward's launch
 };
 
@@ -761,7 +763,8 @@ struct GemmCfg {
   int cus = 256;                        // compute units of the handle's device
   Arith arith = kF32;                   // NsrwConfig::flags: NSRW_FLAG_MLP_F16X2 -> kH2, NSRW_FLAG_MLP_BF16X3 -> kB3, neither -> kF32
   int tile_wm = 4;                      // 256-column tiles with 256 rows / 512 threads (4) or 128 rows / 256 threads (2: NSRW_B3_WM = 2)
-  int flags = 0;                        // NsrwConfig::flags (onchip_plan reads the arithmetic and the four on-chip flags)
+  int flags = 0;                        // NsrwConfig::flags (onchip_plan reads the arithmetic and the five on-chip flags)
+  unsigned long long* keep_passes = nullptr;      // host: kept forward passes launched on chip so far (Handle::keep_passes)
   unsigned* d_range = nullptr;          // device: [0] flag of the f16x2 pass in flight, [1] passes run, [2] passes re-run on bf16x3
 };
 
@@ -783,6 +786,7 @@ struct Handle {
   unsigned* d_range = nullptr;      // GemmCfg::d_range
   bool timed = false;
   int chunks = 0;
+  unsigned long long keep_passes = 0;     // nsrw_keep_status
 };
 
 // appends a packed [Np][Kp] matrix to `img`; get(n, k) is consulted for n < rows, k < cols only
@@ -885,6 +889,7 @@ struct Chunk {
   float *E, *ED, *FA, *HV, *RAW;
   std::vector<float*> H;
   float *DRAW, *GV, *G0, *G1, *GEP, *GED, *gscale;
+  unsigned short* MB = nullptr;     // NSRW_FLAG_TRUNK_KEEP, grad >= 1: the relu masks of a kept pass as bits (keep_masks)
 };
 
 // grad: 0 = forward only, 1 = + the last pass's backward (nsrw_render_rays_vjp), 2 = + the coarse pass's backward as well
@@ -916,6 +921,15 @@ void carve_chunk(const Handle& h, long long R, int grad, Carve& c, Chunk& k) {
     k.GEP = c.f(Pg * last.Ci); k.GED = c.f(Pg * last.Cv);
   } else {
     k.scr_a = k.scr_t = k.DRAW = k.GV = k.G0 = k.G1 = k.GEP = k.GED = k.gscale = nullptr;
+  }
+  // handles with NSRW_FLAG_TRUNK_KEEP: the masks of a kept on-chip pass, Wp / 8 bytes per point and kept layer over whole blocks of 128
+  // points, for the larger of the networks that have the form (behind everything else: without the flag the carve is what it was)
+  k.MB = nullptr;
+  if (grad && (h.cfg.flags & NSRW_FLAG_TRUNK_KEEP)) {
+    size_t words = 0;
+    for (const Net* n : {&n0, &n1})
+      if (n->onchip.keep.form) words = std::max(words, (size_t)(n->d.D - 1) * (size_t)((P + 127) / 128) * (n->Wp / 32) * 256);
+    if (words) k.MB = reinterpret_cast<unsigned short*>(c.f((words + 1) / 2));
   }
 }
 
@@ -1022,30 +1036,43 @@ int gemm(const GemmCfg& cfg, Run run, hipStream_t st, const Net& net, const Mat&
 // these rows and the launches run the row they are handed: the kernel, its tile rows and its LDS bytes are stated here and nowhere else.
 typedef void (*TrunkKernel)(TrunkArgs);
 typedef void (*TrunkBwdKernel)(TrunkBwdArgs);
+typedef void (*TrunkKeepKernel)(TrunkArgs, TrunkKeepArgs);
+typedef void (*TrunkKeepBwdKernel)(TrunkBwdArgs, KeepMasks);
+enum TrunkKind { kFormFwd, kFormBwd, kFormKeep, kFormKeepBwd };
 struct TrunkForm {
+  TrunkKind kind;                       // which of the four kernels below the row has
   int nj, tile_rows;                    // 32-column blocks of the output one wave accumulates; points of a block
   bool heads;                           // forward rows: the heads run behind the trunk in the launch
   TrunkKernel fwd;                      // kw_trunk_h2, or
-  TrunkBwdKernel bwd;                   // kw_trunk_bwd_h2: exactly one of the two
+  TrunkBwdKernel bwd;                   // kw_trunk_bwd_h2, or
+  TrunkKeepKernel keep;                 // kw_keep_h2, or
+  TrunkKeepBwdKernel keep_bwd;          // kw_keep_bwd_h2: exactly one of the four
   int lds_bytes;                        // the kernel's own (static) LDS
 };
 template <int NJ, bool HEADS, int WR = 4>
-TrunkForm trunk_fwd_form() { return {NJ, trunk_rows<WR>(), HEADS, kw_trunk_h2<NJ, HEADS, WR>, nullptr, trunk_lds_bytes<NJ, WR>()}; }
+TrunkForm trunk_fwd_form() { return {kFormFwd, NJ, trunk_rows<WR>(), HEADS, kw_trunk_h2<NJ, HEADS, WR>, nullptr, nullptr, nullptr, trunk_lds_bytes<NJ, WR>()}; }
 template <int NJ>
-TrunkForm trunk_bwd_form_row() { return {NJ, trunk_rows<4>(), false, nullptr, kw_trunk_bwd_h2<NJ>, trunk_bwd_lds_bytes<NJ>()}; }
+TrunkForm trunk_bwd_form_row() { return {kFormBwd, NJ, trunk_rows<4>(), false, nullptr, kw_trunk_bwd_h2<NJ>, nullptr, nullptr, trunk_bwd_lds_bytes<NJ>()}; }
+template <int NJ, bool HEADS>
+TrunkForm trunk_keep_form() { return {kFormKeep, NJ, trunk_rows<4>(), HEADS, nullptr, nullptr, kw_keep_h2<NJ, HEADS>, nullptr, trunk_lds_bytes<NJ, 4>()}; }
+template <int NJ>
+TrunkForm trunk_keep_bwd_form() { return {kFormKeepBwd, NJ, trunk_rows<4>(), false, nullptr, nullptr, nullptr, kw_keep_bwd_h2<NJ>, trunk_bwd_lds_bytes<NJ>()}; }
 // (in this order: the order of instantiation is the order of the kernels in the code object)
 const TrunkForm kTrunkForms[] = {trunk_fwd_form<1, true>(), trunk_fwd_form<2, true>(), trunk_fwd_form<1, false>(), trunk_fwd_form<2, false>(),
-                                 trunk_fwd_form<2, false, 2>(), trunk_bwd_form_row<1>(), trunk_bwd_form_row<2>()};
+                                 trunk_fwd_form<2, false, 2>(), trunk_bwd_form_row<1>(), trunk_bwd_form_row<2>(),
+                                 trunk_keep_form<1, true>(), trunk_keep_form<2, true>(), trunk_keep_form<1, false>(), trunk_keep_form<2, false>(),
+                                 trunk_keep_bwd_form<1>(), trunk_keep_bwd_form<2>()};
 constexpr int kTrunkThreads = 512;
 
-const TrunkForm* find_trunk_form(bool bwd, int nj, int tile_rows, bool heads) {
+const TrunkForm* find_trunk_form(TrunkKind kind, int nj, int tile_rows, bool heads) {
   for (const TrunkForm& f : kTrunkForms)
-    if ((f.bwd != nullptr) == bwd && f.nj == nj && f.tile_rows == tile_rows && f.heads == heads) return &f;
+    if (f.kind == kind && f.nj == nj && f.tile_rows == tile_rows && f.heads == heads) return &f;
   return nullptr;
 }
 
 // What a handle created with `flags` runs on chip for the network `d` -- pure host arithmetic, no HIP call (nsrw_trunk_plan,
-// nsrw_heads_plan and nsrw_trunk_bwd_plan expose its three decisions; nsrw_upload_network keeps it).  DESIGN.md 8 has the table.
+// nsrw_heads_plan, nsrw_trunk_bwd_plan and nsrw_trunk_keep_plan expose its four decisions; nsrw_upload_network keeps it).  DESIGN.md 8
+// has the table.
 //   trunk: an f16x2 handle with NSRW_FLAG_TRUNK_ONCHIP, at least two layers, and a packed width of at most 128, so that the whole N
 //     extent is one tile of 128 rows (NJ = 1: <= 64 columns, NJ = 2: 128); with NSRW_FLAG_TRUNK_WIDE on top a packed width of
 //     160 .. 256 too: the wide form, tiles of 64 rows by 256 columns.
@@ -1053,14 +1080,16 @@ const TrunkForm* find_trunk_form(bool bwd, int nj, int tile_rows, bool heads) {
 //     the encoding image it takes over.  The kernel's LDS is the trunk's.
 //   bwd: NSRW_FLAG_TRUNK_BWD and a trunk on chip in its 128-row form (hence f16x2 and at least two layers: there is a hidden row).
 //     NJ covers the wider of the two outputs: the hidden width and the encoding.
+//   keep: NSRW_FLAG_TRUNK_KEEP and a backward trunk on chip (hence f16x2, the 128-row forward form and at least two layers).  The
+//     forward form the heads decision chooses, with the trunk's NJ and LDS; the backward launch becomes the bit-reading one of bwd's NJ.
 OnchipPlan onchip_plan(const NsrwNet& d, int flags) {
   OnchipPlan p;
-  auto decide = [](Onchip& c, const char* why, bool bwd, int nj, int tile_rows, bool heads) {
-    if (!why && !(c.form = find_trunk_form(bwd, nj, tile_rows, heads))) why = "internal error: form not compiled";
+  auto decide = [](Onchip& c, const char* why, TrunkKind kind, int nj, int tile_rows, bool heads) {
+    if (!why && !(c.form = find_trunk_form(kind, nj, tile_rows, heads))) why = "internal error: form not compiled";
     c.why = why ? why : "";
   };
   if (!check_net(d).empty()) {
-    p.trunk.why = p.heads.why = p.bwd.why = "invalid network";
+    p.trunk.why = p.heads.why = p.bwd.why = p.keep.why = "invalid network";
     return p;
   }
   const int Wp = pad32(d.W), Ci = pad32(3 + 6 * d.multires), narrow = trunk_rows<4>();
@@ -1074,7 +1103,7 @@ OnchipPlan onchip_plan(const NsrwNet& d, int flags) {
          : !wide && Wp > 128               ? "padded width above 128"
          : Ci > kTrunkCiMax                ? "encoding wider than 96"
                                            : nullptr,
-         false, nj, wide ? trunk_rows<2>() : narrow, false);
+         kFormFwd, nj, wide ? trunk_rows<2>() : narrow, false);
   const bool narrow_trunk = p.trunk.form && p.trunk.form->tile_rows == narrow;
   decide(p.heads,
          !(flags & NSRW_FLAG_HEADS_ONCHIP) ? "NSRW_FLAG_HEADS_ONCHIP not set"
@@ -1082,13 +1111,22 @@ OnchipPlan onchip_plan(const NsrwNet& d, int flags) {
          : !narrow_trunk                   ? "padded width above 128: the wide trunk has no heads form"
          : d.use_viewdirs && pad32(3 + 6 * d.multires_views) > kTrunkCiMax ? "direction encoding wider than 96"
                                            : nullptr,
-         false, nj, narrow, true);
+         kFormFwd, nj, narrow, true);
   decide(p.bwd,
          !(flags & NSRW_FLAG_TRUNK_BWD) ? "NSRW_FLAG_TRUNK_BWD not set"
          : !p.trunk.form                ? "the trunk is not on chip"
          : !narrow_trunk                ? "padded width above 128: the wide trunk has no backward form"
                                         : nullptr,
-         true, std::max(nj, Ci <= 64 ? 1 : 2), narrow, false);
+         kFormBwd, std::max(nj, Ci <= 64 ? 1 : 2), narrow, false);
+  decide(p.keep,
+         !(flags & NSRW_FLAG_TRUNK_KEEP) ? "NSRW_FLAG_TRUNK_KEEP not set"
+         : !p.bwd.form                   ? "the backward trunk is not on chip"
+                                         : nullptr,
+         kFormKeep, nj, narrow, p.heads.form != nullptr);
+  if (p.keep.form && !(p.keep_bwd = find_trunk_form(kFormKeepBwd, p.bwd.form->nj, narrow, false))) {
+    p.keep.form = nullptr;
+    p.keep.why = "internal error: form not compiled";
+  }
   return p;
 }
 
@@ -1106,6 +1144,8 @@ constexpr FlagNeeds kFlagNeeds[] = {
      "nsrw_create: NSRW_FLAG_HEADS_ONCHIP needs NSRW_FLAG_TRUNK_ONCHIP (the on-chip heads run behind the on-chip trunk, in its launch)"},
     {NSRW_FLAG_TRUNK_BWD, NSRW_FLAG_TRUNK_ONCHIP,
      "nsrw_create: NSRW_FLAG_TRUNK_BWD needs NSRW_FLAG_TRUNK_ONCHIP (the on-chip backward trunk serves the networks the on-chip trunk serves)"},
+    {NSRW_FLAG_TRUNK_KEEP, NSRW_FLAG_TRUNK_BWD,
+     "nsrw_create: NSRW_FLAG_TRUNK_KEEP needs NSRW_FLAG_TRUNK_BWD (the kept on-chip forward leaves its relu masks as bits, which only the on-chip backward trunk reads)"},
 };
 
 // the decisions as the diagnostic entries report them (no form: every figure 0, and the reason)
@@ -1200,21 +1240,69 @@ void trunk_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk&
   hipLaunchKernelGGL(f.fwd, trunk_grid(cfg, f, P), dim3(kTrunkThreads), 0, st, t);
 }
 
+// The masks of a kept on-chip pass of `n` over P points inside k.MB, in the layout of keep_mask_word (nsr_wide_trunk.inc)
+KeepMasks keep_masks(const Net& n, const Chunk& k, long long P) {
+  const int nblk = (int)((P + 127) / 128);
+  return KeepMasks{k.MB, (long long)nblk * (n.Wp / 32) * 256, nblk, n.d.D - 1};
+}
+
+// The f16x2 pass of a forward that KEEPS its activations, in one launch (n.onchip.keep): k.E, k.ED -> the masks of layers 0 .. D - 2
+// as bits in k.MB, fp32 k.H[D - 1] -- where the kept per-layer chain leaves it -- and, in the heads form, fp32 k.HV and k.RAW
+int keep_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P) {
+  const TrunkForm& f = *n.onchip.keep.form;
+  if (!k.MB) return fail("nsrw: internal error: a kept on-chip pass without a mask buffer");
+  TrunkKeepArgs a{};
+  TrunkArgs t{};
+  t.E = k.E; t.ldE = n.Ci;
+  t.img = n.dImg[kH2]; t.img_bytes = (unsigned)n.img_bytes[kH2];
+  t.bias = n.dBias; t.bias_floats = n.bias_floats;
+  t.layers = n.dTrunk; t.D = n.trunk_rows; t.Dt = n.d.D;
+  t.C = k.H[n.d.D - 1]; t.Wp = n.Wp;
+  t.ED = n.d.use_viewdirs ? k.ED : nullptr; t.ldED = n.Cv;
+  t.RAW = k.RAW;
+  t.M = P;
+  t.range_flag = cfg.d_range;
+  a.HV = k.HV; a.ldHV = n.W2p;
+  a.masks = keep_masks(n, k, P);
+  hipLaunchKernelGGL(f.keep, trunk_grid(cfg, f, P), dim3(kTrunkThreads), 0, st, t, a);
+  if (cfg.keep_passes) ++*cfg.keep_passes;
+  return 0;
+}
+
+// kw_mask_pack / kw_mask_unpack over the masks of a kept pass, conditional on the range flag like the bf16x3 chain's launches
+int mask_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P, bool pack) {
+  const long long ldH = k.H[1] - k.H[0];
+  for (int i = 0; i + 1 < n.d.D; ++i)
+    if (k.H[i] != k.H[0] + i * ldH) return fail("nsrw: internal error: the kept activations are not equally spaced");
+  MaskArgs g{};
+  g.H0 = k.H[0]; g.ldH = ldH; g.Wp = n.Wp; g.M = P;
+  g.masks = keep_masks(n, k, P);
+  g.run_if = cfg.d_range;
+  const long long words = g.masks.ld * g.masks.n_layers;
+  hipLaunchKernelGGL(pack ? kw_mask_pack : kw_mask_unpack, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, g);
+  return 0;
+}
+// whether the kept passes of `n` over P points run on chip: the forward's f16x2 pass in keep_launch, the backward's reading bits
+bool keep_pass(const Net& n, long long P) { return onchip_pass(Run{kH2, nullptr}, n.onchip.keep.form, P); }
+
 // RH:99-122 over P points whose encodings are in k.E / k.ED: leaves the rgb logits in k.RAW (ld 32; all output_linear rows
 // without view directions) and the density at sigma / ld_sigma.  keep: every pts layer's activation stays (k.H[i]).
 int net_forward_chain(const GemmCfg& cfg, Run run, hipStream_t st, const Net& n, const Chunk& k, long long P, bool keep, const float** sigma,
                       int* ld_sigma) {
   const float* h = nullptr;
-  // f16x2 pass of an eligible network on an on-chip handle, no activation kept: the one trunk launch (the conditional bf16x3
-  // re-run and every pass that keeps its activations for a backward stay layer by layer)
-  const bool onchip = !keep && onchip_pass(run, n.onchip.forward(), P);
+  // f16x2 pass of an eligible network on an on-chip handle: the one trunk launch where no activation is kept, the one kept launch
+  // where the network has that form (the conditional bf16x3 re-run and every other pass that keeps its activations for a backward
+  // stay layer by layer)
+  const bool kept = keep && onchip_pass(run, n.onchip.keep.form, P);
+  const bool onchip = kept || (!keep && onchip_pass(run, n.onchip.forward(), P));
   if (onchip) {
-    trunk_launch(cfg, st, n, k, P);
-    if (n.onchip.heads.form) {        // the heads ran behind the trunk: k.H, k.FA and k.HV are not written
+    if (kept) { if (keep_launch(cfg, st, n, k, P)) return 1; }
+    else trunk_launch(cfg, st, n, k, P);
+    if (n.onchip.heads.form) {        // the heads ran behind the trunk: k.FA is not written (kept: k.H[D - 1], k.HV and the masks are)
       *sigma = k.RAW + 3; *ld_sigma = n.ldraw;
       return 0;
     }
-    h = k.H[(n.d.D - 1) & 1];
+    h = k.H[kept ? n.d.D - 1 : (n.d.D - 1) & 1];
   }
   for (int i = 0; i < n.d.D && !onchip; ++i) {
     float* out = k.H[keep ? i : (i & 1)];
@@ -1255,6 +1343,8 @@ int net_forward(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k
   // range (its inputs -- the encodings -- are untouched, every buffer it writes is written again); then the tally
   if (net_forward_chain(cfg, Run{kH2, nullptr}, st, n, k, P, keep, sigma, ld_sigma)) return 1;
   if (net_forward_chain(cfg, Run{kB3, cfg.d_range}, st, n, k, P, keep, sigma, ld_sigma)) return 1;
+  // a kept on-chip pass that was re-run: the re-run has rewritten every fp32 H, the backward reads bits
+  if (keep && keep_pass(n, P) && mask_launch(cfg, st, n, k, P, true)) return 1;
   hipLaunchKernelGGL(kw_range_tally, dim3(1), dim3(64), 0, st, cfg.d_range);
   return 0;
 }
@@ -1275,6 +1365,10 @@ int trunk_bwd_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chu
   t.GEP = k.GEP; t.Ci = n.Ci;
   t.M = P;
   t.range_flag = cfg.d_range;
+  if (n.onchip.keep.form) {           // the forward was kept on chip: the masks are bits (k.H[0 .. D - 2] is not read)
+    hipLaunchKernelGGL(n.onchip.keep_bwd->keep_bwd, trunk_grid(cfg, *n.onchip.keep_bwd, P), dim3(kTrunkThreads), 0, st, t, keep_masks(n, k, P));
+    return 0;
+  }
   hipLaunchKernelGGL(f.bwd, trunk_grid(cfg, f, P), dim3(kTrunkThreads), 0, st, t);
   return 0;
 }
@@ -1314,6 +1408,8 @@ int net_backward_chain(const GemmCfg& cfg, Run run, hipStream_t st, const Net& n
 int net_backward(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P) {
   if (cfg.arith != kH2 || P <= 0) return net_backward_chain(cfg, Run{cfg.arith, nullptr}, st, n, k, P);
   if (net_backward_chain(cfg, Run{kH2, nullptr}, st, n, k, P)) return 1;
+  // a forward kept on chip left bits: the re-run masks by fp32 H > 0, so H[0 .. D - 2] = 1 / 0 from the bits first
+  if (keep_pass(n, P) && mask_launch(cfg, st, n, k, P, false)) return 1;
   if (net_backward_chain(cfg, Run{kB3, cfg.d_range}, st, n, k, P)) return 1;
   hipLaunchKernelGGL(kw_range_tally, dim3(1), dim3(64), 0, st, cfg.d_range);
   return 0;
@@ -1543,6 +1639,7 @@ int nsrw_create(const NsrwConfig* cfg, nsrw_handle* out) {
     return fail("nsrw_create: out of device memory");
   }
   h->gemm_cfg.d_range = h->d_range;
+  h->gemm_cfg.keep_passes = &h->keep_passes;
   *out = reinterpret_cast<nsrw_handle>(h);
   return 0;
 }
@@ -1875,6 +1972,20 @@ int nsrw_trunk_bwd_plan(const NsrwNet* net, int flags, NsrwTrunkPlan* plan_out) 
   OnchipPlan p;
   if (plan_entry("nsrw_trunk_bwd_plan", net, plan_out, flags, &p)) return -1;
   *plan_out = as_trunk_plan(p.bwd);
+  return 0;
+}
+
+int nsrw_trunk_keep_plan(const NsrwNet* net, int flags, NsrwTrunkPlan* plan_out) {
+  OnchipPlan p;
+  const int rc = plan_entry("nsrw_trunk_keep_plan", net, plan_out, flags, &p);
+  if (rc == 0) *plan_out = as_trunk_plan(p.keep);
+  return rc;
+}
+
+int nsrw_keep_status(nsrw_handle hh, unsigned long long* passes_onchip) {
+  Handle* h = reinterpret_cast<Handle*>(hh);
+  if (!h || !passes_onchip) return fail("nsrw_keep_status: null argument");
+  *passes_onchip = h->keep_passes;
   return 0;
 }
 

@@ -87,6 +87,8 @@ SIGNATURES = {
     "nsrw_trunk_plan": (C.c_int, [C.POINTER(NsrwNet), C.c_int, C.POINTER(NsrwTrunkPlan)]),
     "nsrw_heads_plan": (C.c_int, [C.POINTER(NsrwNet), C.c_int, C.POINTER(NsrwHeadsPlan)]),
     "nsrw_trunk_bwd_plan": (C.c_int, [C.POINTER(NsrwNet), C.c_int, C.POINTER(NsrwTrunkPlan)]),
+    "nsrw_trunk_keep_plan": (C.c_int, [C.POINTER(NsrwNet), C.c_int, C.POINTER(NsrwTrunkPlan)]),
+    "nsrw_keep_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "nsrw_debug_bounds_status": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
     "nsrw_range_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "nsrw_sample_pdf": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -97,10 +99,12 @@ SIGNATURES = {
 FLAG_WHITE_BKGD, FLAG_LINDISP, FLAG_MLP_BF16X3, FLAG_MLP_F16X2, FLAG_TRUNK_ONCHIP, FLAG_HEADS_ONCHIP = 1, 2, 4, 8, 16, 32
 FLAG_TRUNK_WIDE = 64
 FLAG_TRUNK_BWD = 128
+FLAG_TRUNK_KEEP = 256
 MLPS = ("bf16x3", "fp32", "f16x2")
 TRUNKS = ("layers", "onchip")
 HEADS = ("layers", "onchip")
 TRUNK_BWDS = ("layers", "onchip")
+TRUNK_KEEPS = ("layers", "onchip")
 TRUNK_WIDTHS = (128, 256)       # the largest padded width trunk="onchip" takes: 256 adds the wide form (FLAG_TRUNK_WIDE)
 
 DEFAULT_MLP = "f16x2"           # r06: the fused default kernel's arithmetic; same parity bounds as the fp32 MFMAs and bf16x3 (tests/test_gpu_wide.py
@@ -161,6 +165,9 @@ KNOBS = (
     _Knob("trunk_bwd", "NSR_WIDE_TRUNK_BWD", TRUNK_BWDS, "onchip", FLAG_TRUNK_BWD, _ONCHIP,
           "trunk_bwd=\"onchip\" serves the networks the on-chip trunk serves: it needs mlp=\"f16x2\" and "
           "trunk=\"onchip\" (got mlp=%(mlp)r, trunk=%(trunk)r)"),
+    _Knob("trunk_keep", "NSR_WIDE_TRUNK_KEEP", TRUNK_KEEPS, "onchip", FLAG_TRUNK_KEEP, dict(_ONCHIP, trunk_bwd="onchip"),
+          "trunk_keep=\"onchip\" leaves the relu masks as bits for the on-chip backward trunk: it needs mlp=\"f16x2\", "
+          "trunk=\"onchip\" and trunk_bwd=\"onchip\" (got mlp=%(mlp)r, trunk=%(trunk)r, trunk_bwd=%(trunk_bwd)r)"),
 )
 
 
@@ -191,16 +198,17 @@ def resolve_knobs(mlp, wishes, environ):
     return got
 
 
-def _trunk_flags(trunk, trunk_width=128, heads="layers", trunk_bwd="layers"):
+def _trunk_flags(trunk, trunk_width=128, heads="layers", trunk_bwd="layers", trunk_keep="layers"):
     """the NsrwConfig.flags of the knobs (a trunk_width of 256 says nothing without trunk="onchip")"""
     if trunk_width not in TRUNK_WIDTHS:
         raise ValueError("trunk_width must be one of %s (got %r)" % (TRUNK_WIDTHS, trunk_width))
-    got = dict(trunk=trunk, heads=heads, trunk_width=trunk_width if trunk == "onchip" else 128, trunk_bwd=trunk_bwd)
+    got = dict(trunk=trunk, heads=heads, trunk_width=trunk_width if trunk == "onchip" else 128, trunk_bwd=trunk_bwd,
+               trunk_keep=trunk_keep)
     return sum(k.flag for k in KNOBS if got[k.name] == k.on)
 
 
 def _plan(entry, struct, fields, net_or_sd, flags):
-    """one of the library's three plan entries (diagnostic; no device, no handle) on a network -- an NsrwNet or a state dict"""
+    """one of the library's four plan entries (diagnostic; no device, no handle) on a network -- an NsrwNet or a state dict"""
     lib = load()
     net = net_or_sd if isinstance(net_or_sd, NsrwNet) else describe(net_or_sd)[0]
     plan = struct()
@@ -234,6 +242,15 @@ def trunk_bwd_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", trunk_bwd="onchip
     dict(mode="layers", reason=...) for a GEMM launch per product."""
     return _plan("nsrw_trunk_bwd_plan", NsrwTrunkPlan, ("nj", "tile_rows", "lds_bytes"), net_or_sd,
                  _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width, trunk_bwd=trunk_bwd))
+
+
+def trunk_keep_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", trunk_bwd="onchip", trunk_keep="onchip", heads="layers", trunk_width=128):
+    """nsrw_trunk_keep_plan (diagnostic; no device, no handle): how a handle of arithmetic `mlp` created with these knobs runs the
+    f16x2 pass of a forward that keeps its activations for a backward, on a network (an NsrwNet or a state dict) --
+    dict(mode="onchip", nj, tile_rows, lds_bytes) for the one kept launch of csrc/nsr_wide_trunk.inc (the relu masks as bits, read by
+    the bit-reading backward launch), or dict(mode="layers", reason=...) for a GEMM launch per layer with fp32 activations kept."""
+    return _plan("nsrw_trunk_keep_plan", NsrwTrunkPlan, ("nj", "tile_rows", "lds_bytes"), net_or_sd,
+                 _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width, heads, trunk_bwd, trunk_keep))
 
 
 def _np(v):
@@ -350,7 +367,7 @@ class WideModel:
     schedule = "layers"
 
     def __init__(self, sd_coarse, sd_fine=None, device=None, n_importance=128, white_bkgd=False, lindisp=False, n_samples=64,
-                 mlp=None, trunk=None, heads=None, trunk_width=None, trunk_bwd=None):
+                 mlp=None, trunk=None, heads=None, trunk_width=None, trunk_bwd=None, trunk_keep=None):
         """mlp: the arithmetic of the layer GEMMs -- "bf16x3" (bf16 MFMAs on three-way split fp32 operands, fp32-grade results at
         2.67x the matrix-pipe rate: csrc/nsr_wide_gemm.inc), "fp32" (fp32 MFMAs, the strict mode) or "f16x2" (fp16 MFMAs with
         two-piece operands -- the fused default kernel's arithmetic; a network pass that leaves fp16's range is re-run on bf16x3
@@ -371,12 +388,19 @@ class WideModel:
         trunk="onchip" only: a network the on-chip trunk takes in its 128-row form runs that chain in ONE launch behind the
         backward's head launches, the gradient between two layers in LDS -- the same bits; the kept forward pass and any other
         network stay layer by layer: trunk_bwd_plan); default $NSR_WIDE_TRUNK_BWD (which handles that cannot honour it ignore, while
-        an explicit trunk_bwd="onchip" there raises), else "layers"."""
+        an explicit trunk_bwd="onchip" there raises), else "layers".
+        trunk_keep: "layers" (a forward pass that keeps its activations for a backward runs a GEMM launch per layer and keeps fp32
+        rows) or "onchip" (with trunk="onchip" and trunk_bwd="onchip" only: on a network whose backward trunk is on chip the f16x2
+        pass of such a forward is ONE launch too -- with heads="onchip" the heads behind it -- and keeps the relu masks as one bit per
+        (point, unit), which the on-chip backward reads -- the same bits; the workspace of a gradient call grows by W / 8 bytes per
+        point and kept layer: trunk_keep_plan, keep_status); default $NSR_WIDE_TRUNK_KEEP (which handles that cannot honour it
+        ignore, while an explicit trunk_keep="onchip" there raises), else "layers"."""
         mlp = mlp or os.environ.get("NSR_WIDE_MLP") or DEFAULT_MLP
         if mlp not in MLPS:
             raise ValueError("mlp must be one of %s (got %r)" % (MLPS, mlp))
-        knobs = resolve_knobs(mlp, dict(trunk=trunk, heads=heads, trunk_width=trunk_width, trunk_bwd=trunk_bwd), os.environ)
-        self.trunk, self.heads, self.trunk_width, self.trunk_bwd = (knobs[k.name] for k in KNOBS)
+        knobs = resolve_knobs(mlp, dict(trunk=trunk, heads=heads, trunk_width=trunk_width, trunk_bwd=trunk_bwd, trunk_keep=trunk_keep),
+                              os.environ)
+        self.trunk, self.heads, self.trunk_width, self.trunk_bwd, self.trunk_keep = (knobs[k.name] for k in KNOBS)
         self.mlp = "layered-" + mlp
         if not torch.cuda.is_available():
             raise _lib.NsrError("no HIP device visible: the render path has no CPU fallback")
@@ -399,7 +423,7 @@ class WideModel:
         self._ws_need = {}                                # (rays, grad) -> bytes one chunk of that many rays needs
         cfg = NsrwConfig(self.device.index, n_samples, n_importance,
                          (FLAG_WHITE_BKGD if white_bkgd else 0) | (FLAG_LINDISP if lindisp else 0) |
-                         _mlp_flags(mlp) | _trunk_flags(self.trunk, self.trunk_width, self.heads, self.trunk_bwd))
+                         _mlp_flags(mlp) | _trunk_flags(self.trunk, self.trunk_width, self.heads, self.trunk_bwd, self.trunk_keep))
         h = C.c_void_p()
         check(self.lib.nsrw_create(C.byref(cfg), C.byref(h)))
         self.h = h
@@ -624,6 +648,12 @@ class WideModel:
             check(self.lib.nsrw_range_status(self.h, C.byref(a), C.byref(b)))
             out["passes"], out["passes_rerun"] = int(a.value), int(b.value)
         return out
+
+    def keep_status(self):
+        """nsrw_keep_status: `passes_onchip` kept forward passes launched on chip so far (trunk_keep="onchip" handles; 0 elsewhere)"""
+        n = C.c_ulonglong()
+        check(self.lib.nsrw_keep_status(self.h, C.byref(n)))
+        return dict(passes_onchip=int(n.value))
 
     def debug_bounds_status(self):
         """(built_with_checks, first_bad_line): see nsrw_debug_bounds_status / `make debug`."""

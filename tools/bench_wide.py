@@ -5,13 +5,15 @@ quoted against; for those the issued fraction of the fp16 / bf16 peak is reporte
 
     python tools/bench_wide.py [--hw 400] [--cases ycbv,w512,d10w384,small] [--steps 3] [--trunk layers|onchip|both]
                                   [--heads layers|onchip|both] [--trunk-width 128|256|both] [--trunk-bwd layers|onchip|both]
+                                  [--trunk-keep layers|onchip|both]
 
 --trunk (f16x2): the pts_linears layer by layer (the default), in the one-launch on-chip trunk (csrc/nsr_wide_trunk.inc), or both in
 turn on the same rays in one process -- the comparison DESIGN.md 8 quotes.  --heads (with the on-chip trunk): the heads one launch
 each behind the trunk (the default), inside the trunk's launch, or both in turn.  --trunk-width (with the on-chip trunk): the largest
 padded width it takes, 128 (the default), 256 (the wide form: the 8 x 160 .. 8 x 256 cases run their trunk on chip) or both in turn.
 --trunk-bwd (with the on-chip trunk): the gradient call's input-gradient chain a launch per product (the default), in the one-launch
-backward trunk, or both in turn.
+backward trunk, or both in turn.  --trunk-keep (with the on-chip backward trunk): the gradient call's kept forward a launch per layer
+with fp32 activations kept (the default), in the one kept launch that leaves the relu masks as bits, or both in turn.
 """
 import argparse
 import json
@@ -82,24 +84,27 @@ def main():
     ap.add_argument("--heads", default="layers", choices=("layers", "onchip", "both"))
     ap.add_argument("--trunk-width", default="128", choices=("128", "256", "both"))
     ap.add_argument("--trunk-bwd", default="layers", choices=("layers", "onchip", "both"))
+    ap.add_argument("--trunk-keep", default="layers", choices=("layers", "onchip", "both"))
     a = ap.parse_args()
     trunks = ("layers", "onchip") if a.trunk == "both" else (a.trunk,)
     widths = (128, 256) if a.trunk_width == "both" else (int(a.trunk_width),)
     bwds = ("layers", "onchip") if a.trunk_bwd == "both" else (a.trunk_bwd,)
-    # (trunk, heads, trunk width, backward trunk): the heads and the backward trunk run on chip, and the trunk takes widths up to 256,
-    # behind the on-chip trunk only
-    modes = [(t, h, w, b) for t in trunks for h in (("layers", "onchip") if a.heads == "both" else (a.heads,)) for w in widths
-             for b in bwds if t == "onchip" or (h == "layers" and w == widths[0] and b == "layers")]
+    keeps = ("layers", "onchip") if a.trunk_keep == "both" else (a.trunk_keep,)
+    # (trunk, heads, trunk width, backward trunk, kept forward): the heads and the backward trunk run on chip, and the trunk takes
+    # widths up to 256, behind the on-chip trunk only; the kept forward runs on chip behind the on-chip backward trunk only
+    modes = [(t, h, w, b, k) for t in trunks for h in (("layers", "onchip") if a.heads == "both" else (a.heads,)) for w in widths
+             for b in bwds for k in keeps
+             if (t == "onchip" or (h == "layers" and w == widths[0] and b == "layers")) and (b == "onchip" or k == "layers")]
     if not modes or (a.trunk == "layers" and a.trunk_width != "128"):
-        ap.error("--heads onchip, --trunk-width 256 and --trunk-bwd onchip need --trunk onchip or both")
+        ap.error("--heads onchip, --trunk-width 256 and --trunk-bwd onchip need --trunk onchip or both; --trunk-keep onchip needs --trunk-bwd onchip or both")
     K = S.scaled_K(400.0 / a.hw)
     pose = S.sweep_poses(1, seed=0)[0]
     out = {}
-    for name, trunk, heads, width, bwd in [(c, t, h, w, b) for c in a.cases.split(",") for t, h, w, b in modes]:
+    for name, trunk, heads, width, bwd, keep in [(c, t, h, w, b, k) for c in a.cases.split(",") for t, h, w, b, k in modes]:
         D, W, L, Lv, skips, ns, ni = CASES[name]
         sd = net_sd(D, W, L, Lv, skips, 1)
         m = WideModel(sd, sd, n_samples=ns, n_importance=ni, mlp=a.mlp, trunk=trunk, heads=heads,
-                      trunk_width=width if trunk == "onchip" else None, trunk_bwd=bwd)
+                      trunk_width=width if trunk == "onchip" else None, trunk_bwd=bwd, trunk_keep=keep)
         n = a.hw * a.hw
         evals = n * (ns + ns + ni)
         flop = evals * flop_per_point(sd)
@@ -109,7 +114,7 @@ def main():
         cot = torch.randn(n, 3, device=m.device)      # of the backward depends on it: 8 x 64 re-ran one or two passes per call unseeded)
         res = {"network": "%d x %d, skips %s, %d + %d samples" % (D, W, skips, ns, ni), "rays": n,
                "flop_per_point": flop_per_point(sd), "mlp": m.mlp, "trunk": m.trunk, "heads": m.heads,
-               "trunk_width": m.trunk_width, "trunk_bwd": m.trunk_bwd}
+               "trunk_width": m.trunk_width, "trunk_bwd": m.trunk_bwd, "trunk_keep": m.trunk_keep}
         for what in ("forward",) + (() if a.no_grad else ("forward+input-gradient",)):
             ms = []
             ps = None
@@ -138,9 +143,11 @@ def main():
                 res[what]["Mray_samples_per_s"] = round(n * (ns + ni) / t / 1e3, 2)
         if m.mlp.endswith("f16x2"):
             res["range_status"] = m.range_status()
+            res["keep_status"] = m.keep_status()
         key = name + (":" + trunk if a.trunk == "both" else "") + (":heads-" + heads if a.heads == "both" else "") + \
             (":width-%d" % width if a.trunk_width == "both" and trunk == "onchip" else "") + \
-            (":bwd-" + bwd if a.trunk_bwd == "both" and trunk == "onchip" else "")
+            (":bwd-" + bwd if a.trunk_bwd == "both" and trunk == "onchip" else "") + \
+            (":keep-" + keep if a.trunk_keep == "both" and bwd == "onchip" else "")
         out[key] = res
         print(key, json.dumps(res), flush=True)
         m.close()
