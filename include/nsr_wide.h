@@ -82,6 +82,15 @@ enum { NSRW_FLAG_TRUNK_KEEP = 256 };/* opt-in, with NSRW_FLAG_TRUNK_BWD only (ns
                                       * of a gradient call grows by the masks, W / 8 bytes per point and kept layer
                                       * (nsrw_trunk_keep_plan says which networks; nsrw_keep_status counts the passes). */
 
+enum { NSRW_FLAG_STAGES_WAVE = 512 };   /* opt-in, any arithmetic, needs nothing beside it */
+                                     /* The render and gradient calls run the per-ray stages between the network passes -- compositing
+                                      * (RN:343-387), resampling (RH:199-243) and the compositing backward -- with ONE WAVE per ray
+                                      * (csrc/nsr_wide_stages.inc) instead of one thread: consecutive lanes at consecutive samples,
+                                      * every sum and product whose order the reference fixes on one lane in that order -- the same
+                                      * IEEE operations on the same values in the same order, so the same bits in every output, tap
+                                      * and gradient.  The workspace and the chunking are unchanged (nsrw_stage_plan says how a stage
+                                      * runs; nsrw_stages_status counts the launches).  The stage entry nsrw_sample_pdf stays as it is. */
+
 typedef struct NsrwConfig {
   int32_t device;
   int32_t n_samples;                 /* N_samples (RN:439): 3 .. NSRW_MAX_SAMPLES -- sample_pdf needs an interior weight; nsrw_create refuses less */
@@ -262,6 +271,21 @@ int nsrw_trunk_keep_plan(const NsrwNet* net, int flags, NsrwTrunkPlan* plan_out)
  * enqueued; 0 on every other handle).  Does not synchronise. */
 int nsrw_keep_status(nsrw_handle h, unsigned long long* passes_onchip);
 
+/* DIAGNOSTIC; needs no device and no handle.  How a handle created with `flags` runs one per-ray stage of a pass with `samples`
+ * samples per ray -- N_samples for the coarse pass, N_samples + N_importance for the fine one; NSRW_STAGE_SAMPLE_PDF: N_samples, and
+ * n_importance samples to draw (n_importance is read for that stage only).  wave = 0: the thread-per-ray kernel (rays_per_group =
+ * lds_bytes = 0) with the reason.  wave = 1 (NSRW_FLAG_STAGES_WAVE): the wave-per-ray kernel, lds_bytes of dynamic LDS per RAY --
+ * composite 20 samples, sample_pdf 4 (3 samples + n_importance), composite_bwd 16 samples -- and rays_per_group waves per workgroup,
+ * the largest of 4, 2, 1 with rays_per_group * lds_bytes <= 65536.  Returns 0, or -1 for an argument out of range. */
+enum { NSRW_STAGE_COMPOSITE = 0, NSRW_STAGE_SAMPLE_PDF = 1, NSRW_STAGE_COMPOSITE_BWD = 2 };
+typedef struct { int wave; int rays_per_group; int lds_bytes; char reason[96]; } NsrwStagePlan;
+int nsrw_stage_plan(int stage, int samples, int n_importance, int flags, NsrwStagePlan* plan_out);
+
+/* NSRW_FLAG_STAGES_WAVE handles: wave-per-ray stage launches enqueued so far (counted on the host; 0 on every other handle) -- per
+ * chunk of rays two or three for a forward (compositing per pass, resampling), one more per pass whose backward runs.  Does not
+ * synchronise. */
+int nsrw_stages_status(nsrw_handle h, unsigned long long* launches_wave);
+
 /* DIAGNOSTIC; needs no device and no handle.  How a handle created with `flags` runs the heads of `net` behind its pts_linears
  * (DESIGN.md 8): onchip = 1 -- inside the trunk's one launch, kw_trunk_h2<nj, true>, with lds_bytes of LDS per workgroup -- or
  * onchip = 0 (a GEMM launch per head; lds_bytes = 0) with the reason.  Returns 0, or -1 for an invalid network description. */
@@ -275,7 +299,7 @@ int nsrw_heads_plan(const NsrwNet* net, int flags, NsrwHeadsPlan* plan_out);
  * recorded, not trapped.  built_with_checks: 1 in that build, 0 in the product library; first_bad_line: 0 = clean, else the source
  * line of the (highest) failed check -- nsr_wide.hip's line, 100000 + the line of nsr_wide_gemm.inc, or 200000 + the line of
  * nsr_wide_trunk.inc (all forms of kw_trunk_h2, the wide one included, kw_trunk_bwd_h2, kw_keep_h2, kw_keep_bwd_h2 and the two mask
- * kernels).  Synchronises the device. */
+ * kernels), or 300000 + the line of nsr_wide_stages.inc (the three wave-per-ray stage kernels).  Synchronises the device. */
 int nsrw_debug_bounds_status(int* built_with_checks, unsigned* first_bad_line);
 
 #ifdef __cplusplus

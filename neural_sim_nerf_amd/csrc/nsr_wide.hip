@@ -43,7 +43,7 @@ __device__ unsigned g_wide_violation = 0u;
 #else
 #define NSRW_CHECK(cond) do { } while (0)
 #endif
-#define NSRW_FILE_TAG 0            /* nsr_wide.hip: the line itself; nsr_wide_gemm.inc: 100000 + line, nsr_wide_trunk.inc: 200000 + line (they set their own tags) */
+#define NSRW_FILE_TAG 0            /* nsr_wide.hip: the line itself; nsr_wide_gemm.inc: 100000 + line, nsr_wide_trunk.inc: 200000 + line, nsr_wide_stages.inc: 300000 + line (they set their own tags) */
 
 // ------------------------------------------------------------------------------------------------------------------------
 // GEMM: C[m][n] = epi( sum_k A[m][k] * Wt[n][k] + bias[n] ), A = [A1 | A2] (two row-major segments: the skip concatenation
@@ -494,6 +494,11 @@ __global__ void __launch_bounds__(256) kw_composite_bwd(const CompositeBwdArgs a
   a.gnorm[r] = (float)dn;
 }
 
+// the same three stages with one wave per ray (NSRW_FLAG_STAGES_WAVE)
+#include "nsr_wide_stages.inc"
+#undef NSRW_FILE_TAG
+#define NSRW_FILE_TAG 0
+
 __device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
   int lo = __double2loint(v), hi = __double2hiint(v);
   lo = __shfl_xor(lo, mask);
@@ -787,6 +792,7 @@ struct Handle {
   bool timed = false;
   int chunks = 0;
   unsigned long long keep_passes = 0;     // nsrw_keep_status
+  unsigned long long stage_launches = 0;  // nsrw_stages_status
 };
 
 // appends a packed [Np][Kp] matrix to `img`; get(n, k) is consulted for n < rows, k < cols only
@@ -1415,6 +1421,40 @@ int net_backward(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& 
   return 0;
 }
 
+// How a handle created with `flags` runs one per-ray stage of a pass with `samples` samples per ray (SAMPLE_PDF: the coarse pass's,
+// and n_importance samples to draw) -- pure host arithmetic, no HIP call (nsrw_stage_plan exposes it).  Without
+// NSRW_FLAG_STAGES_WAVE: the thread-per-ray kernel.  With it: the wave-per-ray kernel of nsr_wide_stages.inc, the LDS one ray takes
+// there (stage_lds_*), and as many rays per workgroup -- 4, 2 or 1 -- as 64 KiB hold; a ray that does not fit stays on the thread
+// kernel.  ("Per-ray stages".)
+NsrwStagePlan stage_plan(int stage, int samples, int n_importance, int flags) {
+  NsrwStagePlan p{};
+  auto thread_form = [&](const char* why) { p = NsrwStagePlan{}; snprintf(p.reason, sizeof p.reason, "%s", why); };
+  if (!(flags & NSRW_FLAG_STAGES_WAVE)) { thread_form("NSRW_FLAG_STAGES_WAVE not set"); return p; }
+  const long long lds = stage == NSRW_STAGE_COMPOSITE    ? (long long)stage_lds_composite(samples)
+                        : stage == NSRW_STAGE_SAMPLE_PDF ? (long long)stage_lds_sample_pdf(samples, n_importance)
+                                                         : (long long)stage_lds_composite_bwd(samples);
+  for (int rays : {4, 2, 1})
+    if (lds * rays <= kStageLdsMax) {
+      p.wave = 1; p.rays_per_group = rays; p.lds_bytes = (int)lds;
+      return p;
+    }
+  thread_form("one ray's samples do not fit 64 KiB of LDS");
+  return p;
+}
+
+// One stage launch over Rc rays: the kernel, the grid and the LDS from the plan
+template <typename Args>
+void stage_launch(Handle* h, int stage, void (*threads)(Args), void (*wave)(Args), const Args& args, int Rc, int samples, hipStream_t st) {
+  const NsrwStagePlan p = stage_plan(stage, samples, h->cfg.n_importance, h->cfg.flags);
+  if (!p.wave) {
+    hipLaunchKernelGGL(threads, dim3((unsigned)((Rc + 255) / 256)), dim3(256), 0, st, args);
+    return;
+  }
+  const int rpg = p.rays_per_group;
+  hipLaunchKernelGGL(wave, dim3((unsigned)((Rc + rpg - 1) / rpg)), dim3(64 * rpg), (size_t)p.lds_bytes * rpg, st, args);
+  ++h->stage_launches;
+}
+
 // the timing events are skipped while the stream is being captured into a hipGraph (an event recorded under capture cannot be
 // waited on by nsrw_last_ms); everything else a launch call does -- kernels, memset / memcpy nodes -- is capturable
 bool capturing(hipStream_t st) {
@@ -1514,7 +1554,7 @@ int render_impl(Handle* h, const float* ro, const float* rd, long long n, float 
       if (!n0.d.use_viewdirs) { ca.raw_src = k.RAW; ca.ld_raw = 32; }
     }
     if (ca.rgb_map && !(ca.disp && ca.acc)) return fail("nsrw: rgb / disp / acc outputs of a pass must be given together");
-    hipLaunchKernelGGL(kw_composite, dim3(rb), dim3(256), 0, st, ca);
+    stage_launch<CompositeArgs>(h, NSRW_STAGE_COMPOSITE, kw_composite, kw_composite_wave, ca, Rc, S0, st);
     if (o.d_weights0) NSRW_HIP(hipMemcpyAsync(o.d_weights0 + r0 * S0, k.w0, (size_t)Rc * S0 * 4, hipMemcpyDeviceToDevice, st));
     const float* z_last = k.z0;
     const float* noise_last = ca.noise;
@@ -1524,7 +1564,7 @@ int render_impl(Handle* h, const float* ro, const float* rd, long long n, float 
       pa.R = Rc; pa.S0 = S0; pa.NI = NI; pa.z0 = k.z0; pa.w0 = k.w0; pa.u_tab = h->d_tab + S0;
       pa.u_rays = e.d_u ? e.d_u + r0 * NI : nullptr; pa.pdf = k.pdf; pa.cdf = k.cdf; pa.zs = k.zs;
       pa.inds = o.d_inds ? o.d_inds + r0 * NI : nullptr; pa.z_std = o.d_z_std ? o.d_z_std + r0 : nullptr;
-      hipLaunchKernelGGL(kw_sample_pdf, dim3(rb), dim3(256), 0, st, pa);
+      stage_launch<PdfArgs>(h, NSRW_STAGE_SAMPLE_PDF, kw_sample_pdf, kw_sample_pdf_wave, pa, Rc, S0, st);
       if (o.d_z_samples) NSRW_HIP(hipMemcpyAsync(o.d_z_samples + r0 * NI, k.zs, (size_t)Rc * NI * 4, hipMemcpyDeviceToDevice, st));
       hipLaunchKernelGGL(kw_sort, dim3((unsigned)Rc), dim3(64), (size_t)S1 * sizeof(float), st, k.z0, k.zs, S0, NI, k.zf);
       if (e.d_z_fine)          // given depths (constants of the gradient, RN:475) replace the resampled ones for the fine pass
@@ -1543,7 +1583,7 @@ int render_impl(Handle* h, const float* ro, const float* rd, long long n, float 
         if (!last.d.use_viewdirs) { cf.raw_src = k.RAW; cf.ld_raw = 32; }
       }
       if (cf.rgb_map && !(cf.disp && cf.acc)) return fail("nsrw: rgb / disp / acc outputs of a pass must be given together");
-      hipLaunchKernelGGL(kw_composite, dim3(rb), dim3(256), 0, st, cf);
+      stage_launch<CompositeArgs>(h, NSRW_STAGE_COMPOSITE, kw_composite, kw_composite_wave, cf, Rc, S1, st);
       z_last = k.zf;
       noise_last = cf.noise;
     }
@@ -1559,7 +1599,7 @@ int render_impl(Handle* h, const float* ro, const float* rd, long long n, float 
       cb.grad_rgb = g_rgb ? g_rgb + r0 * 3 : nullptr; cb.grad_disp = g_disp ? g_disp + r0 : nullptr;
       cb.grad_acc = g_acc ? g_acc + r0 : nullptr;
       cb.scr_a = k.scr_a; cb.scr_t = k.scr_t; cb.gscale = h->gemm_cfg.arith == kH2 ? k.gscale : nullptr;
-      hipLaunchKernelGGL(kw_composite_bwd, dim3(rb), dim3(256), 0, st, cb);
+      stage_launch<CompositeBwdArgs>(h, NSRW_STAGE_COMPOSITE_BWD, kw_composite_bwd, kw_composite_bwd_wave, cb, Rc, S, st);
       if (net_backward(h->gemm_cfg, st, nn, k, P)) return 1;
       EmbedBwdArgs eb{};
       eb.R = Rc; eb.S = S; eb.L = nn.d.multires; eb.Lv = nn.d.multires_views;
@@ -1986,6 +2026,26 @@ int nsrw_keep_status(nsrw_handle hh, unsigned long long* passes_onchip) {
   Handle* h = reinterpret_cast<Handle*>(hh);
   if (!h || !passes_onchip) return fail("nsrw_keep_status: null argument");
   *passes_onchip = h->keep_passes;
+  return 0;
+}
+
+int nsrw_stage_plan(int stage, int samples, int n_importance, int flags, NsrwStagePlan* plan_out) {
+  if (!plan_out) { fail("nsrw_stage_plan: null argument"); return -1; }
+  const bool pdf = stage == NSRW_STAGE_SAMPLE_PDF;
+  if (stage != NSRW_STAGE_COMPOSITE && !pdf && stage != NSRW_STAGE_COMPOSITE_BWD) { fail("nsrw_stage_plan: no such stage"); return -1; }
+  if (samples < 3 || samples > (pdf ? NSRW_MAX_SAMPLES : 2 * NSRW_MAX_SAMPLES) || (pdf && (n_importance < 1 || n_importance > NSRW_MAX_SAMPLES))) {
+    fail("nsrw_stage_plan: 3.." + std::to_string(2 * NSRW_MAX_SAMPLES) + " samples of a pass (NSRW_STAGE_SAMPLE_PDF: 3.." +
+         std::to_string(NSRW_MAX_SAMPLES) + " coarse samples and 1.." + std::to_string(NSRW_MAX_SAMPLES) + " to draw)");
+    return -1;
+  }
+  *plan_out = stage_plan(stage, samples, pdf ? n_importance : 0, flags);
+  return 0;
+}
+
+int nsrw_stages_status(nsrw_handle hh, unsigned long long* launches_wave) {
+  Handle* h = reinterpret_cast<Handle*>(hh);
+  if (!h || !launches_wave) return fail("nsrw_stages_status: null argument");
+  *launches_wave = h->stage_launches;
   return 0;
 }
 

@@ -57,6 +57,10 @@ class NsrwHeadsPlan(C.Structure):
     _fields_ = [("onchip", C.c_int32), ("lds_bytes", C.c_int32), ("reason", C.c_char * 64)]
 
 
+class NsrwStagePlan(C.Structure):
+    _fields_ = [("wave", C.c_int), ("rays_per_group", C.c_int), ("lds_bytes", C.c_int), ("reason", C.c_char * 96)]
+
+
 # render()'s differentiable outputs (RN:488-494) -> the field of NsrwCotangents and the shape of one ray's cotangent
 COTANGENTS = {"rgb_map": ("d_rgb", 3), "disp_map": ("d_disp", 1), "acc_map": ("d_acc", 1),
               "rgb0": ("d_rgb0", 3), "disp0": ("d_disp0", 1), "acc0": ("d_acc0", 1)}
@@ -89,6 +93,8 @@ SIGNATURES = {
     "nsrw_trunk_bwd_plan": (C.c_int, [C.POINTER(NsrwNet), C.c_int, C.POINTER(NsrwTrunkPlan)]),
     "nsrw_trunk_keep_plan": (C.c_int, [C.POINTER(NsrwNet), C.c_int, C.POINTER(NsrwTrunkPlan)]),
     "nsrw_keep_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
+    "nsrw_stage_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(NsrwStagePlan)]),
+    "nsrw_stages_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "nsrw_debug_bounds_status": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
     "nsrw_range_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "nsrw_sample_pdf": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -100,11 +106,15 @@ FLAG_WHITE_BKGD, FLAG_LINDISP, FLAG_MLP_BF16X3, FLAG_MLP_F16X2, FLAG_TRUNK_ONCHI
 FLAG_TRUNK_WIDE = 64
 FLAG_TRUNK_BWD = 128
 FLAG_TRUNK_KEEP = 256
+FLAG_STAGES_WAVE = 512
 MLPS = ("bf16x3", "fp32", "f16x2")
 TRUNKS = ("layers", "onchip")
 HEADS = ("layers", "onchip")
 TRUNK_BWDS = ("layers", "onchip")
 TRUNK_KEEPS = ("layers", "onchip")
+STAGES = ("threads", "wave")    # the per-ray stages between the network passes: one thread per ray, or one wave (FLAG_STAGES_WAVE)
+STAGE_COMPOSITE, STAGE_SAMPLE_PDF, STAGE_COMPOSITE_BWD = 0, 1, 2
+STAGE_IDS = {"composite": STAGE_COMPOSITE, "sample_pdf": STAGE_SAMPLE_PDF, "composite_bwd": STAGE_COMPOSITE_BWD}
 TRUNK_WIDTHS = (128, 256)       # the largest padded width trunk="onchip" takes: 256 adds the wide form (FLAG_TRUNK_WIDE)
 
 DEFAULT_MLP = "f16x2"           # r06: the fused default kernel's arithmetic; same parity bounds as the fp32 MFMAs and bf16x3 (tests/test_gpu_wide.py
@@ -205,6 +215,29 @@ def _trunk_flags(trunk, trunk_width=128, heads="layers", trunk_bwd="layers", tru
     got = dict(trunk=trunk, heads=heads, trunk_width=trunk_width if trunk == "onchip" else 128, trunk_bwd=trunk_bwd,
                trunk_keep=trunk_keep)
     return sum(k.flag for k in KNOBS if got[k.name] == k.on)
+
+
+def resolve_stages(wish, environ):
+    """How a handle runs its per-ray stages: the caller's wish, else $NSR_WIDE_STAGES, else "threads".  Not an on-chip form -- any
+    arithmetic takes it and it needs no other knob -- so it is not a row of KNOBS.  Pure: no device, no library."""
+    v = wish or environ.get("NSR_WIDE_STAGES") or STAGES[0]
+    if v not in STAGES:
+        raise ValueError("stages must be one of %s (got %r)" % (STAGES, v))
+    return v
+
+
+def stage_plan(stage, samples, n_importance=0, flags=FLAG_STAGES_WAVE):
+    """nsrw_stage_plan (diagnostic; no device, no handle): how a handle created with `flags` runs the per-ray stage `stage`
+    (STAGE_COMPOSITE / STAGE_SAMPLE_PDF / STAGE_COMPOSITE_BWD, or its name in STAGE_IDS) of a pass with `samples` samples per ray
+    (sample_pdf: N_samples, drawing n_importance) -- dict(mode="wave", rays_per_group, lds_bytes: per ray) for the wave-per-ray
+    kernel of csrc/nsr_wide_stages.inc, or dict(mode="threads", reason=...) for the thread-per-ray kernel."""
+    lib = load()
+    plan = NsrwStagePlan()
+    if lib.nsrw_stage_plan(int(STAGE_IDS.get(stage, stage)), int(samples), int(n_importance), int(flags), C.byref(plan)) != 0:
+        raise _lib.NsrError(lib.nsrw_last_error().decode("utf-8", "replace"))
+    if plan.wave:
+        return dict(mode="wave", rays_per_group=int(plan.rays_per_group), lds_bytes=int(plan.lds_bytes))
+    return dict(mode="threads", reason=plan.reason.decode("utf-8", "replace"))
 
 
 def _plan(entry, struct, fields, net_or_sd, flags):
@@ -367,7 +400,7 @@ class WideModel:
     schedule = "layers"
 
     def __init__(self, sd_coarse, sd_fine=None, device=None, n_importance=128, white_bkgd=False, lindisp=False, n_samples=64,
-                 mlp=None, trunk=None, heads=None, trunk_width=None, trunk_bwd=None, trunk_keep=None):
+                 mlp=None, trunk=None, heads=None, trunk_width=None, trunk_bwd=None, trunk_keep=None, stages=None):
         """mlp: the arithmetic of the layer GEMMs -- "bf16x3" (bf16 MFMAs on three-way split fp32 operands, fp32-grade results at
         2.67x the matrix-pipe rate: csrc/nsr_wide_gemm.inc), "fp32" (fp32 MFMAs, the strict mode) or "f16x2" (fp16 MFMAs with
         two-piece operands -- the fused default kernel's arithmetic; a network pass that leaves fp16's range is re-run on bf16x3
@@ -394,13 +427,18 @@ class WideModel:
         pass of such a forward is ONE launch too -- with heads="onchip" the heads behind it -- and keeps the relu masks as one bit per
         (point, unit), which the on-chip backward reads -- the same bits; the workspace of a gradient call grows by W / 8 bytes per
         point and kept layer: trunk_keep_plan, keep_status); default $NSR_WIDE_TRUNK_KEEP (which handles that cannot honour it
-        ignore, while an explicit trunk_keep="onchip" there raises), else "layers"."""
+        ignore, while an explicit trunk_keep="onchip" there raises), else "layers".
+        stages: "threads" (compositing, resampling and the compositing backward run one thread per ray) or "wave" (one wave per
+        ray: consecutive lanes at consecutive samples, every ordered sum on one lane in its order -- the same bits; any arithmetic,
+        any other knob; the workspace and the chunks are the same: stage_plan, stages_status); default $NSR_WIDE_STAGES, else
+        "threads"."""
         mlp = mlp or os.environ.get("NSR_WIDE_MLP") or DEFAULT_MLP
         if mlp not in MLPS:
             raise ValueError("mlp must be one of %s (got %r)" % (MLPS, mlp))
         knobs = resolve_knobs(mlp, dict(trunk=trunk, heads=heads, trunk_width=trunk_width, trunk_bwd=trunk_bwd, trunk_keep=trunk_keep),
                               os.environ)
         self.trunk, self.heads, self.trunk_width, self.trunk_bwd, self.trunk_keep = (knobs[k.name] for k in KNOBS)
+        self.stages = resolve_stages(stages, os.environ)
         self.mlp = "layered-" + mlp
         if not torch.cuda.is_available():
             raise _lib.NsrError("no HIP device visible: the render path has no CPU fallback")
@@ -423,7 +461,8 @@ class WideModel:
         self._ws_need = {}                                # (rays, grad) -> bytes one chunk of that many rays needs
         cfg = NsrwConfig(self.device.index, n_samples, n_importance,
                          (FLAG_WHITE_BKGD if white_bkgd else 0) | (FLAG_LINDISP if lindisp else 0) |
-                         _mlp_flags(mlp) | _trunk_flags(self.trunk, self.trunk_width, self.heads, self.trunk_bwd, self.trunk_keep))
+                         _mlp_flags(mlp) | _trunk_flags(self.trunk, self.trunk_width, self.heads, self.trunk_bwd, self.trunk_keep) |
+                         (FLAG_STAGES_WAVE if self.stages == "wave" else 0))
         h = C.c_void_p()
         check(self.lib.nsrw_create(C.byref(cfg), C.byref(h)))
         self.h = h
@@ -654,6 +693,12 @@ class WideModel:
         n = C.c_ulonglong()
         check(self.lib.nsrw_keep_status(self.h, C.byref(n)))
         return dict(passes_onchip=int(n.value))
+
+    def stages_status(self):
+        """nsrw_stages_status: `launches_wave` wave-per-ray stage launches enqueued so far (stages="wave" handles; 0 elsewhere)"""
+        n = C.c_ulonglong()
+        check(self.lib.nsrw_stages_status(self.h, C.byref(n)))
+        return dict(launches_wave=int(n.value))
 
     def debug_bounds_status(self):
         """(built_with_checks, first_bad_line): see nsrw_debug_bounds_status / `make debug`."""

@@ -5,7 +5,7 @@ quoted against; for those the issued fraction of the fp16 / bf16 peak is reporte
 
     python tools/bench_wide.py [--hw 400] [--cases ycbv,w512,d10w384,small] [--steps 3] [--trunk layers|onchip|both]
                                   [--heads layers|onchip|both] [--trunk-width 128|256|both] [--trunk-bwd layers|onchip|both]
-                                  [--trunk-keep layers|onchip|both]
+                                  [--trunk-keep layers|onchip|both] [--stages threads|wave|both] [--cotangents rgb|all]
 
 --trunk (f16x2): the pts_linears layer by layer (the default), in the one-launch on-chip trunk (csrc/nsr_wide_trunk.inc), or both in
 turn on the same rays in one process -- the comparison DESIGN.md 8 quotes.  --heads (with the on-chip trunk): the heads one launch
@@ -13,7 +13,10 @@ each behind the trunk (the default), inside the trunk's launch, or both in turn.
 padded width it takes, 128 (the default), 256 (the wide form: the 8 x 160 .. 8 x 256 cases run their trunk on chip) or both in turn.
 --trunk-bwd (with the on-chip trunk): the gradient call's input-gradient chain a launch per product (the default), in the one-launch
 backward trunk, or both in turn.  --trunk-keep (with the on-chip backward trunk): the gradient call's kept forward a launch per layer
-with fp32 activations kept (the default), in the one kept launch that leaves the relu masks as bits, or both in turn.
+with fp32 activations kept (the default), in the one kept launch that leaves the relu masks as bits, or both in turn.  --stages (any
+arithmetic): compositing, resampling and the compositing backward one thread per ray (the default), one wave per ray
+(csrc/nsr_wide_stages.inc), or both in turn on the same rays in one process.  --cotangents: the gradient call differentiates rgb_map
+(the default) or all six outputs (the coarse pass's backward too).
 """
 import argparse
 import json
@@ -45,6 +48,8 @@ CASES = {
     # the widths the wide on-chip trunk adds (--trunk-width 256), next to ycbv (8 x 256 at 64 + 128) and d8w192
     "ycbv48": (8, 256, 10, 4, [4], 48, 100),       # sample counts without a fused kernel
     "d8w160": (8, 160, 10, 4, [4], 64, 128),
+    # the per-ray stages at their largest share: a small network, three coarse samples, 512 importance samples
+    "s3n512": (4, 128, 6, 2, [1], 3, 512),
 }
 
 
@@ -85,26 +90,29 @@ def main():
     ap.add_argument("--trunk-width", default="128", choices=("128", "256", "both"))
     ap.add_argument("--trunk-bwd", default="layers", choices=("layers", "onchip", "both"))
     ap.add_argument("--trunk-keep", default="layers", choices=("layers", "onchip", "both"))
+    ap.add_argument("--stages", default="threads", choices=("threads", "wave", "both"))
+    ap.add_argument("--cotangents", default="rgb", choices=("rgb", "all"))
     a = ap.parse_args()
     trunks = ("layers", "onchip") if a.trunk == "both" else (a.trunk,)
     widths = (128, 256) if a.trunk_width == "both" else (int(a.trunk_width),)
     bwds = ("layers", "onchip") if a.trunk_bwd == "both" else (a.trunk_bwd,)
     keeps = ("layers", "onchip") if a.trunk_keep == "both" else (a.trunk_keep,)
+    stages_modes = ("threads", "wave") if a.stages == "both" else (a.stages,)
     # (trunk, heads, trunk width, backward trunk, kept forward): the heads and the backward trunk run on chip, and the trunk takes
     # widths up to 256, behind the on-chip trunk only; the kept forward runs on chip behind the on-chip backward trunk only
-    modes = [(t, h, w, b, k) for t in trunks for h in (("layers", "onchip") if a.heads == "both" else (a.heads,)) for w in widths
-             for b in bwds for k in keeps
+    modes = [(t, h, w, b, k, s) for t in trunks for h in (("layers", "onchip") if a.heads == "both" else (a.heads,)) for w in widths
+             for b in bwds for k in keeps for s in stages_modes
              if (t == "onchip" or (h == "layers" and w == widths[0] and b == "layers")) and (b == "onchip" or k == "layers")]
     if not modes or (a.trunk == "layers" and a.trunk_width != "128"):
         ap.error("--heads onchip, --trunk-width 256 and --trunk-bwd onchip need --trunk onchip or both; --trunk-keep onchip needs --trunk-bwd onchip or both")
     K = S.scaled_K(400.0 / a.hw)
     pose = S.sweep_poses(1, seed=0)[0]
     out = {}
-    for name, trunk, heads, width, bwd, keep in [(c, t, h, w, b, k) for c in a.cases.split(",") for t, h, w, b, k in modes]:
+    for name, trunk, heads, width, bwd, keep, stages in [(c,) + mode for c in a.cases.split(",") for mode in modes]:
         D, W, L, Lv, skips, ns, ni = CASES[name]
         sd = net_sd(D, W, L, Lv, skips, 1)
         m = WideModel(sd, sd, n_samples=ns, n_importance=ni, mlp=a.mlp, trunk=trunk, heads=heads,
-                      trunk_width=width if trunk == "onchip" else None, trunk_bwd=bwd, trunk_keep=keep)
+                      trunk_width=width if trunk == "onchip" else None, trunk_bwd=bwd, trunk_keep=keep, stages=stages)
         n = a.hw * a.hw
         evals = n * (ns + ns + ni)
         flop = evals * flop_per_point(sd)
@@ -112,9 +120,15 @@ def main():
         ro, rd = ro.reshape(-1, 3), rd.reshape(-1, 3)
         torch.manual_seed(0)              # every mode and every process differentiates the same cotangent (a borderline f16x2 re-run
         cot = torch.randn(n, 3, device=m.device)      # of the backward depends on it: 8 x 64 re-ran one or two passes per call unseeded)
+        cots = None
+        if a.cotangents == "all":
+            cots = {k: torch.randn((n, 3) if k in ("rgb_map", "rgb0") else (n,), device=m.device) for k in
+                    ("disp_map", "acc_map", "rgb0", "disp0", "acc0")}
+            cots["rgb_map"] = cot
         res = {"network": "%d x %d, skips %s, %d + %d samples" % (D, W, skips, ns, ni), "rays": n,
                "flop_per_point": flop_per_point(sd), "mlp": m.mlp, "trunk": m.trunk, "heads": m.heads,
-               "trunk_width": m.trunk_width, "trunk_bwd": m.trunk_bwd, "trunk_keep": m.trunk_keep}
+               "trunk_width": m.trunk_width, "trunk_bwd": m.trunk_bwd, "trunk_keep": m.trunk_keep, "stages": m.stages,
+               "cotangents": a.cotangents}
         for what in ("forward",) + (() if a.no_grad else ("forward+input-gradient",)):
             ms = []
             ps = None
@@ -124,6 +138,8 @@ def main():
                     ps.start()
                 if what == "forward":
                     m.render_rays(ro, rd, S.YCBV_NEAR, S.YCBV_FAR)
+                elif cots:
+                    m.render_rays_vjp(ro, rd, S.YCBV_NEAR, S.YCBV_FAR, cotangents=cots)
                 else:
                     m.render_rays_vjp(ro, rd, S.YCBV_NEAR, S.YCBV_FAR, cot)
                 t, chunks = m.last_kernel_ms()
@@ -131,6 +147,8 @@ def main():
             power = ps.stop() if ps else None
             t = float(np.median(ms[1:]))
             f = flop if what == "forward" else flop + n * (ns + ni) * flop_per_point(sd)     # + the fine pass's transposed GEMMs
+            if what != "forward" and cots:
+                f += 2 * n * ns * flop_per_point(sd)                                          # + the coarse pass again, and its transposed GEMMs
             res[what] = {"ms_per_view": round(t, 2), "ms_min_max": [round(min(ms[1:]), 2), round(max(ms[1:]), 2)], "chunks": chunks, "workspace_GB": round(m.workspace_bytes / 2 ** 30, 2),
                          "algorithmic_TFLOPs": round(f / t / 1e9, 1), "frac_of_fp32_mfma_peak": round(f / t / 1e9 / PEAK_FP32_MFMA, 3)}
             if m.mlp.endswith("bf16x3"):       # six bf16 piece products per product: ceiling 2500 / 6 TFLOP/s of algorithmic work
@@ -147,7 +165,8 @@ def main():
         key = name + (":" + trunk if a.trunk == "both" else "") + (":heads-" + heads if a.heads == "both" else "") + \
             (":width-%d" % width if a.trunk_width == "both" and trunk == "onchip" else "") + \
             (":bwd-" + bwd if a.trunk_bwd == "both" and trunk == "onchip" else "") + \
-            (":keep-" + keep if a.trunk_keep == "both" and bwd == "onchip" else "")
+            (":keep-" + keep if a.trunk_keep == "both" and bwd == "onchip" else "") + \
+            (":stages-" + stages if a.stages == "both" else "")
         out[key] = res
         print(key, json.dumps(res), flush=True)
         m.close()
