@@ -91,6 +91,16 @@ enum { NSRW_FLAG_STAGES_WAVE = 512 };   /* opt-in, any arithmetic, needs nothing
                                       * and gradient.  The workspace and the chunking are unchanged (nsrw_stage_plan says how a stage
                                       * runs; nsrw_stages_status counts the launches).  The stage entry nsrw_sample_pdf stays as it is. */
 
+enum { NSRW_FLAG_TRUNK_RERUN = (1 << 10) }; /* opt-in, with NSRW_FLAG_TRUNK_ONCHIP only (nsrw_create refuses it without, hence without NSRW_FLAG_MLP_F16X2) */
+                                     /* On a network whose trunk runs on chip in its 128-row form, the conditional bf16x3 re-run of a
+                                      * forward pass that keeps no activations runs its pts_linears as ONE launch too (kw_rerun_b3:
+                                      * the bf16x3 arithmetic of the per-layer chain per output element, activations in LDS, tiles of
+                                      * 128 points up to a padded width of 64 and of 64 points at 96 and 128), which returns at once
+                                      * unless the f16x2 pass left fp16's range; the re-run's heads stay a conditional launch each
+                                      * behind it.  The same bits.  The re-run of a kept pass and of a backward, and the networks of
+                                      * the wide form, stay layer by layer (nsrw_trunk_rerun_plan says which networks;
+                                      * nsrw_rerun_status counts the launches).  The workspace is unchanged. */
+
 typedef struct NsrwConfig {
   int32_t device;
   int32_t n_samples;                 /* N_samples (RN:439): 3 .. NSRW_MAX_SAMPLES -- sample_pdf needs an interior weight; nsrw_create refuses less */
@@ -270,6 +280,17 @@ int nsrw_trunk_keep_plan(const NsrwNet* net, int flags, NsrwTrunkPlan* plan_out)
 /* NSRW_FLAG_TRUNK_KEEP handles: kept forward passes launched on chip so far (kw_keep_h2 launches, counted on the host as they are
  * enqueued; 0 on every other handle).  Does not synchronise. */
 int nsrw_keep_status(nsrw_handle h, unsigned long long* passes_onchip);
+
+/* DIAGNOSTIC; needs no device and no handle.  How a handle created with `flags` runs the pts_linears of the conditional bf16x3
+ * re-run of a forward pass of `net` that keeps no activations: onchip = 1 -- one kw_rerun_b3<nj, wave rows> launch over
+ * tiles of tile_rows points with lds_bytes of LDS per workgroup, nj = 1: tile_rows = 128 (4 wave rows x 2 wave columns, padded width
+ * <= 64) or 64 (2 x 4, padded width 96 or 128) -- or onchip = 0 (a conditional GEMM launch per layer; nj = tile_rows = lds_bytes = 0)
+ * with the reason.  Returns 0, or -1 for an invalid network description. */
+int nsrw_trunk_rerun_plan(const NsrwNet* net, int flags, NsrwTrunkPlan* plan_out);
+
+/* NSRW_FLAG_TRUNK_RERUN handles: kw_rerun_b3 launches enqueued so far, whether or not their pass left the range (counted on the host as
+ * they are enqueued; 0 on every other handle).  Does not synchronise. */
+int nsrw_rerun_status(nsrw_handle h, unsigned long long* launches_onchip);
 
 /* DIAGNOSTIC; needs no device and no handle.  How a handle created with `flags` runs one per-ray stage of a pass with `samples`
  * samples per ray -- N_samples for the coarse pass, N_samples + N_importance for the fine one; NSRW_STAGE_SAMPLE_PDF: N_samples, and

@@ -682,14 +682,15 @@ struct Mat {                 // one packed matrix [Np][K1p + K2p] and its (nulla
 // What a handle runs on chip for one network (onchip_plan): per decision the kernel form that does it -- a row of kTrunkForms -- or
 // why there is none.  trunk: the pts_linears in one launch; heads: the heads behind them in that launch (its form replaces the
 // trunk's); bwd: the layer loop of the input-gradient chain in one launch; keep: the f16x2 pass of a forward that keeps its
-// activations in one launch (with it, keep_bwd: the backward launch that reads the masks as bits instead of bwd's).
+// activations in one launch (with it, keep_bwd: the backward launch that reads the masks as bits instead of bwd's); rerun: the
+// pts_linears of the conditional bf16x3 re-run of a forward pass that keeps nothing, in one launch.
 struct TrunkForm;
 struct Onchip {
   const TrunkForm* form = nullptr;
   const char* why = "";
 };
 struct OnchipPlan {
-  Onchip trunk, heads, bwd, keep;
+  Onchip trunk, heads, bwd, keep, rerun;
   const TrunkForm* keep_bwd = nullptr;
   const TrunkForm* forward() const { return heads.form ? heads.form : trunk.form; }      // the form of the forward's launch
 };
@@ -706,8 +707,8 @@ struct Net {
   size_t img_bytes[kArithSlots] = {};
   std::vector<Mat> fwd;               // pts_linears
   OnchipPlan onchip;                  // onchip_plan: which kernels of nsr_wide_trunk.inc run this network's passes, if any
-  TrunkLayer* dTrunk = nullptr;       // device: trunk_table -- the rows of the forward launch, the backward launch's behind them
-  int trunk_rows = 0, trunk_bwd_rows = 0;
+  TrunkLayer* dTrunk = nullptr;       // device: trunk_table -- the rows of the forward launch, the backward launch's behind them,
+  int trunk_rows = 0, trunk_bwd_rows = 0, trunk_rerun_rows = 0;       // the bf16x3 re-run launch's behind those
   Mat fa, al, hv, rgb, out;           // feature_linear, alpha_linear, views_linears.0, rgb_linear / output_linear
   std::vector<Mat> bwd_h, bwd_e;      // per pts layer: G W_i[:, hidden part] (i >= 1), G W_i[:, encoding part] (layer 0, skip layers)
   Mat b_rgb, b_feat, b_ed, b_head;
@@ -768,8 +769,9 @@ struct GemmCfg {
   int cus = 256;                        // compute units of the handle's device
   Arith arith = kF32;                   // NsrwConfig::flags: NSRW_FLAG_MLP_F16X2 -> kH2, NSRW_FLAG_MLP_BF16X3 -> kB3, neither -> kF32
   int tile_wm = 4;                      // 256-column tiles with 256 rows / 512 threads (4) or 128 rows / 256 threads (2: NSRW_B3_WM = 2)
-  int flags = 0;                        // NsrwConfig::flags (onchip_plan reads the arithmetic and the five on-chip flags)
+  int flags = 0;                        // NsrwConfig::flags (onchip_plan reads the arithmetic and the six on-chip flags)
   unsigned long long* keep_passes = nullptr;      // host: kept forward passes launched on chip so far (Handle::keep_passes)
+  unsigned long long* rerun_launches = nullptr;   // host: kw_rerun_b3 launches enqueued so far (Handle::rerun_launches)
   unsigned* d_range = nullptr;          // device: [0] flag of the f16x2 pass in flight, [1] passes run, [2] passes re-run on bf16x3
 };
 
@@ -792,6 +794,7 @@ struct Handle {
   bool timed = false;
   int chunks = 0;
   unsigned long long keep_passes = 0;     // nsrw_keep_status
+  unsigned long long rerun_launches = 0;  // nsrw_rerun_status
   unsigned long long stage_launches = 0;  // nsrw_stages_status
 };
 
@@ -1044,30 +1047,34 @@ typedef void (*TrunkKernel)(TrunkArgs);
 typedef void (*TrunkBwdKernel)(TrunkBwdArgs);
 typedef void (*TrunkKeepKernel)(TrunkArgs, TrunkKeepArgs);
 typedef void (*TrunkKeepBwdKernel)(TrunkBwdArgs, KeepMasks);
-enum TrunkKind { kFormFwd, kFormBwd, kFormKeep, kFormKeepBwd };
+typedef void (*TrunkRerunKernel)(TrunkArgs, const unsigned*);
+enum TrunkKind { kFormFwd, kFormBwd, kFormKeep, kFormKeepBwd, kFormRerun };
 struct TrunkForm {
-  TrunkKind kind;                       // which of the four kernels below the row has
+  TrunkKind kind;                       // which of the five kernels below the row has
   int nj, tile_rows;                    // 32-column blocks of the output one wave accumulates; points of a block
   bool heads;                           // forward rows: the heads run behind the trunk in the launch
   TrunkKernel fwd;                      // kw_trunk_h2, or
   TrunkBwdKernel bwd;                   // kw_trunk_bwd_h2, or
   TrunkKeepKernel keep;                 // kw_keep_h2, or
-  TrunkKeepBwdKernel keep_bwd;          // kw_keep_bwd_h2: exactly one of the four
+  TrunkKeepBwdKernel keep_bwd;          // kw_keep_bwd_h2, or
+  TrunkRerunKernel rerun;               // kw_rerun_b3: exactly one of the five
   int lds_bytes;                        // the kernel's own (static) LDS
 };
 template <int NJ, bool HEADS, int WR = 4>
-TrunkForm trunk_fwd_form() { return {kFormFwd, NJ, trunk_rows<WR>(), HEADS, kw_trunk_h2<NJ, HEADS, WR>, nullptr, nullptr, nullptr, trunk_lds_bytes<NJ, WR>()}; }
+TrunkForm trunk_fwd_form() { return {kFormFwd, NJ, trunk_rows<WR>(), HEADS, kw_trunk_h2<NJ, HEADS, WR>, nullptr, nullptr, nullptr, nullptr, trunk_lds_bytes<NJ, WR>()}; }
 template <int NJ>
-TrunkForm trunk_bwd_form_row() { return {kFormBwd, NJ, trunk_rows<4>(), false, nullptr, kw_trunk_bwd_h2<NJ>, nullptr, nullptr, trunk_bwd_lds_bytes<NJ>()}; }
+TrunkForm trunk_bwd_form_row() { return {kFormBwd, NJ, trunk_rows<4>(), false, nullptr, kw_trunk_bwd_h2<NJ>, nullptr, nullptr, nullptr, trunk_bwd_lds_bytes<NJ>()}; }
 template <int NJ, bool HEADS>
-TrunkForm trunk_keep_form() { return {kFormKeep, NJ, trunk_rows<4>(), HEADS, nullptr, nullptr, kw_keep_h2<NJ, HEADS>, nullptr, trunk_lds_bytes<NJ, 4>()}; }
+TrunkForm trunk_keep_form() { return {kFormKeep, NJ, trunk_rows<4>(), HEADS, nullptr, nullptr, kw_keep_h2<NJ, HEADS>, nullptr, nullptr, trunk_lds_bytes<NJ, 4>()}; }
 template <int NJ>
-TrunkForm trunk_keep_bwd_form() { return {kFormKeepBwd, NJ, trunk_rows<4>(), false, nullptr, nullptr, nullptr, kw_keep_bwd_h2<NJ>, trunk_bwd_lds_bytes<NJ>()}; }
+TrunkForm trunk_keep_bwd_form() { return {kFormKeepBwd, NJ, trunk_rows<4>(), false, nullptr, nullptr, nullptr, kw_keep_bwd_h2<NJ>, nullptr, trunk_bwd_lds_bytes<NJ>()}; }
+template <int NJ, int WR>
+TrunkForm trunk_rerun_form() { return {kFormRerun, NJ, trunk_rows<WR>(), false, nullptr, nullptr, nullptr, nullptr, kw_rerun_b3<NJ, WR>, trunk_lds_bytes<NJ, WR, 3>()}; }
 // (in this order: the order of instantiation is the order of the kernels in the code object)
 const TrunkForm kTrunkForms[] = {trunk_fwd_form<1, true>(), trunk_fwd_form<2, true>(), trunk_fwd_form<1, false>(), trunk_fwd_form<2, false>(),
                                  trunk_fwd_form<2, false, 2>(), trunk_bwd_form_row<1>(), trunk_bwd_form_row<2>(),
                                  trunk_keep_form<1, true>(), trunk_keep_form<2, true>(), trunk_keep_form<1, false>(), trunk_keep_form<2, false>(),
-                                 trunk_keep_bwd_form<1>(), trunk_keep_bwd_form<2>()};
+                                 trunk_keep_bwd_form<1>(), trunk_keep_bwd_form<2>(), trunk_rerun_form<1, 4>(), trunk_rerun_form<1, 2>()};
 constexpr int kTrunkThreads = 512;
 
 const TrunkForm* find_trunk_form(TrunkKind kind, int nj, int tile_rows, bool heads) {
@@ -1077,8 +1084,8 @@ const TrunkForm* find_trunk_form(TrunkKind kind, int nj, int tile_rows, bool hea
 }
 
 // What a handle created with `flags` runs on chip for the network `d` -- pure host arithmetic, no HIP call (nsrw_trunk_plan,
-// nsrw_heads_plan, nsrw_trunk_bwd_plan and nsrw_trunk_keep_plan expose its four decisions; nsrw_upload_network keeps it).  DESIGN.md 8
-// has the table.
+// nsrw_heads_plan, nsrw_trunk_bwd_plan, nsrw_trunk_keep_plan and nsrw_trunk_rerun_plan expose its five decisions; nsrw_upload_network
+// keeps it).  DESIGN.md 8 has the table.
 //   trunk: an f16x2 handle with NSRW_FLAG_TRUNK_ONCHIP, at least two layers, and a packed width of at most 128, so that the whole N
 //     extent is one tile of 128 rows (NJ = 1: <= 64 columns, NJ = 2: 128); with NSRW_FLAG_TRUNK_WIDE on top a packed width of
 //     160 .. 256 too: the wide form, tiles of 64 rows by 256 columns.
@@ -1088,6 +1095,8 @@ const TrunkForm* find_trunk_form(TrunkKind kind, int nj, int tile_rows, bool hea
 //     NJ covers the wider of the two outputs: the hidden width and the encoding.
 //   keep: NSRW_FLAG_TRUNK_KEEP and a backward trunk on chip (hence f16x2, the 128-row forward form and at least two layers).  The
 //     forward form the heads decision chooses, with the trunk's NJ and LDS; the backward launch becomes the bit-reading one of bwd's NJ.
+//   rerun: NSRW_FLAG_TRUNK_RERUN and a trunk on chip in its 128-row form.  Three bf16 pieces take more LDS than two fp16 ones: a
+//     packed width of at most 64 keeps tiles of 128 rows, 96 and 128 take tiles of 64 rows by 128 columns; one column block a wave.
 OnchipPlan onchip_plan(const NsrwNet& d, int flags) {
   OnchipPlan p;
   auto decide = [](Onchip& c, const char* why, TrunkKind kind, int nj, int tile_rows, bool heads) {
@@ -1095,7 +1104,7 @@ OnchipPlan onchip_plan(const NsrwNet& d, int flags) {
     c.why = why ? why : "";
   };
   if (!check_net(d).empty()) {
-    p.trunk.why = p.heads.why = p.bwd.why = p.keep.why = "invalid network";
+    p.trunk.why = p.heads.why = p.bwd.why = p.keep.why = p.rerun.why = "invalid network";
     return p;
   }
   const int Wp = pad32(d.W), Ci = pad32(3 + 6 * d.multires), narrow = trunk_rows<4>();
@@ -1133,6 +1142,12 @@ OnchipPlan onchip_plan(const NsrwNet& d, int flags) {
     p.keep.form = nullptr;
     p.keep.why = "internal error: form not compiled";
   }
+  decide(p.rerun,
+         !(flags & NSRW_FLAG_TRUNK_RERUN) ? "NSRW_FLAG_TRUNK_RERUN not set"
+         : !p.trunk.form                  ? "the trunk is not on chip"
+         : !narrow_trunk                  ? "padded width above 128: the wide trunk has no re-run form"
+                                          : nullptr,
+         kFormRerun, 1, Wp <= 64 ? trunk_rows<4>() : trunk_rows<2>(), false);
   return p;
 }
 
@@ -1152,6 +1167,8 @@ constexpr FlagNeeds kFlagNeeds[] = {
      "nsrw_create: NSRW_FLAG_TRUNK_BWD needs NSRW_FLAG_TRUNK_ONCHIP (the on-chip backward trunk serves the networks the on-chip trunk serves)"},
     {NSRW_FLAG_TRUNK_KEEP, NSRW_FLAG_TRUNK_BWD,
      "nsrw_create: NSRW_FLAG_TRUNK_KEEP needs NSRW_FLAG_TRUNK_BWD (the kept on-chip forward leaves its relu masks as bits, which only the on-chip backward trunk reads)"},
+    {NSRW_FLAG_TRUNK_RERUN, NSRW_FLAG_TRUNK_ONCHIP,
+     "nsrw_create: NSRW_FLAG_TRUNK_RERUN needs NSRW_FLAG_TRUNK_ONCHIP (the on-chip bf16x3 re-run serves the passes whose f16x2 trunk ran on chip)"},
 };
 
 // the decisions as the diagnostic entries report them (no form: every figure 0, and the reason)
@@ -1180,7 +1197,7 @@ dim3 trunk_grid(const GemmCfg& cfg, const TrunkForm& f, long long P) {
 
 // The per-row table of the on-chip launches of `n` (Net::dTrunk; launch calls only enqueue): the rows of the forward launch -- the D
 // layers, with the heads behind them where n.onchip says so -- then the backward launch's.  Empty when the trunk is not on chip.
-std::vector<TrunkLayer> trunk_table(const Net& n, int* fwd_rows, int* bwd_rows) {
+std::vector<TrunkLayer> trunk_table_h2(const Net& n, int* fwd_rows, int* bwd_rows) {
   std::vector<TrunkLayer> trunk;
   *fwd_rows = *bwd_rows = 0;
   if (!n.onchip.trunk.form) return trunk;
@@ -1228,6 +1245,22 @@ std::vector<TrunkLayer> trunk_table(const Net& n, int* fwd_rows, int* bwd_rows) 
   *bwd_rows = (int)trunk.size() - *fwd_rows;
   return trunk;
 }
+// ... and behind those rows, so that none of them moves, the bf16x3 re-run launch's (n.onchip.rerun): the forward launch's D
+// pts_linears rows once more -- the same K, the same bias -- on the bf16x3 image, without cscale, the last one to C whatever the heads do
+std::vector<TrunkLayer> trunk_table(const Net& n, int* fwd_rows, int* bwd_rows, int* rerun_rows) {
+  std::vector<TrunkLayer> trunk = trunk_table_h2(n, fwd_rows, bwd_rows);
+  *rerun_rows = 0;
+  if (!n.onchip.rerun.form) return trunk;
+  for (int i = 0; i < n.d.D; ++i) {
+    TrunkLayer t = trunk[i];
+    t.img_off = (unsigned)n.fwd[i].img[kB3];
+    t.cscale = 1.0f;
+    t.form = trunk_form(n.fwd[i].ncb, n.fwd[i].Np / 32, false, true, i + 1 < n.d.D ? kTrunkToLds : kTrunkToC);
+    trunk.push_back(t);
+  }
+  *rerun_rows = n.d.D;
+  return trunk;
+}
 
 // all D pts_linears layers over P points in ONE launch: k.E -> k.H[(D - 1) & 1], where net_forward_chain's layer loop leaves them;
 // or (the heads form) the heads too: k.E, k.ED -> k.RAW, where net_forward_chain's head launches leave them
@@ -1244,6 +1277,26 @@ void trunk_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk&
   t.M = P;
   t.range_flag = cfg.d_range;
   hipLaunchKernelGGL(f.fwd, trunk_grid(cfg, f, P), dim3(kTrunkThreads), 0, st, t);
+}
+
+// The pts_linears of the conditional bf16x3 re-run of a pass over P points that keeps nothing, in ONE launch (n.onchip.rerun): k.E ->
+// k.H[(D - 1) & 1], where the layer loop of net_forward_chain leaves them for its head launches.  Returns at once unless *run_if is set.
+bool rerun_pass(Run run, const Net& n, long long P) {
+  const TrunkForm* f = n.onchip.rerun.form;
+  return f && run.arith == kB3 && run.run_if && P > 0 && P / f->tile_rows < 0x7fffffffll;
+}
+void rerun_launch(const GemmCfg& cfg, Run run, hipStream_t st, const Net& n, const Chunk& k, long long P) {
+  const TrunkForm& f = *n.onchip.rerun.form;
+  TrunkArgs t{};
+  t.E = k.E; t.ldE = n.Ci;
+  t.img = n.dImg[kB3]; t.img_bytes = (unsigned)n.img_bytes[kB3];
+  t.bias = n.dBias; t.bias_floats = n.bias_floats;
+  t.layers = n.dTrunk + n.trunk_rows + n.trunk_bwd_rows; t.D = n.trunk_rerun_rows; t.Dt = n.d.D;
+  t.C = k.H[(n.d.D - 1) & 1]; t.Wp = n.Wp;
+  t.M = P;
+  t.range_flag = nullptr;             // (only read, as run_if)
+  hipLaunchKernelGGL(f.rerun, trunk_grid(cfg, f, P), dim3(kTrunkThreads), 0, st, t, run.run_if);
+  if (cfg.rerun_launches) ++*cfg.rerun_launches;
 }
 
 // The masks of a kept on-chip pass of `n` over P points inside k.MB, in the layout of keep_mask_word (nsr_wide_trunk.inc)
@@ -1310,7 +1363,14 @@ int net_forward_chain(const GemmCfg& cfg, Run run, hipStream_t st, const Net& n,
     }
     h = k.H[kept ? n.d.D - 1 : (n.d.D - 1) & 1];
   }
-  for (int i = 0; i < n.d.D && !onchip; ++i) {
+  // the conditional bf16x3 re-run of a pass that keeps nothing, on a network with the re-run form: one launch instead of the layer
+  // loop; its heads stay the launches below
+  const bool rerun = !keep && rerun_pass(run, n, P);
+  if (rerun) {
+    rerun_launch(cfg, run, st, n, k, P);
+    h = k.H[(n.d.D - 1) & 1];
+  }
+  for (int i = 0; i < n.d.D && !onchip && !rerun; ++i) {
     float* out = k.H[keep ? i : (i & 1)];
     int rc;
     if (i == 0) rc = gemm(cfg, run, st, n, n.fwd[0], k.E, n.Ci, nullptr, 0, out, n.Wp, n.Wp, P, kRelu);
@@ -1680,6 +1740,7 @@ int nsrw_create(const NsrwConfig* cfg, nsrw_handle* out) {
   }
   h->gemm_cfg.d_range = h->d_range;
   h->gemm_cfg.keep_passes = &h->keep_passes;
+  h->gemm_cfg.rerun_launches = &h->rerun_launches;
   *out = reinterpret_cast<nsrw_handle>(h);
   return 0;
 }
@@ -1849,7 +1910,7 @@ int nsrw_upload_network(nsrw_handle hh, int net_id, const NsrwNet* desc, const f
     if (image[a].size() >= 0x7fffffffull) return fail(std::string("nsrw_upload_network: network too large for the ") + arith_name(a) + " image");
   }
   n.onchip = onchip_plan(*desc, h->gemm_cfg.flags);
-  const std::vector<TrunkLayer> trunk = trunk_table(n, &n.trunk_rows, &n.trunk_bwd_rows);
+  const std::vector<TrunkLayer> trunk = trunk_table(n, &n.trunk_rows, &n.trunk_bwd_rows, &n.trunk_rerun_rows);
   n.bias_floats = (unsigned)bias.size();
   NSRW_DEVICE(h);
   // (every failure path below frees what this call allocated: ADVICE r05)
@@ -1985,7 +2046,7 @@ int nsrw_gemm_plan(int n_packed_rows, int n_stored_columns, int tile_wm, NsrwGem
   return count;
 }
 
-// the three views of onchip_plan: 0 and the decision, or -1 for an invalid description (nsrw_last_error says why)
+// the views of onchip_plan: 0 and the decision, or -1 for an invalid description (nsrw_last_error says why)
 static int plan_entry(const char* name, const NsrwNet* net, const void* plan_out, int flags, OnchipPlan* p) {
   if (!net || !plan_out) { fail(std::string(name) + ": null argument"); return -1; }
   const std::string why = check_net(*net);
@@ -2026,6 +2087,20 @@ int nsrw_keep_status(nsrw_handle hh, unsigned long long* passes_onchip) {
   Handle* h = reinterpret_cast<Handle*>(hh);
   if (!h || !passes_onchip) return fail("nsrw_keep_status: null argument");
   *passes_onchip = h->keep_passes;
+  return 0;
+}
+
+int nsrw_trunk_rerun_plan(const NsrwNet* net, int flags, NsrwTrunkPlan* plan_out) {
+  OnchipPlan p;
+  if (plan_entry("nsrw_trunk_rerun_plan", net, plan_out, flags, &p)) return -1;
+  *plan_out = as_trunk_plan(p.rerun);
+  return 0;
+}
+
+int nsrw_rerun_status(nsrw_handle hh, unsigned long long* launches_onchip) {
+  Handle* h = reinterpret_cast<Handle*>(hh);
+  if (!h || !launches_onchip) return fail("nsrw_rerun_status: null argument");
+  *launches_onchip = h->rerun_launches;
   return 0;
 }
 

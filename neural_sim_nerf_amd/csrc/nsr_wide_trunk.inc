@@ -3,7 +3,8 @@
 // (nsr_wide.hip), after nsr_wide_gemm.inc, whose arithmetic they restate per output element and must reproduce BIT FOR BIT
 // (tests/test_gpu_wide_trunk.py, test_gpu_wide_heads.py, test_gpu_wide_trunk_bwd.py).  Two __global__ templates, kw_trunk_h2<NJ,
 // HEADS, WR> (forward) and kw_trunk_bwd_h2<NJ> (input-gradient backward), made of ONE set of building blocks; a kernel body is a
-// prologue, the block loop, the row loop and its own epilogue.
+// prologue, the block loop, the row loop and its own epilogue.  (At the end of the file: kw_rerun_b3<NJ, WR>, the forward trunk once more
+// on the bf16x3 arithmetic, for the conditional re-run of a pass that left fp16's range; the blocks that count pieces take NP = 2 or 3.)
 //
 // The building blocks (above the kernels, each stated once):
 //   * the row table.  A launch walks a table of TrunkLayer rows (Net::dTrunk): per row the weight image, K as k16 blocks of the
@@ -121,9 +122,10 @@ constexpr int kTrunkSE = 2 * kTrunkCiMax + 16;                                  
 template <int WR = 4> constexpr int trunk_rows() { return 32 * WR; }             // points of a block
 template <int NJ, int WR = 4> constexpr int trunk_ncb() { return 8 / WR * NJ; }  // col-blocks of a block's output
 template <int NJ, int WR = 4> constexpr int trunk_sh() { return 64 * trunk_ncb<NJ, WR>() + 16; }          // ... of an activation piece image
-template <int NJ, int WR = 4> constexpr int trunk_wstage() { return trunk_ncb<NJ, WR>() * 2 * 2048; }     // one stage of weights: every col-block x 2 k16 blocks
-template <int NJ, int WR = 4> constexpr int trunk_lds_bytes() {
-  return 2 * trunk_wstage<NJ, WR>() + 2 * trunk_rows<WR>() * trunk_sh<NJ, WR>() + 2 * trunk_rows<WR>() * kTrunkSE;
+// NP: pieces per operand -- 2: f16x2, 3: bf16x3 (kw_rerun_b3); a fragment is NP KiB, a piece image row has the same bytes in either
+template <int NJ, int WR = 4, int NP = 2> constexpr int trunk_wstage() { return trunk_ncb<NJ, WR>() * 2 * NP * 1024; }     // one stage of weights: every col-block x 2 k16 blocks
+template <int NJ, int WR = 4, int NP = 2> constexpr int trunk_lds_bytes() {
+  return 2 * trunk_wstage<NJ, WR, NP>() + NP * trunk_rows<WR>() * trunk_sh<NJ, WR>() + NP * trunk_rows<WR>() * kTrunkSE;
 }
 
 typedef unsigned short __attribute__((may_alias)) u16a;
@@ -159,10 +161,11 @@ __device__ __forceinline__ constexpr int trunk_acc_row(int r, int first = 0, int
 // lanes][8 fp16] as the image holds it; wave w moves chunk w % (2 NCB) (NCB = 2: every chunk twice, the same bytes to the same place,
 // so that one wait serves all waves; NCB = 8: 16 chunks, wave w moves w and w + 8, the two k16 blocks of col-block w).  VARIES: the
 // image of a row may have fewer than NCB col-blocks (`ncb`); the chunks behind them are not moved, and no MFMA reads them.
-template <int NCB, bool VARIES, int LDS>
+// NP = 3: chunks of 3 KiB, [piece 3][64 lanes][8 bf16], three LDS-DMAs each.
+template <int NCB, bool VARIES, int NP = 2, int LDS>
 __device__ __forceinline__ void trunk_dma(const TrunkCtx<LDS>& c, const __amdgpu_buffer_rsrc_t rsrc, unsigned img_bytes, unsigned img_off, int KB,
                                           int kb0, int buf, int ncb) {
-  constexpr int kWStage = NCB * 2 * 2048;
+  constexpr int kFrag = NP * 1024, kWStage = NCB * 2 * kFrag;
 #pragma unroll
   for (int i = 0; i < (2 * NCB + 7) / 8; ++i) {
     const int u = (c.wave + 8 * i) % (2 * NCB), cb = u % NCB, kbl = u / NCB;
@@ -170,11 +173,12 @@ __device__ __forceinline__ void trunk_dma(const TrunkCtx<LDS>& c, const __amdgpu
       NSRW_CHECK(ncb >= 1 && ncb <= NCB);
       if (cb >= ncb) continue;
     }
-    char* l = c.smem() + buf * kWStage + (cb * 2 + kbl) * 2048;
-    const int soff = __builtin_amdgcn_readfirstlane((int)img_off + (cb * KB + kb0 + kbl) * 2048);
-    NSRW_CHECK(kb0 >= 0 && kb0 + kbl < KB && soff >= 0 && (unsigned)soff + 2048u <= img_bytes && (buf == 0 || buf == 1) &&
-               buf * kWStage + (cb * 2 + kbl) * 2048 + 2048 <= 2 * kWStage);
+    char* l = c.smem() + buf * kWStage + (cb * 2 + kbl) * kFrag;
+    const int soff = __builtin_amdgcn_readfirstlane((int)img_off + (cb * KB + kb0 + kbl) * kFrag);
+    NSRW_CHECK(kb0 >= 0 && kb0 + kbl < KB && soff >= 0 && (unsigned)soff + (unsigned)kFrag <= img_bytes && (buf == 0 || buf == 1) &&
+               buf * kWStage + (cb * 2 + kbl) * kFrag + kFrag <= 2 * kWStage);
     NSRW_DMA(rsrc, l, c.lane, soff, 0); NSRW_DMA(rsrc, l, c.lane, soff, 1);
+    if constexpr (NP == 3) NSRW_DMA(rsrc, l, c.lane, soff, 2);
   }
 }
 
@@ -191,39 +195,51 @@ __device__ __forceinline__ void trunk_lds_barrier() {
   asm volatile("" ::: "memory");
 }
 // the end of a kernel: no LDS-DMA may outlive the workgroup; the range flag rises when a lane has split a value outside fp16's range
+// (kw_rerun_b3, which splits nothing that has a range, takes the first half alone)
+__device__ __forceinline__ void trunk_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 template <int LDS>
 __device__ __forceinline__ void trunk_tail(const TrunkCtx<LDS>& c, float amax, unsigned* range_flag) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  trunk_drain();
   if (__builtin_amdgcn_ballot_w64(!(amax < 65504.0f)) != 0ull && c.lane == 0) atomicOr(range_flag, 1u);
 }
 
 // one stage of this wave's first NA accumulators (accumulator j = column block cb_of(j)): the A fragments at aoff (pieces pstride
 // apart), the weights of the buffer at wbuf
-template <int NA, int NJ, class CbOf, int LDS>
+// NP = 3 (bf16x3): three pieces a fragment and the six products (2,0) (1,1) (0,2) (1,0) (0,1) (0,0) on v_mfma_f32_32x32x16_bf16, gemm_split_body's
+// order at NP = 3; one stage = 12 NA MFMAs of a wave.
+template <int NA, int NP = 2, int NJ, class CbOf, int LDS>
 __device__ __forceinline__ void trunk_stage(const TrunkCtx<LDS>& c, const CbOf& cb_of, f32x16 (&acc)[NJ], int wbuf, int aoff, int pstride) {
+  constexpr int kFrag = NP * 1024;
   const char* pb = c.smem() + wbuf + c.lane * 16;
-  u32x4 fa[2][2], fb[2][NA][2];
+  u32x4 fa[2][NP], fb[2][NA][NP];
 #pragma unroll
   for (int kbl = 0; kbl < 2; ++kbl) {
 #pragma unroll
-    for (int q = 0; q < 2; ++q) fa[kbl][q] = *reinterpret_cast<const u32x4a*>(c.smem() + aoff + q * pstride + kbl * 32);
+    for (int q = 0; q < NP; ++q) fa[kbl][q] = *reinterpret_cast<const u32x4a*>(c.smem() + aoff + q * pstride + kbl * 32);
 #pragma unroll
     for (int j = 0; j < NA; ++j)
 #pragma unroll
-      for (int q = 0; q < 2; ++q) fb[kbl][j][q] = *reinterpret_cast<const u32x4a*>(pb + (cb_of(j) * 2 + kbl) * 2048 + q * 1024);
+      for (int q = 0; q < NP; ++q) fb[kbl][j][q] = *reinterpret_cast<const u32x4a*>(pb + (cb_of(j) * 2 + kbl) * kFrag + q * 1024);
   }
   // per accumulator the order of gemm_split_body: k16 blocks ascending, per block (1,0) (0,1) (0,0); the column blocks alternate
 #pragma unroll
   for (int kbl = 0; kbl < 2; ++kbl) {
+    if constexpr (NP == 3) {
+#define NSRW_B3_ROUND(PA, PB) \
+  _Pragma("unroll") for (int j = 0; j < NA; ++j) acc[j] = mfma_b3(fa[kbl][PA], fb[kbl][j][PB], acc[j]);
+      NSRW_B3_ROUND(2, 0) NSRW_B3_ROUND(1, 1) NSRW_B3_ROUND(0, 2) NSRW_B3_ROUND(1, 0) NSRW_B3_ROUND(0, 1) NSRW_B3_ROUND(0, 0)
+#undef NSRW_B3_ROUND
+    } else {
 #pragma unroll
-    for (int j = 0; j < NA; ++j) acc[j] = mfma_h2w(fa[kbl][1], fb[kbl][j][0], acc[j]);
+      for (int j = 0; j < NA; ++j) acc[j] = mfma_h2w(fa[kbl][1], fb[kbl][j][0], acc[j]);
 #pragma unroll
-    for (int j = 0; j < NA; ++j) acc[j] = mfma_h2w(fa[kbl][0], fb[kbl][j][1], acc[j]);
+      for (int j = 0; j < NA; ++j) acc[j] = mfma_h2w(fa[kbl][0], fb[kbl][j][1], acc[j]);
 #pragma unroll
-    for (int j = 0; j < NA; ++j) acc[j] = mfma_h2w(fa[kbl][0], fb[kbl][j][0], acc[j]);
+      for (int j = 0; j < NA; ++j) acc[j] = mfma_h2w(fa[kbl][0], fb[kbl][j][0], acc[j]);
+    }
   }
-  NSRW_SGB(NSRW_MASK_DSRD, 4 + 4 * NA);                                  // every fragment read of the stage ahead of its MFMAs
-  NSRW_SGB(NSRW_MASK_MFMA, 6 * NA);
+  NSRW_SGB(NSRW_MASK_DSRD, 2 * NP + 2 * NP * NA);                        // every fragment read of the stage ahead of its MFMAs
+  NSRW_SGB(NSRW_MASK_MFMA, (NP == 3 ? 12 : 6) * NA);
 }
 
 // The rows of the block at m0 of X [M, ld] (KBX k16 blocks) -> a piece image, in two steps (a kernel may put a row's stages between
@@ -246,18 +262,21 @@ __device__ __forceinline__ void trunk_rows_fetch(const TrunkCtx<LDS>& c, const f
 }
 // ... split by split8_h2 and written to the image whose fragment of this lane is at frag (TrunkCtx::frag0), pieces pstride apart,
 // rows of `stride` bytes, inside the first lds_end bytes of LDS
-template <int IT, int WC, int LDS>
+// (NP = 3: by split8_b3, which has no range and leaves amax alone)
+template <int IT, int WC, int NP = 2, int LDS>
 __device__ __forceinline__ void trunk_rows_store(const TrunkCtx<LDS>& c, int KBX, const f32x4 (&e)[IT][2], int frag, int pstride, int stride, int lds_end,
                                                  float& amax) {
 #pragma unroll
   for (int i = 0; i < IT; ++i) {
     const int kb = WC * i + c.wc;
     if (kb < KBX) {
-      u32x4 p[2];
-      split8_h2(e[i][0], e[i][1], p, amax);
-      NSRW_CHECK(kb * 32 + c.lh * 16 + 16 <= stride - 16 && frag + pstride + kb * 32 + 16 <= lds_end);
+      u32x4 p[NP];
+      if constexpr (NP == 3) split8_b3(e[i][0], e[i][1], p);
+      else split8_h2(e[i][0], e[i][1], p, amax);
+      NSRW_CHECK(kb * 32 + c.lh * 16 + 16 <= stride - 16 && frag + (NP - 1) * pstride + kb * 32 + 16 <= lds_end);
       *reinterpret_cast<u32x4a*>(c.smem() + frag + kb * 32) = p[0];
       *reinterpret_cast<u32x4a*>(c.smem() + frag + pstride + kb * 32) = p[1];
+      if constexpr (NP == 3) *reinterpret_cast<u32x4a*>(c.smem() + frag + 2 * pstride + kb * 32) = p[2];
     }
   }
 }
@@ -265,16 +284,17 @@ __device__ __forceinline__ void trunk_rows_store(const TrunkCtx<LDS>& c, int KBX
 // The in-place epilogue write of half an accumulator column: p = split8_h2 of the lane's registers 8 hf .. 8 hf + 7 of column n, packed
 // pairs (r, r + 1) -> the activation image of the <NJ, WR> layout, each half of a pair to its row as one 16-bit write (the
 // transposition), inside the first lds_end bytes of LDS.  (The split8_h2 call itself stays with the kernel's epilogue arithmetic.)
-template <int NJ, int WR, int LDS>
-__device__ __forceinline__ void trunk_write_inplace(const TrunkCtx<LDS>& c, const u32x4 (&p)[2], int hf, int n, int lds_end) {
-  constexpr int kRows = trunk_rows<WR>(), kSH = trunk_sh<NJ, WR>(), kHPiece = kRows * kSH, kHOff = 2 * trunk_wstage<NJ, WR>();
+// NP (the pieces of p: split8_b3's three) is read off the argument.
+template <int NJ, int WR, int NP, int LDS>
+__device__ __forceinline__ void trunk_write_inplace(const TrunkCtx<LDS>& c, const u32x4 (&p)[NP], int hf, int n, int lds_end) {
+  constexpr int kRows = trunk_rows<WR>(), kSH = trunk_sh<NJ, WR>(), kHPiece = kRows * kSH, kHOff = 2 * trunk_wstage<NJ, WR, NP>();
 #pragma unroll
   for (int jj = 0; jj < 4; ++jj) {
     const int row = trunk_acc_row(8 * hf + 2 * jj, 32 * c.wr, 4 * c.lh);
     const int off = kHOff + row * kSH + n * 2;
-    NSRW_CHECK(row + 1 < kRows && n * 2 + 2 <= kSH - 16 && off + kSH + kHPiece + 2 <= lds_end);
+    NSRW_CHECK(row + 1 < kRows && n * 2 + 2 <= kSH - 16 && off + kSH + (NP - 1) * kHPiece + 2 <= lds_end);
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
+    for (int q = 0; q < NP; ++q) {
       *reinterpret_cast<u16a*>(c.smem() + off + q * kHPiece) = (unsigned short)(p[q][jj] & 0xffffu);
       *reinterpret_cast<u16a*>(c.smem() + off + q * kHPiece + kSH) = (unsigned short)(p[q][jj] >> 16);
     }
@@ -952,3 +972,127 @@ __device__ __forceinline__ void mask_convert(const MaskArgs& g) {
 }
 __global__ void __launch_bounds__(256) kw_mask_pack(const MaskArgs g) { mask_convert<true>(g); }
 __global__ void __launch_bounds__(256) kw_mask_unpack(const MaskArgs g) { mask_convert<false>(g); }
+
+// ---- the bf16x3 RE-RUN of the trunk (NSRW_FLAG_TRUNK_RERUN): kw_rerun_b3<NJ, WR>, the pts_linears of the conditional bf16x3 pass that
+// follows an f16x2 pass which left fp16's range, as ONE launch in place of net_forward_chain's D kw_gemm_b3 launches.  The shape and
+// cadence of kw_trunk_h2<NJ, false, WR> -- trunk_dma one stage ahead, trunk_stage, trunk_sync, the in-place split, the last row's fp32
+// output to C (rows of Wp floats: where the per-layer chain leaves it, what its head launches read) -- on THREE bf16 pieces per
+// operand.  Per output element it restates gemm_split_body<.., NP = 3>: the accumulator from 0, the k16 blocks of [encoding | h]
+// ascending, per block (2,0) (1,1) (0,2) (1,0) (0,1) (0,0) on v_mfma_f32_32x32x16_bf16, acc + bias (no cscale), relu with NaN kept,
+// the next row's A pieces by split8_b3 (truncation pieces, exact) of that fp32 value; the weights are the image the chain's LDS-DMA
+// moves (Mat::img[kB3], [col-block][k16 block][piece 3][64 lanes][8]).  bf16x3 has fp32's range: there is no amax, and the range word
+// is only READ -- a workgroup whose *run_if is 0 returns before its first LDS-DMA or store, the contract of the chain's conditional
+// launches and of kw_mask_pack.
+//
+// Three pieces do not fit the f16x2 tile shapes into 160 KiB, so the forms are (trunk_lds_bytes<NJ, WR, 3>):
+//   Wp <= 64      <NJ = 1, WR = 4>: 128 rows x 64 columns; weights 2 x 12 288, activation 3 x 128 x 144, encoding 3 x 128 x 208 = 159 744 B
+//   Wp = 96, 128  <NJ = 1, WR = 2>:  64 rows x 128 columns, 2 x 4 waves of one column block each; 2 x 24 576 + 3 x 64 x 272 + 3 x 64 x 208 = 141 312 B
+// (128 rows x 128 columns would take 233 472 B).  The image of either width has exactly the form's column blocks (col_blocks rounds up
+// to an even count); at Wp = 96 the fourth wave column multiplies zero weights and stores nothing.
+template <int NJ, int WR>
+__global__ void __launch_bounds__(512, 1) kw_rerun_b3(const TrunkArgs g, const unsigned* run_if) {
+#ifdef __HIP_DEVICE_COMPILE__
+  static_assert(NJ == 1 && (WR == 4 || WR == 2), "one column block a wave: 4 x 2 waves on 128 rows, or 2 x 4 on 64");
+  constexpr int NP = 3, WC = 8 / WR, NCB = trunk_ncb<NJ, WR>(), kTrunkRows = trunk_rows<WR>();
+  constexpr int kWStage = trunk_wstage<NJ, WR, NP>(), kSH = trunk_sh<NJ, WR>(), kHPiece = kTrunkRows * kSH, kEPiece = kTrunkRows * kTrunkSE;
+  constexpr int kHOff = 2 * kWStage, kEOff = kHOff + NP * kHPiece, kLds = trunk_lds_bytes<NJ, WR, NP>();
+  constexpr int kKbeMax = kTrunkCiMax / 16, kEncIt = (kKbeMax + WC - 1) / WC;
+  static_assert(kEOff + NP * kEPiece == kLds && kLds <= 160 * 1024, "the three piece images behind the weight double buffer");
+  if (*run_if == 0u) return;          // the f16x2 pass stayed in range: nothing is fetched, nothing is stored
+  const TrunkCtx<kLds> c = trunk_ctx<WR, kLds>();
+  auto cb_of = [&](int j) { return c.wc * NJ + j; };
+  const int mblocks = (int)((g.M + kTrunkRows - 1) / kTrunkRows);      // (the host refuses more than 2^31 - 1 blocks)
+  if ((int)blockIdx.x >= mblocks) return;
+  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)g.img, 0, (int)g.img_bytes, 0x00020000);
+  const int KBE = g.ldE >> 4, KBH = g.Wp >> 4, ncbr = g.Wp >> 5;
+  NSRW_CHECK(KBE >= 2 && KBE <= kKbeMax && KBH >= 2 && KBH <= 2 * NCB && ncbr >= 1 && ncbr <= NCB && g.D >= 1);
+  auto dma = [&](unsigned img_off, int KB, int kb0, int b) { trunk_dma<NCB, false, NP>(c, rsrc, g.img_bytes, img_off, KB, kb0, b, NCB); };
+
+  float no_amax = 0.0f;             // (trunk_rows_store's f16x2 argument: split8_b3 has no range)
+  int buf = 0;
+  const int row_e = c.frag0(kEOff, kTrunkSE), row_h = c.frag0(kHOff, kSH);
+  {
+    const TrunkLayer l0 = g.layers[0];
+    dma(l0.img_off, l0.kbe + l0.kbh, 0, 0);
+  }
+  for (int mb = blockIdx.x; mb < mblocks; mb += gridDim.x) {
+    const long long m0 = (long long)mb * kTrunkRows;
+    {
+      f32x4 e[kEncIt][2];
+      trunk_rows_fetch<kEncIt, WC>(c, g.E, g.ldE, KBE, m0, g.M, e);
+      trunk_rows_store<kEncIt, WC, NP>(c, KBE, e, row_e, kEPiece, kTrunkSE, kLds, no_amax);
+    }
+    trunk_sync();                   // the encodings are written (and, in the first block, the first stage of weights has landed)
+    for (int li = 0; li < g.D; ++li) {
+      const TrunkLayer L = g.layers[li];
+      const int ln = li + 1 < g.D ? li + 1 : 0;                       // behind the last row: layer 0 of the next block
+      const unsigned img_next = g.layers[ln].img_off;
+      const int kb_next = g.layers[ln].kbe + g.layers[ln].kbh;
+      const int KB = L.kbe + L.kbh, nst = KB >> 1;
+      NSRW_CHECK((L.kbe == 0 || L.kbe == KBE) && (L.kbh == 0 || L.kbh == KBH) && KB >= 2 && (KB & 1) == 0 &&
+                 trunk_form_ncb(L.form) == NCB && trunk_form_ncb(g.layers[ln].form) == NCB);
+      f32x16 acc[NJ];
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
+      for (int s = 0; s < nst; ++s) {
+        const bool last = s + 1 >= nst;
+        dma(last ? img_next : L.img_off, last ? kb_next : KB, last ? 0 : 2 * s + 2, buf ^ 1);
+        const int kb0 = 2 * s;
+        const bool from_e = kb0 < L.kbe;
+        const int kbr = from_e ? kb0 : kb0 - L.kbe;                      // kb0 within its image
+        const int aoff = (from_e ? row_e : row_h) + kbr * 32;
+        const int pstride = from_e ? kEPiece : kHPiece;
+        NSRW_CHECK(from_e ? (kb0 + 1 < KBE) : (kbr >= 0 && kbr + 1 < KBH));
+        NSRW_CHECK(aoff >= kHOff && aoff + (NP - 1) * pstride + 32 + 16 <= kLds);
+        trunk_stage<NJ, NP>(c, cb_of, acc, buf * kWStage, aoff, pstride);
+        trunk_sync();
+        buf ^= 1;
+      }
+      // epilogue: acc + bias, relu, split in place for the next row or (the last row) to C.  Column blocks behind Wp hold zero weights
+      // and are dropped.
+      const bool to_c = li + 1 == g.D;
+      const bool inside = m0 + kTrunkRows <= g.M;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const int cb = cb_of(j);
+        if (cb < ncbr) {
+          const int n = cb * 32 + c.lrow;
+          NSRW_CHECK(n < g.Wp && L.bias_off + (unsigned)n < g.bias_floats);
+          const float b = g.bias[L.bias_off + n];
+          f32x4 v[4];
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            float x = acc[j][r] + b;
+            x = (x < 0.0f) ? 0.0f : x;                                   // NaN stays NaN, as through torch's relu
+            v[r >> 2][r & 3] = x;
+          }
+          if (!to_c) {
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+              u32x4 p[NP];
+              split8_b3(v[2 * hf], v[2 * hf + 1], p);
+              trunk_write_inplace<NJ, WR>(c, p, hf, n, kEOff);
+            }
+          } else {
+            const long long mt = m0 + 32 * c.wr + 4 * c.lh;
+            float* cp = g.C + mt * g.Wp + n;
+            if (inside) {
+              NSRW_CHECK(mt + 27 < g.M && n < g.Wp);
+#pragma unroll
+              for (int r = 0; r < 16; ++r) cp[trunk_acc_row(r) * g.Wp] = v[r >> 2][r & 3];
+            } else {
+#pragma unroll
+              for (int r = 0; r < 16; ++r)
+                if (mt + trunk_acc_row(r) < g.M) cp[trunk_acc_row(r) * g.Wp] = v[r >> 2][r & 3];
+            }
+          }
+        }
+      }
+      if (!to_c) trunk_lds_barrier();
+    }
+  }
+  trunk_drain();                    // no LDS-DMA may outlive the workgroup
+#endif
+}

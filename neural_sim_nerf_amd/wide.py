@@ -93,6 +93,8 @@ SIGNATURES = {
     "nsrw_trunk_bwd_plan": (C.c_int, [C.POINTER(NsrwNet), C.c_int, C.POINTER(NsrwTrunkPlan)]),
     "nsrw_trunk_keep_plan": (C.c_int, [C.POINTER(NsrwNet), C.c_int, C.POINTER(NsrwTrunkPlan)]),
     "nsrw_keep_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
+    "nsrw_trunk_rerun_plan": (C.c_int, [C.POINTER(NsrwNet), C.c_int, C.POINTER(NsrwTrunkPlan)]),
+    "nsrw_rerun_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "nsrw_stage_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(NsrwStagePlan)]),
     "nsrw_stages_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "nsrw_debug_bounds_status": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
@@ -107,11 +109,13 @@ FLAG_TRUNK_WIDE = 64
 FLAG_TRUNK_BWD = 128
 FLAG_TRUNK_KEEP = 256
 FLAG_STAGES_WAVE = 512
+FLAG_TRUNK_RERUN = 1024
 MLPS = ("bf16x3", "fp32", "f16x2")
 TRUNKS = ("layers", "onchip")
 HEADS = ("layers", "onchip")
 TRUNK_BWDS = ("layers", "onchip")
 TRUNK_KEEPS = ("layers", "onchip")
+TRUNK_RERUNS = ("layers", "onchip")     # the bf16x3 re-run of a pass whose trunk ran on chip: a launch per layer, or one (FLAG_TRUNK_RERUN)
 STAGES = ("threads", "wave")    # the per-ray stages between the network passes: one thread per ray, or one wave (FLAG_STAGES_WAVE)
 STAGE_COMPOSITE, STAGE_SAMPLE_PDF, STAGE_COMPOSITE_BWD = 0, 1, 2
 STAGE_IDS = {"composite": STAGE_COMPOSITE, "sample_pdf": STAGE_SAMPLE_PDF, "composite_bwd": STAGE_COMPOSITE_BWD}
@@ -226,6 +230,23 @@ def resolve_stages(wish, environ):
     return v
 
 
+def resolve_rerun(wish, environ, mlp, trunk):
+    """How a handle of arithmetic `mlp` with trunk=`trunk` runs the bf16x3 re-run of a forward pass whose trunk ran on chip: the
+    caller's wish, else $NSR_WIDE_TRUNK_RERUN, else "layers".  Resolved beside `stages`, not a row of KNOBS.  Only an f16x2 handle
+    with trunk="onchip" has such a re-run: the environment's wish is dropped elsewhere, an explicit "onchip" there raises
+    NotImplementedError.  Pure: no device, no library."""
+    v = wish or environ.get("NSR_WIDE_TRUNK_RERUN") or TRUNK_RERUNS[0]
+    if v not in TRUNK_RERUNS:
+        raise ValueError("trunk_rerun must be one of %s (got %r)" % (TRUNK_RERUNS, v))
+    can = mlp == "f16x2" and trunk == "onchip"
+    if not wish and not can:
+        v = TRUNK_RERUNS[0]
+    if v == "onchip" and not can:
+        raise NotImplementedError("trunk_rerun=\"onchip\" re-runs a pass of the on-chip trunk: it needs mlp=\"f16x2\" and "
+                                  "trunk=\"onchip\" (got mlp=%r, trunk=%r)" % (mlp, trunk))
+    return v
+
+
 def stage_plan(stage, samples, n_importance=0, flags=FLAG_STAGES_WAVE):
     """nsrw_stage_plan (diagnostic; no device, no handle): how a handle created with `flags` runs the per-ray stage `stage`
     (STAGE_COMPOSITE / STAGE_SAMPLE_PDF / STAGE_COMPOSITE_BWD, or its name in STAGE_IDS) of a pass with `samples` samples per ray
@@ -284,6 +305,18 @@ def trunk_keep_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", trunk_bwd="onchi
     the bit-reading backward launch), or dict(mode="layers", reason=...) for a GEMM launch per layer with fp32 activations kept."""
     return _plan("nsrw_trunk_keep_plan", NsrwTrunkPlan, ("nj", "tile_rows", "lds_bytes"), net_or_sd,
                  _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width, heads, trunk_bwd, trunk_keep))
+
+
+def trunk_rerun_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", trunk_rerun="onchip", trunk_width=128):
+    """nsrw_trunk_rerun_plan (diagnostic; no device, no handle): how a handle of arithmetic `mlp` created with trunk=`trunk`,
+    trunk_rerun=`trunk_rerun`, trunk_width=`trunk_width` runs the pts_linears of the conditional bf16x3 re-run of a forward pass that
+    keeps no activations, on a network (an NsrwNet or a state dict) -- dict(mode="onchip", nj, tile_rows, lds_bytes) for the one
+    launch of kw_rerun_b3 (csrc/nsr_wide_trunk.inc; tile_rows = 128 up to a padded width of 64, 64 for 96 and 128), or
+    dict(mode="layers", reason=...) for a conditional GEMM launch per layer."""
+    if trunk_rerun not in TRUNK_RERUNS:
+        raise ValueError("trunk_rerun must be one of %s (got %r)" % (TRUNK_RERUNS, trunk_rerun))
+    return _plan("nsrw_trunk_rerun_plan", NsrwTrunkPlan, ("nj", "tile_rows", "lds_bytes"), net_or_sd,
+                 _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width) | (FLAG_TRUNK_RERUN if trunk_rerun == "onchip" else 0))
 
 
 def _np(v):
@@ -400,7 +433,8 @@ class WideModel:
     schedule = "layers"
 
     def __init__(self, sd_coarse, sd_fine=None, device=None, n_importance=128, white_bkgd=False, lindisp=False, n_samples=64,
-                 mlp=None, trunk=None, heads=None, trunk_width=None, trunk_bwd=None, trunk_keep=None, stages=None):
+                 mlp=None, trunk=None, heads=None, trunk_width=None, trunk_bwd=None, trunk_keep=None, stages=None,
+                 trunk_rerun=None):
         """mlp: the arithmetic of the layer GEMMs -- "bf16x3" (bf16 MFMAs on three-way split fp32 operands, fp32-grade results at
         2.67x the matrix-pipe rate: csrc/nsr_wide_gemm.inc), "fp32" (fp32 MFMAs, the strict mode) or "f16x2" (fp16 MFMAs with
         two-piece operands -- the fused default kernel's arithmetic; a network pass that leaves fp16's range is re-run on bf16x3
@@ -431,7 +465,13 @@ class WideModel:
         stages: "threads" (compositing, resampling and the compositing backward run one thread per ray) or "wave" (one wave per
         ray: consecutive lanes at consecutive samples, every ordered sum on one lane in its order -- the same bits; any arithmetic,
         any other knob; the workspace and the chunks are the same: stage_plan, stages_status); default $NSR_WIDE_STAGES, else
-        "threads"."""
+        "threads".
+        trunk_rerun: "layers" (the conditional bf16x3 re-run of a pass that left fp16's range is a GEMM launch per layer, fp32
+        activations through HBM) or "onchip" (with trunk="onchip" only: where the trunk ran on chip in its 128-row form and no
+        activation is kept, the re-run's pts_linears are ONE conditional launch with the activations in LDS, the heads a launch each
+        behind it -- the same bits; the re-run of a kept pass and of a backward stay layer by layer: trunk_rerun_plan,
+        rerun_status); default $NSR_WIDE_TRUNK_RERUN (which handles that cannot honour it ignore, while an explicit
+        trunk_rerun="onchip" there raises), else "layers"."""
         mlp = mlp or os.environ.get("NSR_WIDE_MLP") or DEFAULT_MLP
         if mlp not in MLPS:
             raise ValueError("mlp must be one of %s (got %r)" % (MLPS, mlp))
@@ -439,6 +479,7 @@ class WideModel:
                               os.environ)
         self.trunk, self.heads, self.trunk_width, self.trunk_bwd, self.trunk_keep = (knobs[k.name] for k in KNOBS)
         self.stages = resolve_stages(stages, os.environ)
+        self.trunk_rerun = resolve_rerun(trunk_rerun, os.environ, mlp, self.trunk)
         self.mlp = "layered-" + mlp
         if not torch.cuda.is_available():
             raise _lib.NsrError("no HIP device visible: the render path has no CPU fallback")
@@ -462,7 +503,8 @@ class WideModel:
         cfg = NsrwConfig(self.device.index, n_samples, n_importance,
                          (FLAG_WHITE_BKGD if white_bkgd else 0) | (FLAG_LINDISP if lindisp else 0) |
                          _mlp_flags(mlp) | _trunk_flags(self.trunk, self.trunk_width, self.heads, self.trunk_bwd, self.trunk_keep) |
-                         (FLAG_STAGES_WAVE if self.stages == "wave" else 0))
+                         (FLAG_STAGES_WAVE if self.stages == "wave" else 0) |
+                         (FLAG_TRUNK_RERUN if self.trunk_rerun == "onchip" else 0))
         h = C.c_void_p()
         check(self.lib.nsrw_create(C.byref(cfg), C.byref(h)))
         self.h = h
@@ -699,6 +741,13 @@ class WideModel:
         n = C.c_ulonglong()
         check(self.lib.nsrw_stages_status(self.h, C.byref(n)))
         return dict(launches_wave=int(n.value))
+
+    def rerun_status(self):
+        """nsrw_rerun_status: `launches_onchip` conditional kw_rerun_b3 launches enqueued so far, whether or not their pass left
+        the range (trunk_rerun="onchip" handles; 0 elsewhere)"""
+        n = C.c_ulonglong()
+        check(self.lib.nsrw_rerun_status(self.h, C.byref(n)))
+        return dict(launches_onchip=int(n.value))
 
     def debug_bounds_status(self):
         """(built_with_checks, first_bad_line): see nsrw_debug_bounds_status / `make debug`."""
