@@ -101,6 +101,18 @@ enum { NSRW_FLAG_TRUNK_RERUN = (1 << 10) }; /* opt-in, with NSRW_FLAG_TRUNK_ONCH
                                       * the wide form, stay layer by layer (nsrw_trunk_rerun_plan says which networks;
                                       * nsrw_rerun_status counts the launches).  The workspace is unchanged. */
 
+enum { NSRW_FLAG_EMBED_ONCHIP = (1 << 11) }; /* opt-in, with NSRW_FLAG_TRUNK_ONCHIP only (nsrw_create refuses it without, hence without NSRW_FLAG_MLP_F16X2) */
+                                     /* Wherever the f16x2 pass of a network runs as one on-chip launch -- the trunk's, the heads form's,
+                                      * the wide form's, the kept forward's -- that launch computes the position encodings of its block
+                                      * of points itself, from the rays and depths (or the points of nsrw_run_network), by the very
+                                      * functions of the encoding kernel: the kw_embed launch, its write of [P, Ci] floats and the
+                                      * trunk's read of them go.  In a heads form the direction encodings too; behind a trunk-only or
+                                      * wide launch the heads are launches that read them from memory, so kw_embed still writes them
+                                      * (alone).  The same bits.  The conditional bf16x3 re-run reads encodings from memory: an
+                                      * encoding launch conditional on the range word stands in front of it.  A pass that runs layer
+                                      * by layer is encoded as without the flag.  The workspace and the chunking are unchanged
+                                      * (nsrw_embed_plan says which encodings of which pass; nsrw_embed_status counts). */
+
 typedef struct NsrwConfig {
   int32_t device;
   int32_t n_samples;                 /* N_samples (RN:439): 3 .. NSRW_MAX_SAMPLES -- sample_pdf needs an interior weight; nsrw_create refuses less */
@@ -291,6 +303,24 @@ int nsrw_trunk_rerun_plan(const NsrwNet* net, int flags, NsrwTrunkPlan* plan_out
 /* NSRW_FLAG_TRUNK_RERUN handles: kw_rerun_b3 launches enqueued so far, whether or not their pass left the range (counted on the host as
  * they are enqueued; 0 on every other handle).  Does not synchronise. */
 int nsrw_rerun_status(nsrw_handle h, unsigned long long* launches_onchip);
+
+/* DIAGNOSTIC; needs no device and no handle.  Where a handle created with `flags` computes the encodings of a pass of `net`
+ * -- kept = 0: a pass that keeps no activations, kept = 1: one that keeps them for a backward -- separately for the positions and for
+ * the directions: onchip = 1 -- inside the pass's one f16x2 launch -- or 0 (the kw_embed launch writes them) with the reason.  The
+ * positions go on chip with any on-chip form of the pass, the directions with a heads form.  Returns 0, or -1 for an invalid network
+ * description. */
+typedef struct NsrwEmbedPlan {
+  int32_t positions_onchip, directions_onchip;
+  char positions_reason[64], directions_reason[64];
+} NsrwEmbedPlan;
+int nsrw_embed_plan(const NsrwNet* net, int flags, int kept, NsrwEmbedPlan* plan_out);
+
+/* Counted on the host as enqueued, on every handle: passes_onchip network passes whose f16x2 launch computed its position encodings
+ * itself (NSRW_FLAG_EMBED_ONCHIP handles; 0 elsewhere), embed_launches unconditional kw_embed launches (whole, or the direction
+ * encodings alone), embed_launches_conditional kw_embed launches conditional on the range word in front of a bf16x3 re-run (one per
+ * pass counted in passes_onchip).  Does not synchronise. */
+int nsrw_embed_status(nsrw_handle h, unsigned long long* passes_onchip, unsigned long long* embed_launches,
+                      unsigned long long* embed_launches_conditional);
 
 /* DIAGNOSTIC; needs no device and no handle.  How a handle created with `flags` runs one per-ray stage of a pass with `samples`
  * samples per ray -- N_samples for the coarse pass, N_samples + N_importance for the fine one; NSRW_STAGE_SAMPLE_PDF: N_samples, and

@@ -46,6 +46,76 @@ __device__ unsigned g_wide_violation = 0u;
 #define NSRW_FILE_TAG 0            /* nsr_wide.hip: the line itself; nsr_wide_gemm.inc: 100000 + line, nsr_wide_trunk.inc: 200000 + line, nsr_wide_stages.inc: 300000 + line (they set their own tags) */
 
 // ------------------------------------------------------------------------------------------------------------------------
+// The encodings (ahead of the on-chip kernels, which compute them too: trunk_rows_encode of nsr_wide_trunk.inc)
+// ------------------------------------------------------------------------------------------------------------------------
+// gamma(x) (RH:18-48): sin / cos of the fp32 argument 2^l x (the scaling is exact) by sincos_enc: <= 1 ulp from the true value,
+// i.e. inside the reference's own libm error.  sin / cos of inf / NaN are NaN, as in torch.
+struct EmbedArgs {
+  const float* rays_o; const float* rays_d;   // rays form: point (r, s) = o + d z[r][s]  (RN:463, RN:478)
+  const float* z; const float* vd;            // [R,S], [R,3]
+  const float* pts; const float* dirs;        // points form (run_network): [P,3] each; used when rays_o == nullptr
+  long long P; int S;
+  int L, Lv;                                  // frequencies; Lv < 0: no direction encoding
+  float* E; int ldE;                          // [P, Ci]; nullptr: the direction encodings alone (the positions are encoded on chip)
+  float* ED; int ldED;                        // [P, Cv]
+  const unsigned* run_if;                     // nullable: the launch returns at once unless the word is set (the bf16x3 re-run's encodings)
+};
+
+// sin and cos of the fp32 argument a for the encodings.  |a| < 2^24 (every scene: 2^14 |x| < 2^24 means |x| < 1024): ONE fp64
+// range reduction -- t = a * 2 / pi has >= 24 spare bits, the split into quadrant and fraction is exact -- and the Cephes
+// single-precision minimax polynomials on [-pi / 4, pi / 4] (1 ulp), as the fused kernels' enc_trig (nsr_kernels.hip); ~30 VALU
+// for the pair where the fp64 library sincos costs several hundred (r06: kw_embed was 2-9 % of a layered render).  Beyond that,
+// and for inf / NaN: the fp64 library routine, rounded once, as before.  (In three pieces, so that a caller with many columns a lane
+// -- trunk_rows_encode -- can keep the library routine out of its unrolled path: sincos_enc itself is what it was.)
+__device__ __forceinline__ bool sincos_enc_is_fast(float a) { return fabsf(a) < 16777216.0f; }
+__device__ __forceinline__ void sincos_enc_slow(float a, float& s, float& c) {
+  double sd, cd;
+  sincos((double)a, &sd, &cd);
+  s = (float)sd; c = (float)cd;
+}
+__device__ __forceinline__ void sincos_enc_fast(float a, float& s, float& c) {
+  const double kMagic = 6755399441055744.0;                 // 1.5 * 2^52: t + kMagic holds rint(t) in its low word
+  const double t = (double)a * 0.63661977236758134308;      // a * 2 / pi
+  const double tm = t + kMagic;
+  const int n = __double2loint(tm);
+  const double f = t - (tm - kMagic);                       // [-0.5, 0.5], exact
+  const float r = (float)(f * 1.57079632679489661923);
+  const float z = r * r;
+  float ps = __builtin_fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f);
+  ps = __builtin_fmaf(ps, z, -1.6666654611e-1f);
+  ps = __builtin_fmaf(ps * z, r, r);
+  float pc = __builtin_fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f);
+  pc = __builtin_fmaf(pc, z, 4.166664568298827e-2f);
+  pc = __builtin_fmaf(pc * z, z, __builtin_fmaf(-0.5f, z, 1.0f));
+  const float vs = (n & 1) ? pc : ps, vc = (n & 1) ? ps : pc;              // sin(a) = sin(r + n pi/2), cos(a) = sin(r + (n + 1) pi/2)
+  s = __uint_as_float(__float_as_uint(vs) ^ ((unsigned)(n & 2) << 30));
+  c = __uint_as_float(__float_as_uint(vc) ^ ((unsigned)((n + 1) & 2) << 30));
+}
+__device__ __forceinline__ void sincos_enc(float a, float& s, float& c) {
+  if (!sincos_enc_is_fast(a)) sincos_enc_slow(a, s, c);
+  else sincos_enc_fast(a, s, c);
+}
+
+// THE point and THE encoding column, stated once for kw_embed and for trunk_rows_encode (nsr_wide_trunk.inc), whose bits are kw_embed's.
+// embed_point: coordinate c of o + d z (RN:463, RN:478) -- a multiplication and an addition (the build has -ffp-contract=off).
+__device__ __forceinline__ float embed_point(float o, float d, float z) { return o + d * z; }
+// embed_arg: the fp32 argument 2^band x[c] of a band (exact scaling).  embed_band: columns 3 + 6 band + c (the sine) and 6 + 6 band + c
+// (the cosine) of the row of x, from its coordinate xc = x[c]: one sincos_enc serves both, which is how kw_embed asks.  embed_col:
+// column i of the row of an encoding with L bands, whichever it is -- x[i], one of that pair, or the exact zero of a padding column --
+// which is how a lane that owns arbitrary columns asks; trig(a, s, c) is sincos_enc, or a caller's wrapper of its pieces.
+__device__ __forceinline__ float embed_arg(float xc, int band) { return xc * ldexpf(1.0f, band); }
+__device__ __forceinline__ void embed_band(float xc, int band, float& s, float& c) { sincos_enc(embed_arg(xc, band), s, c); }
+template <class Trig>
+__device__ __forceinline__ float embed_col(const float (&x)[3], int i, int L, const Trig& trig) {
+  if (i >= 3 + 6 * L) return 0.0f;
+  if (i < 3) return i == 0 ? x[0] : i == 1 ? x[1] : x[2];
+  const int j = i - 3, band = j / 6, w = j - 6 * band, c = w < 3 ? w : w - 3;
+  float s, co;
+  trig(embed_arg(c == 0 ? x[0] : c == 1 ? x[1] : x[2], band), s, co);
+  return w < 3 ? s : co;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
 // GEMM: C[m][n] = epi( sum_k A[m][k] * Wt[n][k] + bias[n] ), A = [A1 | A2] (two row-major segments: the skip concatenation
 // cat[input_pts, h] RH:105-106 and cat[feature, input_views] RH:113 without materialising them), both K extents multiples of 32.
 // ONE kernel body for the three arithmetics (nsr_wide_gemm.inc: gemm_split_body -> kw_gemm_h2 / kw_gemm_b3 / kw_gemm_f32): weights as an
@@ -113,52 +183,11 @@ __global__ void __launch_bounds__(256) kw_ray_setup(const RayArgs a) {
   }
 }
 
-// gamma(x) (RH:18-48): sin / cos of the fp32 argument 2^l x (the scaling is exact) by sincos_enc: <= 1 ulp from the true value,
-// i.e. inside the reference's own libm error.  sin / cos of inf / NaN are NaN, as in torch.
-struct EmbedArgs {
-  const float* rays_o; const float* rays_d;   // rays form: point (r, s) = o + d z[r][s]  (RN:463, RN:478)
-  const float* z; const float* vd;            // [R,S], [R,3]
-  const float* pts; const float* dirs;        // points form (run_network): [P,3] each; used when rays_o == nullptr
-  long long P; int S;
-  int L, Lv;                                  // frequencies; Lv < 0: no direction encoding
-  float* E; int ldE;                          // [P, Ci]
-  float* ED; int ldED;                        // [P, Cv]
-};
-
-// sin and cos of the fp32 argument a for the encodings.  |a| < 2^24 (every scene: 2^14 |x| < 2^24 means |x| < 1024): ONE fp64
-// range reduction -- t = a * 2 / pi has >= 24 spare bits, the split into quadrant and fraction is exact -- and the Cephes
-// single-precision minimax polynomials on [-pi / 4, pi / 4] (1 ulp), as the fused kernels' enc_trig (nsr_kernels.hip); ~30 VALU
-// for the pair where the fp64 library sincos costs several hundred (r06: kw_embed was 2-9 % of a layered render).  Beyond that,
-// and for inf / NaN: the fp64 library routine, rounded once, as before.
-__device__ __forceinline__ void sincos_enc(float a, float& s, float& c) {
-  if (!(fabsf(a) < 16777216.0f)) {
-    double sd, cd;
-    sincos((double)a, &sd, &cd);
-    s = (float)sd; c = (float)cd;
-    return;
-  }
-  const double kMagic = 6755399441055744.0;                 // 1.5 * 2^52: t + kMagic holds rint(t) in its low word
-  const double t = (double)a * 0.63661977236758134308;      // a * 2 / pi
-  const double tm = t + kMagic;
-  const int n = __double2loint(tm);
-  const double f = t - (tm - kMagic);                       // [-0.5, 0.5], exact
-  const float r = (float)(f * 1.57079632679489661923);
-  const float z = r * r;
-  float ps = __builtin_fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f);
-  ps = __builtin_fmaf(ps, z, -1.6666654611e-1f);
-  ps = __builtin_fmaf(ps * z, r, r);
-  float pc = __builtin_fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f);
-  pc = __builtin_fmaf(pc, z, 4.166664568298827e-2f);
-  pc = __builtin_fmaf(pc * z, z, __builtin_fmaf(-0.5f, z, 1.0f));
-  const float vs = (n & 1) ? pc : ps, vc = (n & 1) ? ps : pc;              // sin(a) = sin(r + n pi/2), cos(a) = sin(r + (n + 1) pi/2)
-  s = __uint_as_float(__float_as_uint(vs) ^ ((unsigned)(n & 2) << 30));
-  c = __uint_as_float(__float_as_uint(vc) ^ ((unsigned)((n + 1) & 2) << 30));
-}
-
 // 16 threads per point, 16 points per workgroup: thread q computes x (q = 0) or band q - 1 (1 <= q <= L) of the position row and the
 // same of the direction row into LDS; the workgroup then writes its 16 consecutive rows of E (and of ED) -- one contiguous piece of
 // memory -- 16 bytes per thread, padding columns included (r06: the rows used to be written 24 strided bytes per thread, twelve
-// dword stores each; the kernel was 4-15 % of a layered render).
+// dword stores each; the kernel was 4-15 % of a layered render).  E == nullptr: the direction rows alone (a pass whose positions are
+// encoded in its on-chip launch); run_if: nothing unless the word is set (the encodings a bf16x3 re-run reads, behind such a pass).
 constexpr int kEmbedLdMax = 96;          // pad32(3 + 6 * 15)
 __global__ void __launch_bounds__(256) kw_embed(const EmbedArgs a) {
   __shared__ __attribute__((aligned(16))) float sE[16 * kEmbedLdMax];
@@ -167,7 +196,8 @@ __global__ void __launch_bounds__(256) kw_embed(const EmbedArgs a) {
   const long long p0 = (long long)blockIdx.x * 16;
   const int lp = tid >> 4, q = tid & 15;
   const long long p = p0 + lp;
-  const int nE = 16 * a.ldE / 4, nD = a.Lv >= 0 ? 16 * a.ldED / 4 : 0;          // float4s of the workgroup's rows
+  if (a.run_if && !*a.run_if) return;
+  const int nE = a.E ? 16 * a.ldE / 4 : 0, nD = a.Lv >= 0 ? 16 * a.ldED / 4 : 0;          // float4s of the workgroup's rows
   for (int t = tid; t < nE; t += 256) reinterpret_cast<f32x4*>(sE)[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
   for (int t = tid; t < nD; t += 256) reinterpret_cast<f32x4*>(sD)[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
   __syncthreads();
@@ -177,7 +207,7 @@ __global__ void __launch_bounds__(256) kw_embed(const EmbedArgs a) {
       const long long r = p / a.S;
       const float zz = a.z[p];
 #pragma unroll
-      for (int c = 0; c < 3; ++c) x[c] = a.rays_o[r * 3 + c] + a.rays_d[r * 3 + c] * zz;
+      for (int c = 0; c < 3; ++c) x[c] = embed_point(a.rays_o[r * 3 + c], a.rays_d[r * 3 + c], zz);
       if (a.Lv >= 0)
 #pragma unroll
         for (int c = 0; c < 3; ++c) v[c] = a.vd[r * 3 + c];
@@ -189,28 +219,27 @@ __global__ void __launch_bounds__(256) kw_embed(const EmbedArgs a) {
         for (int c = 0; c < 3; ++c) v[c] = a.dirs[p * 3 + c];
     }
     float* e = sE + lp * a.ldE;
-    NSRW_CHECK(a.ldE <= kEmbedLdMax && a.ldED <= kEmbedLdMax && 3 + 6 * a.L <= a.ldE);
-    if (q == 0) {
+    NSRW_CHECK(a.ldE <= kEmbedLdMax && a.ldED <= kEmbedLdMax && 3 + 6 * a.L <= a.ldE && (a.Lv < 0 || a.ED) && (a.E || a.Lv >= 0));
+    if (!a.E) {
+    } else if (q == 0) {
       e[0] = x[0]; e[1] = x[1]; e[2] = x[2];
     } else if (q <= a.L) {
-      const float f = ldexpf(1.0f, q - 1);
 #pragma unroll
-      for (int c = 0; c < 3; ++c) sincos_enc(x[c] * f, e[3 + 6 * (q - 1) + c], e[6 + 6 * (q - 1) + c]);
+      for (int c = 0; c < 3; ++c) embed_band(x[c], q - 1, e[3 + 6 * (q - 1) + c], e[6 + 6 * (q - 1) + c]);
     }
     if (a.Lv >= 0) {
       float* ed = sD + lp * a.ldED;
       if (q == 0) {
         ed[0] = v[0]; ed[1] = v[1]; ed[2] = v[2];
       } else if (q <= a.Lv) {
-        const float f = ldexpf(1.0f, q - 1);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) sincos_enc(v[c] * f, ed[3 + 6 * (q - 1) + c], ed[6 + 6 * (q - 1) + c]);
+        for (int c = 0; c < 3; ++c) embed_band(v[c], q - 1, ed[3 + 6 * (q - 1) + c], ed[6 + 6 * (q - 1) + c]);
       }
     }
   }
   __syncthreads();
   const long long rows = a.P - p0 < 16 ? a.P - p0 : 16;
-  const int mE = (int)(rows * a.ldE / 4), mD = a.Lv >= 0 ? (int)(rows * a.ldED / 4) : 0;
+  const int mE = a.E ? (int)(rows * a.ldE / 4) : 0, mD = a.Lv >= 0 ? (int)(rows * a.ldED / 4) : 0;
   f32x4* gE = reinterpret_cast<f32x4*>(a.E + p0 * a.ldE);
   for (int t = tid; t < mE; t += 256) gE[t] = reinterpret_cast<const f32x4*>(sE)[t];
   if (mD) {
@@ -689,9 +718,19 @@ struct Onchip {
   const TrunkForm* form = nullptr;
   const char* why = "";
 };
+// embed (NSRW_FLAG_EMBED_ONCHIP): which encodings the f16x2 launch of a pass computes itself -- form: the ENC twin of the pass's
+// form, which encodes the positions (nullptr: kw_embed writes them, why says why); dirs: it encodes the directions too (the heads
+// forms; else kw_embed writes ED alone, why_dirs says why)
+struct EmbedOn {
+  const TrunkForm* form = nullptr;
+  bool dirs = false;
+  const char* why = "";
+  const char* why_dirs = "";
+};
 struct OnchipPlan {
   Onchip trunk, heads, bwd, keep, rerun;
   const TrunkForm* keep_bwd = nullptr;
+  EmbedOn embed[2];                   // [0]: a pass that keeps nothing (the form of forward()), [1]: a kept pass (keep.form)
   const TrunkForm* forward() const { return heads.form ? heads.form : trunk.form; }      // the form of the forward's launch
 };
 
@@ -769,9 +808,10 @@ struct GemmCfg {
   int cus = 256;                        // compute units of the handle's device
   Arith arith = kF32;                   // NsrwConfig::flags: NSRW_FLAG_MLP_F16X2 -> kH2, NSRW_FLAG_MLP_BF16X3 -> kB3, neither -> kF32
   int tile_wm = 4;                      // 256-column tiles with 256 rows / 512 threads (4) or 128 rows / 256 threads (2: NSRW_B3_WM = 2)
-  int flags = 0;                        // NsrwConfig::flags (onchip_plan reads the arithmetic and the six on-chip flags)
+  int flags = 0;                        // NsrwConfig::flags (onchip_plan reads the arithmetic and the seven on-chip flags)
   unsigned long long* keep_passes = nullptr;      // host: kept forward passes launched on chip so far (Handle::keep_passes)
   unsigned long long* rerun_launches = nullptr;   // host: kw_rerun_b3 launches enqueued so far (Handle::rerun_launches)
+  unsigned long long* embed_counts = nullptr;     // host: Handle::embed_counts (nsrw_embed_status)
   unsigned* d_range = nullptr;          // device: [0] flag of the f16x2 pass in flight, [1] passes run, [2] passes re-run on bf16x3
 };
 
@@ -796,6 +836,7 @@ struct Handle {
   unsigned long long keep_passes = 0;     // nsrw_keep_status
   unsigned long long rerun_launches = 0;  // nsrw_rerun_status
   unsigned long long stage_launches = 0;  // nsrw_stages_status
+  unsigned long long embed_counts[3] = {0, 0, 0};      // nsrw_embed_status: passes encoded on chip, kw_embed launches, conditional ones
 };
 
 // appends a packed [Np][Kp] matrix to `img`; get(n, k) is consulted for n < rows, k < cols only
@@ -1053,6 +1094,7 @@ struct TrunkForm {
   TrunkKind kind;                       // which of the five kernels below the row has
   int nj, tile_rows;                    // 32-column blocks of the output one wave accumulates; points of a block
   bool heads;                           // forward rows: the heads run behind the trunk in the launch
+  bool encode;                          // forward and kept rows: the launch computes its encodings from the points (the ENC forms)
   TrunkKernel fwd;                      // kw_trunk_h2, or
   TrunkBwdKernel bwd;                   // kw_trunk_bwd_h2, or
   TrunkKeepKernel keep;                 // kw_keep_h2, or
@@ -1060,26 +1102,31 @@ struct TrunkForm {
   TrunkRerunKernel rerun;               // kw_rerun_b3: exactly one of the five
   int lds_bytes;                        // the kernel's own (static) LDS
 };
-template <int NJ, bool HEADS, int WR = 4>
-TrunkForm trunk_fwd_form() { return {kFormFwd, NJ, trunk_rows<WR>(), HEADS, kw_trunk_h2<NJ, HEADS, WR>, nullptr, nullptr, nullptr, nullptr, trunk_lds_bytes<NJ, WR>()}; }
+template <int NJ, bool HEADS, int WR = 4, bool ENC = false>
+TrunkForm trunk_fwd_form() { return {kFormFwd, NJ, trunk_rows<WR>(), HEADS, ENC, ENC ? kw_enc_trunk_h2<NJ, HEADS, WR> : kw_trunk_h2<NJ, HEADS, WR>, nullptr, nullptr, nullptr, nullptr, trunk_lds_bytes<NJ, WR>()}; }
 template <int NJ>
-TrunkForm trunk_bwd_form_row() { return {kFormBwd, NJ, trunk_rows<4>(), false, nullptr, kw_trunk_bwd_h2<NJ>, nullptr, nullptr, nullptr, trunk_bwd_lds_bytes<NJ>()}; }
-template <int NJ, bool HEADS>
-TrunkForm trunk_keep_form() { return {kFormKeep, NJ, trunk_rows<4>(), HEADS, nullptr, nullptr, kw_keep_h2<NJ, HEADS>, nullptr, nullptr, trunk_lds_bytes<NJ, 4>()}; }
+TrunkForm trunk_bwd_form_row() { return {kFormBwd, NJ, trunk_rows<4>(), false, false, nullptr, kw_trunk_bwd_h2<NJ>, nullptr, nullptr, nullptr, trunk_bwd_lds_bytes<NJ>()}; }
+template <int NJ, bool HEADS, bool ENC = false>
+TrunkForm trunk_keep_form() { return {kFormKeep, NJ, trunk_rows<4>(), HEADS, ENC, nullptr, nullptr, ENC ? kw_enc_keep_h2<NJ, HEADS> : kw_keep_h2<NJ, HEADS>, nullptr, nullptr, trunk_lds_bytes<NJ, 4>()}; }
 template <int NJ>
-TrunkForm trunk_keep_bwd_form() { return {kFormKeepBwd, NJ, trunk_rows<4>(), false, nullptr, nullptr, nullptr, kw_keep_bwd_h2<NJ>, nullptr, trunk_bwd_lds_bytes<NJ>()}; }
+TrunkForm trunk_keep_bwd_form() { return {kFormKeepBwd, NJ, trunk_rows<4>(), false, false, nullptr, nullptr, nullptr, kw_keep_bwd_h2<NJ>, nullptr, trunk_bwd_lds_bytes<NJ>()}; }
 template <int NJ, int WR>
-TrunkForm trunk_rerun_form() { return {kFormRerun, NJ, trunk_rows<WR>(), false, nullptr, nullptr, nullptr, nullptr, kw_rerun_b3<NJ, WR>, trunk_lds_bytes<NJ, WR, 3>()}; }
-// (in this order: the order of instantiation is the order of the kernels in the code object)
+TrunkForm trunk_rerun_form() { return {kFormRerun, NJ, trunk_rows<WR>(), false, false, nullptr, nullptr, nullptr, nullptr, kw_rerun_b3<NJ, WR>, trunk_lds_bytes<NJ, WR, 3>()}; }
+// (in this order: the order of instantiation is the order of the kernels in the code object; the ENC twins of the forward and kept
+// forms stand behind everything that was there)
 const TrunkForm kTrunkForms[] = {trunk_fwd_form<1, true>(), trunk_fwd_form<2, true>(), trunk_fwd_form<1, false>(), trunk_fwd_form<2, false>(),
                                  trunk_fwd_form<2, false, 2>(), trunk_bwd_form_row<1>(), trunk_bwd_form_row<2>(),
                                  trunk_keep_form<1, true>(), trunk_keep_form<2, true>(), trunk_keep_form<1, false>(), trunk_keep_form<2, false>(),
-                                 trunk_keep_bwd_form<1>(), trunk_keep_bwd_form<2>(), trunk_rerun_form<1, 4>(), trunk_rerun_form<1, 2>()};
+                                 trunk_keep_bwd_form<1>(), trunk_keep_bwd_form<2>(), trunk_rerun_form<1, 4>(), trunk_rerun_form<1, 2>(),
+                                 trunk_fwd_form<1, true, 4, true>(), trunk_fwd_form<2, true, 4, true>(), trunk_fwd_form<1, false, 4, true>(),
+                                 trunk_fwd_form<2, false, 4, true>(), trunk_fwd_form<2, false, 2, true>(),
+                                 trunk_keep_form<1, true, true>(), trunk_keep_form<2, true, true>(), trunk_keep_form<1, false, true>(),
+                                 trunk_keep_form<2, false, true>()};
 constexpr int kTrunkThreads = 512;
 
-const TrunkForm* find_trunk_form(TrunkKind kind, int nj, int tile_rows, bool heads) {
+const TrunkForm* find_trunk_form(TrunkKind kind, int nj, int tile_rows, bool heads, bool encode = false) {
   for (const TrunkForm& f : kTrunkForms)
-    if (f.kind == kind && f.nj == nj && f.tile_rows == tile_rows && f.heads == heads) return &f;
+    if (f.kind == kind && f.nj == nj && f.tile_rows == tile_rows && f.heads == heads && f.encode == encode) return &f;
   return nullptr;
 }
 
@@ -1105,6 +1152,7 @@ OnchipPlan onchip_plan(const NsrwNet& d, int flags) {
   };
   if (!check_net(d).empty()) {
     p.trunk.why = p.heads.why = p.bwd.why = p.keep.why = p.rerun.why = "invalid network";
+    for (EmbedOn& e : p.embed) e.why = e.why_dirs = "invalid network";
     return p;
   }
   const int Wp = pad32(d.W), Ci = pad32(3 + 6 * d.multires), narrow = trunk_rows<4>();
@@ -1148,6 +1196,19 @@ OnchipPlan onchip_plan(const NsrwNet& d, int flags) {
          : !narrow_trunk                  ? "padded width above 128: the wide trunk has no re-run form"
                                           : nullptr,
          kFormRerun, 1, Wp <= 64 ? trunk_rows<4>() : trunk_rows<2>(), false);
+  // embed: per kind of pass, the ENC twin of the form its f16x2 launch has -- it encodes the positions; the directions too where the
+  // heads run in that launch (no view directions: there is nothing to encode)
+  for (int kept = 0; kept < 2; ++kept) {
+    EmbedOn& e = p.embed[kept];
+    const TrunkForm* f = kept ? p.keep.form : p.forward();
+    const char* no_form = kept ? "the kept forward is not on chip" : "the trunk is not on chip";
+    e.why = !(flags & NSRW_FLAG_EMBED_ONCHIP) ? "NSRW_FLAG_EMBED_ONCHIP not set" : !f ? no_form : nullptr;
+    if (!e.why && !(e.form = find_trunk_form(f->kind, f->nj, f->tile_rows, f->heads, true))) e.why = "internal error: form not compiled";
+    e.why_dirs = e.why ? e.why : !d.use_viewdirs ? "no view directions" : !f->heads ? "the heads are not on chip" : nullptr;
+    e.dirs = !e.why_dirs;
+    if (!e.why) e.why = "";
+    if (!e.why_dirs) e.why_dirs = "";
+  }
   return p;
 }
 
@@ -1169,6 +1230,8 @@ constexpr FlagNeeds kFlagNeeds[] = {
      "nsrw_create: NSRW_FLAG_TRUNK_KEEP needs NSRW_FLAG_TRUNK_BWD (the kept on-chip forward leaves its relu masks as bits, which only the on-chip backward trunk reads)"},
     {NSRW_FLAG_TRUNK_RERUN, NSRW_FLAG_TRUNK_ONCHIP,
      "nsrw_create: NSRW_FLAG_TRUNK_RERUN needs NSRW_FLAG_TRUNK_ONCHIP (the on-chip bf16x3 re-run serves the passes whose f16x2 trunk ran on chip)"},
+    {NSRW_FLAG_EMBED_ONCHIP, NSRW_FLAG_TRUNK_ONCHIP,
+     "nsrw_create: NSRW_FLAG_EMBED_ONCHIP needs NSRW_FLAG_TRUNK_ONCHIP (the encodings are computed in the on-chip trunk's launch)"},
 };
 
 // the decisions as the diagnostic entries report them (no form: every figure 0, and the reason)
@@ -1264,10 +1327,13 @@ std::vector<TrunkLayer> trunk_table(const Net& n, int* fwd_rows, int* bwd_rows, 
 
 // all D pts_linears layers over P points in ONE launch: k.E -> k.H[(D - 1) & 1], where net_forward_chain's layer loop leaves them;
 // or (the heads form) the heads too: k.E, k.ED -> k.RAW, where net_forward_chain's head launches leave them
-void trunk_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P) {
-  const TrunkForm& f = *n.onchip.forward();
+// (src: the pass's points, where the launch computes its encodings itself -- the ENC twin of the form, n.onchip.embed; else nullptr)
+TrunkPoints trunk_points(const EmbedArgs& a) { return TrunkPoints{a.rays_o, a.rays_d, a.z, a.vd, a.pts, a.dirs, a.S, a.L, a.Lv}; }
+void trunk_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P, const EmbedArgs* src) {
+  const TrunkForm& f = src ? *n.onchip.embed[0].form : *n.onchip.forward();
   TrunkArgs t{};
-  t.E = k.E; t.ldE = n.Ci;
+  t.E = src ? nullptr : k.E; t.ldE = n.Ci;
+  if (src) t.pts = trunk_points(*src);
   t.img = n.dImg[kH2]; t.img_bytes = (unsigned)n.img_bytes[kH2];
   t.bias = n.dBias; t.bias_floats = n.bias_floats;
   t.layers = n.dTrunk; t.D = n.trunk_rows; t.Dt = n.d.D;
@@ -1307,12 +1373,13 @@ KeepMasks keep_masks(const Net& n, const Chunk& k, long long P) {
 
 // The f16x2 pass of a forward that KEEPS its activations, in one launch (n.onchip.keep): k.E, k.ED -> the masks of layers 0 .. D - 2
 // as bits in k.MB, fp32 k.H[D - 1] -- where the kept per-layer chain leaves it -- and, in the heads form, fp32 k.HV and k.RAW
-int keep_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P) {
-  const TrunkForm& f = *n.onchip.keep.form;
+int keep_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P, const EmbedArgs* src) {
+  const TrunkForm& f = src ? *n.onchip.embed[1].form : *n.onchip.keep.form;
   if (!k.MB) return fail("nsrw: internal error: a kept on-chip pass without a mask buffer");
   TrunkKeepArgs a{};
   TrunkArgs t{};
-  t.E = k.E; t.ldE = n.Ci;
+  t.E = src ? nullptr : k.E; t.ldE = n.Ci;
+  if (src) t.pts = trunk_points(*src);
   t.img = n.dImg[kH2]; t.img_bytes = (unsigned)n.img_bytes[kH2];
   t.bias = n.dBias; t.bias_floats = n.bias_floats;
   t.layers = n.dTrunk; t.D = n.trunk_rows; t.Dt = n.d.D;
@@ -1346,8 +1413,9 @@ bool keep_pass(const Net& n, long long P) { return onchip_pass(Run{kH2, nullptr}
 
 // RH:99-122 over P points whose encodings are in k.E / k.ED: leaves the rgb logits in k.RAW (ld 32; all output_linear rows
 // without view directions) and the density at sigma / ld_sigma.  keep: every pts layer's activation stays (k.H[i]).
+// src: nullptr, or the pass's points where its on-chip launch computes the encodings itself (net_forward decides; f16x2 pass only).
 int net_forward_chain(const GemmCfg& cfg, Run run, hipStream_t st, const Net& n, const Chunk& k, long long P, bool keep, const float** sigma,
-                      int* ld_sigma) {
+                      int* ld_sigma, const EmbedArgs* src = nullptr) {
   const float* h = nullptr;
   // f16x2 pass of an eligible network on an on-chip handle: the one trunk launch where no activation is kept, the one kept launch
   // where the network has that form (the conditional bf16x3 re-run and every other pass that keeps its activations for a backward
@@ -1355,8 +1423,8 @@ int net_forward_chain(const GemmCfg& cfg, Run run, hipStream_t st, const Net& n,
   const bool kept = keep && onchip_pass(run, n.onchip.keep.form, P);
   const bool onchip = kept || (!keep && onchip_pass(run, n.onchip.forward(), P));
   if (onchip) {
-    if (kept) { if (keep_launch(cfg, st, n, k, P)) return 1; }
-    else trunk_launch(cfg, st, n, k, P);
+    if (kept) { if (keep_launch(cfg, st, n, k, P, src)) return 1; }
+    else trunk_launch(cfg, st, n, k, P, src);
     if (n.onchip.heads.form) {        // the heads ran behind the trunk: k.FA is not written (kept: k.H[D - 1], k.HV and the masks are)
       *sigma = k.RAW + 3; *ld_sigma = n.ldraw;
       return 0;
@@ -1402,12 +1470,35 @@ __global__ void kw_range_tally(unsigned* r) {
   }
 }
 
-int net_forward(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P, bool keep, const float** sigma,
-                int* ld_sigma) {
-  if (cfg.arith != kH2 || P <= 0) return net_forward_chain(cfg, Run{cfg.arith, nullptr}, st, n, k, P, keep, sigma, ld_sigma);
+// kw_embed over the points of `src` (EmbedArgs::E / ED are set here): E nullable -- the direction rows alone; run_if nullable
+void embed_launch(const GemmCfg& cfg, hipStream_t st, EmbedArgs a, float* E, float* ED, const unsigned* run_if) {
+  a.E = E; a.ED = ED; a.run_if = run_if;
+  if (!ED) a.Lv = -1;                 // the position rows alone: kw_embed takes Lv >= 0 as "write ED"
+  hipLaunchKernelGGL(kw_embed, dim3((unsigned)((a.P * 16 + 255) / 256)), dim3(256), 0, st, a);
+  if (cfg.embed_counts) ++cfg.embed_counts[run_if ? 2 : 1];
+}
+
+// One network pass over the P points of `src` (EmbedArgs without E / ED: where the points come from, the bands, the row lengths): the
+// encodings, then the chain.  On a handle with NSRW_FLAG_EMBED_ONCHIP the f16x2 launch of a pass that runs on chip computes the
+// position encodings itself (n.onchip.embed; the direction encodings too in a heads form, else kw_embed writes k.ED alone), and
+// kw_embed for k.E (and k.ED) stands conditional on the range word in front of the bf16x3 chain, which reads them from memory.
+int net_forward(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, const EmbedArgs& src, long long P, bool keep,
+                const float** sigma, int* ld_sigma) {
+  if (P <= 0) return net_forward_chain(cfg, Run{cfg.arith, nullptr}, st, n, k, P, keep, sigma, ld_sigma);
+  const EmbedOn& eo = n.onchip.embed[keep ? 1 : 0];
+  // (the conditions under which net_forward_chain's f16x2 pass is the one launch of the form eo.form is the twin of)
+  const bool enc = cfg.arith == kH2 && eo.form && onchip_pass(Run{kH2, nullptr}, keep ? n.onchip.keep.form : n.onchip.forward(), P);
+  float* ED = src.Lv >= 0 ? k.ED : nullptr;
+  if (!enc) embed_launch(cfg, st, src, k.E, ED, nullptr);
+  else if (ED && !eo.dirs) embed_launch(cfg, st, src, nullptr, ED, nullptr);
+  if (cfg.arith != kH2) return net_forward_chain(cfg, Run{cfg.arith, nullptr}, st, n, k, P, keep, sigma, ld_sigma);
   // f16x2: the pass on fp16 MFMAs; then the same pass on bf16x3 in launches that are empty unless an activation left fp16's
   // range (its inputs -- the encodings -- are untouched, every buffer it writes is written again); then the tally
-  if (net_forward_chain(cfg, Run{kH2, nullptr}, st, n, k, P, keep, sigma, ld_sigma)) return 1;
+  if (net_forward_chain(cfg, Run{kH2, nullptr}, st, n, k, P, keep, sigma, ld_sigma, enc ? &src : nullptr)) return 1;
+  if (enc) {
+    embed_launch(cfg, st, src, k.E, eo.dirs ? ED : nullptr, cfg.d_range);
+    if (cfg.embed_counts) ++cfg.embed_counts[0];
+  }
   if (net_forward_chain(cfg, Run{kB3, cfg.d_range}, st, n, k, P, keep, sigma, ld_sigma)) return 1;
   // a kept on-chip pass that was re-run: the re-run has rewritten every fp32 H, the backward reads bits
   if (keep && keep_pass(n, P) && mask_launch(cfg, st, n, k, P, true)) return 1;
@@ -1588,19 +1679,18 @@ int render_impl(Handle* h, const float* ro, const float* rd, long long n, float 
     ra.vd = k.vd; ra.nrm = k.nrm; ra.z0 = k.z0;
     hipLaunchKernelGGL(kw_ray_setup, dim3(rb), dim3(256), 0, st, ra);
 
-    auto encode = [&](const Net& nn, const float* z, int S) {
+    // the points of a pass of `nn` at the depths z (net_forward encodes them, in kw_embed or in the pass's own launch)
+    auto points = [&](const Net& nn, const float* z, int S) {
       EmbedArgs ea{};
       ea.rays_o = ra.rays_o; ea.rays_d = ra.rays_d; ea.z = z; ea.vd = k.vd; ea.P = (long long)Rc * S; ea.S = S;
       ea.L = nn.d.multires; ea.Lv = nn.d.use_viewdirs ? nn.d.multires_views : -1;
-      ea.E = k.E; ea.ldE = nn.Ci; ea.ED = k.ED; ea.ldED = nn.Cv;
-      const long long thr = ea.P * 16;
-      hipLaunchKernelGGL(kw_embed, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, st, ea);
+      ea.ldE = nn.Ci; ea.ldED = nn.Cv;
+      return ea;
     };
     // ---- coarse pass (RN:463-467) ----
     const float* sigma; int ld_sigma;
-    encode(n0, k.z0, S0);
     const bool grad_coarse = grad_last && NI == 0;
-    if (net_forward(h->gemm_cfg, st, n0, k, (long long)Rc * S0, grad_coarse, &sigma, &ld_sigma)) return 1;
+    if (net_forward(h->gemm_cfg, st, n0, k, points(n0, k.z0, S0), (long long)Rc * S0, grad_coarse, &sigma, &ld_sigma)) return 1;
     CompositeArgs ca{};
     ca.R = Rc; ca.S = S0; ca.flags = h->cfg.flags; ca.rgb = k.RAW; ca.ld_rgb = n0.ldraw; ca.sigma = sigma; ca.ld_sigma = ld_sigma;
     ca.z = k.z0; ca.nrm = k.nrm; ca.noise = e.d_noise0 ? e.d_noise0 + r0 * S0 : nullptr; ca.weights = k.w0;
@@ -1630,8 +1720,7 @@ int render_impl(Handle* h, const float* ro, const float* rd, long long n, float 
       if (e.d_z_fine)          // given depths (constants of the gradient, RN:475) replace the resampled ones for the fine pass
         NSRW_HIP(hipMemcpyAsync(k.zf, e.d_z_fine + r0 * S1, (size_t)Rc * S1 * 4, hipMemcpyDeviceToDevice, st));
       // ---- fine pass (RN:478-485) ----
-      encode(n1, k.zf, S1);
-      if (net_forward(h->gemm_cfg, st, n1, k, (long long)Rc * S1, grad_last, &sigma, &ld_sigma)) return 1;
+      if (net_forward(h->gemm_cfg, st, n1, k, points(n1, k.zf, S1), (long long)Rc * S1, grad_last, &sigma, &ld_sigma)) return 1;
       CompositeArgs cf = ca;
       cf.S = S1; cf.ld_rgb = n1.ldraw; cf.sigma = sigma; cf.ld_sigma = ld_sigma; cf.z = k.zf; cf.noise = e.d_noise1 ? e.d_noise1 + r0 * S1 : nullptr;
       cf.weights = k.wf;
@@ -1674,8 +1763,7 @@ int render_impl(Handle* h, const float* ro, const float* rd, long long n, float 
     if (grad_c) {
       // ---- the coarse pass's backward (RN:463-467 with rgb0 / disp0 / acc0, RN:492-494): its forward again, activations kept
       // (the buffers the last pass's backward is done with), then the same three stages, adding into the rays' gradients
-      encode(n0, k.z0, S0);
-      if (net_forward(h->gemm_cfg, st, n0, k, (long long)Rc * S0, true, &sigma, &ld_sigma)) return 1;
+      if (net_forward(h->gemm_cfg, st, n0, k, points(n0, k.z0, S0), (long long)Rc * S0, true, &sigma, &ld_sigma)) return 1;
       if (backward(n0, k.z0, S0, ca.noise, sigma, ld_sigma, cot->d_rgb0, cot->d_disp0, cot->d_acc0, grad_last ? 1 : 0)) return 1;
     }
     if (cot && !grad) {       // cotangents given, all NULL: the gradient of nothing
@@ -1741,6 +1829,7 @@ int nsrw_create(const NsrwConfig* cfg, nsrw_handle* out) {
   h->gemm_cfg.d_range = h->d_range;
   h->gemm_cfg.keep_passes = &h->keep_passes;
   h->gemm_cfg.rerun_launches = &h->rerun_launches;
+  h->gemm_cfg.embed_counts = h->embed_counts;
   *out = reinterpret_cast<nsrw_handle>(h);
   return 0;
 }
@@ -2017,10 +2106,9 @@ int nsrw_run_network(nsrw_handle hh, int net_id, const float* d_pts, const float
     EmbedArgs ea{};
     ea.pts = d_pts + p0 * 3; ea.dirs = d_viewdirs ? d_viewdirs + p0 * 3 : nullptr; ea.P = P; ea.S = 1;
     ea.L = n.d.multires; ea.Lv = n.d.use_viewdirs ? n.d.multires_views : -1;
-    ea.E = k.E; ea.ldE = n.Ci; ea.ED = k.ED; ea.ldED = n.Cv;
-    hipLaunchKernelGGL(kw_embed, dim3((unsigned)((P * 16 + 255) / 256)), dim3(256), 0, st, ea);
+    ea.ldE = n.Ci; ea.ldED = n.Cv;
     const float* sigma; int ld_sigma;
-    if (net_forward(h->gemm_cfg, st, n, k, P, false, &sigma, &ld_sigma)) return 1;
+    if (net_forward(h->gemm_cfg, st, n, k, ea, P, false, &sigma, &ld_sigma)) return 1;
     const int C = n.raw_ch;
     if (n.d.use_viewdirs) {          // the raw block IS [P, 4] = [r g b sigma]
       NSRW_HIP(hipMemcpyAsync(d_raw + p0 * 4, k.RAW, (size_t)P * 4 * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -2101,6 +2189,29 @@ int nsrw_rerun_status(nsrw_handle hh, unsigned long long* launches_onchip) {
   Handle* h = reinterpret_cast<Handle*>(hh);
   if (!h || !launches_onchip) return fail("nsrw_rerun_status: null argument");
   *launches_onchip = h->rerun_launches;
+  return 0;
+}
+
+int nsrw_embed_plan(const NsrwNet* net, int flags, int kept, NsrwEmbedPlan* plan_out) {
+  OnchipPlan p;
+  if (plan_entry("nsrw_embed_plan", net, plan_out, flags, &p)) return -1;
+  const EmbedOn& e = p.embed[kept ? 1 : 0];
+  NsrwEmbedPlan o{};
+  o.positions_onchip = e.form ? 1 : 0;
+  o.directions_onchip = e.dirs ? 1 : 0;
+  snprintf(o.positions_reason, sizeof o.positions_reason, "%s", e.why);
+  snprintf(o.directions_reason, sizeof o.directions_reason, "%s", e.why_dirs);
+  *plan_out = o;
+  return 0;
+}
+
+int nsrw_embed_status(nsrw_handle hh, unsigned long long* passes_onchip, unsigned long long* embed_launches,
+                      unsigned long long* embed_launches_conditional) {
+  Handle* h = reinterpret_cast<Handle*>(hh);
+  if (!h || !passes_onchip || !embed_launches || !embed_launches_conditional) return fail("nsrw_embed_status: null argument");
+  *passes_onchip = h->embed_counts[0];
+  *embed_launches = h->embed_counts[1];
+  *embed_launches_conditional = h->embed_counts[2];
   return 0;
 }
 

@@ -32,6 +32,9 @@
 //     the writes in front of the next row's reads.
 //   * trunk_rows_fetch / trunk_rows_store: a block's rows of an [M, ld] fp32 matrix -> a piece image (the encodings, the direction
 //     encodings, the incoming gradient), rows behind M clamped on the way in, split and fed to amax as above.
+//   * trunk_rows_encode (NSRW_FLAG_EMBED_ONCHIP; the kw_enc_ twins of the forward and kept kernels): the same registers as
+//     trunk_rows_fetch, computed from the block's points by kw_embed's own functions instead of fetched -- kw_embed's bits, and
+//     trunk_rows_store behind it as it was.
 //   * trunk_tail: no LDS-DMA outlives the workgroup; the range flag.
 //
 // kw_trunk_h2<NJ, HEADS, WR>: all D pts_linears layers (RH:99-107) of a network of packed width Wp <= 128 on a block of 128 points
@@ -103,8 +106,17 @@ __host__ __device__ inline int trunk_store_ncols(int store) { return store & 255
 __host__ __device__ inline int trunk_store_col0(int store) { return store >> 8 & 255; }
 __host__ __device__ inline int trunk_store_ld(int store) { return store >> 16 & 255; }
 
+// Where the points of a launch that computes its encodings itself come from (the ENC forms; what EmbedArgs carries of them): rays
+// form -- point p lies on ray p / S at depth z[p] -- or, rays_o == nullptr, the points form of nsrw_run_network
+struct TrunkPoints {
+  const float* rays_o; const float* rays_d; const float* z; const float* vd;      // [R,3], [R,3], [M], [R,3]
+  const float* pts; const float* dirs;                                            // [M,3] each
+  int S;
+  int L, Lv;                        // bands of the position / direction encoding
+};
+
 struct TrunkArgs {
-  const float* E; int ldE;          // encodings [M, ldE], ldE = Ci <= kTrunkCiMax
+  const float* E; int ldE;          // encodings [M, ldE], ldE = Ci <= kTrunkCiMax; nullptr in the ENC forms: encoded here, from `pts`
   const char* img; unsigned img_bytes;
   const float* bias; unsigned bias_floats;
   const TrunkLayer* layers; int D;  // rows of the table: the pts_linears (trunk-only form), and the heads behind them (heads form)
@@ -114,6 +126,7 @@ struct TrunkArgs {
   float* RAW;                       // rows store to
   long long M;
   unsigned* range_flag;
+  TrunkPoints pts;                  // the ENC forms (behind everything else: the other forms read their arguments where they were)
 };
 
 // WR wave rows of 32 points by 8 / WR wave columns of NJ column blocks: WR = 4 the 128-row forms, WR = 2 the wide form
@@ -260,6 +273,78 @@ __device__ __forceinline__ void trunk_rows_fetch(const TrunkCtx<LDS>& c, const f
     e[i][1] = *reinterpret_cast<const f32x4*>(xp + kc * 16 + 4);
   }
 }
+// The same registers from the block's POINTS instead of a matrix (the ENC forms): what trunk_rows_fetch would have loaded from the E
+// (DIRS = false) or ED (DIRS = true) that kw_embed writes, computed by kw_embed's own functions -- embed_point, embed_col -- so that
+// the bits are its bits, the exact zeros of the padding columns behind 3 + 6 L included.  Rows behind M are clamped to point M - 1
+// before anything is read, as there.  Each lane computes the eight consecutive columns of its own fragments: no scratch, no barrier,
+// and trunk_rows_store behind it is what it was.  (A block behind KBX is not computed: it is not written either.)  The unrolled path
+// has sincos_enc's polynomial alone; a wave in which a lane met an argument for the fp64 library routine (|a| >= 2^24, inf, NaN:
+// hostile rays) computes its columns once more, one by one through sincos_enc itself -- embed_col_hard, a CALL, so that the library
+// routine's registers are its own and not the kernel's.  The scheduling barrier after every fourth column keeps four polynomial
+// chains in flight, not twenty-four: the registers of the latter would not fit beside the kernel's.
+__device__ __noinline__ float embed_col_hard(float x0, float x1, float x2, int i, int L) {
+  const float x[3] = {x0, x1, x2};
+  return embed_col(x, i, L, [](float a, float& sn, float& cs) { sincos_enc(a, sn, cs); });
+}
+template <int IT, int WC, bool DIRS, int LDS>
+__device__ __forceinline__ void trunk_rows_encode(const TrunkCtx<LDS>& c, const TrunkPoints& s, int KBX, long long m0, long long M, f32x4 (&e)[IT][2]) {
+  long long am = m0 + 32 * c.wr + c.lrow;
+  if (am >= M) am = M - 1;
+  NSRW_CHECK(am >= 0 && am < M && KBX >= 1 && (s.rays_o ? s.S >= 1 : true));
+  float x[3];
+  if (s.rays_o) {
+    // ray am / S without a 64-bit division per lane: the block's first ray once (uniform), then a 32-bit one of the offset
+    const long long r0 = m0 / s.S;
+    const long long r = r0 + (int)(am - r0 * s.S) / s.S;
+    NSRW_CHECK(am - r0 * s.S >= 0 && am - r0 * s.S < 0x7fffffffll && r * s.S <= am && am < (r + 1) * s.S);
+    if constexpr (DIRS) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q) x[q] = s.vd[r * 3 + q];
+    } else {
+      const float zz = s.z[am];
+#pragma unroll
+      for (int q = 0; q < 3; ++q) x[q] = embed_point(s.rays_o[r * 3 + q], s.rays_d[r * 3 + q], zz);
+    }
+  } else {
+    const float* src = DIRS ? s.dirs : s.pts;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) x[q] = src[am * 3 + q];
+  }
+  const int L = DIRS ? s.Lv : s.L;
+  bool hard = false;
+  auto poly = [&](float a, float& sn, float& cs) {
+    if (sincos_enc_is_fast(a)) sincos_enc_fast(a, sn, cs);
+    else { hard = true; sn = cs = 0.0f; }
+  };
+#pragma unroll
+  for (int i = 0; i < IT; ++i) {
+    const int kb = WC * i + c.wc;
+    if (kb < KBX) {
+      // (opaque: which band and coordinate a column is does not change from block to block, and the compiler would otherwise keep
+      // all of it -- a hundred registers -- across the row loop)
+      int k0 = kb * 16 + 8 * c.lh;
+      asm volatile("" : "+v"(k0));
+#pragma unroll
+      for (int t = 0; t < 8; ++t) {
+        e[i][t >> 2][t & 3] = embed_col(x, k0 + t, L, poly);
+        if ((t & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+      }
+    } else {
+      e[i][0] = e[i][1] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+  }
+  if (__builtin_amdgcn_ballot_w64(hard) != 0ull) {
+#pragma nounroll
+    for (int u = 0; u < 8 * IT; ++u) {
+      const int kb = WC * (u >> 3) + c.wc;
+      if (kb >= KBX) continue;
+      const float v = embed_col_hard(x[0], x[1], x[2], kb * 16 + 8 * c.lh + (u & 7), L);
+#pragma unroll
+      for (int w = 0; w < 8 * IT; ++w)
+        if (w == u) e[w >> 3][(w >> 2) & 1][w & 3] = v;
+    }
+  }
+}
 // ... split by split8_h2 and written to the image whose fragment of this lane is at frag (TrunkCtx::frag0), pieces pstride apart,
 // rows of `stride` bytes, inside the first lds_end bytes of LDS
 // (NP = 3: by split8_b3, which has no range and leaves amax alone)
@@ -303,8 +388,12 @@ __device__ __forceinline__ void trunk_write_inplace(const TrunkCtx<LDS>& c, cons
 
 // ---- the FORWARD trunk, and the heads behind it --------------------------------------------------------------------------------------
 
-template <int NJ, bool HEADS, int WR = 4>
-__global__ void __launch_bounds__(512, 1) kw_trunk_h2(const TrunkArgs g) {
+// ENC (NSRW_FLAG_EMBED_ONCHIP): the block's encodings are computed from its points (trunk_rows_encode) where the other forms fetch
+// g.E -- and, in the heads form, g.ED -- from memory; nothing else differs.  The body is stated once, selected by that template
+// parameter, and has two kernels: kw_trunk_h2<NJ, HEADS, WR> (ENC = false: the code it was, under the name it had) and its twin
+// kw_enc_trunk_h2<NJ, HEADS, WR>.
+template <int NJ, bool HEADS, int WR, bool ENC>
+__device__ __forceinline__ void trunk_h2_body(const TrunkArgs g) {
   static_assert((WR == 4 || (WR == 2 && NJ == 2 && !HEADS)), "the wide form is trunk-only, two column blocks a wave");
   constexpr int WC = 8 / WR, NCB = trunk_ncb<NJ, WR>(), kTrunkRows = trunk_rows<WR>();
   constexpr int kWStage = trunk_wstage<NJ, WR>(), kSH = trunk_sh<NJ, WR>(), kHPiece = kTrunkRows * kSH, kEPiece = kTrunkRows * kTrunkSE;
@@ -322,6 +411,7 @@ __global__ void __launch_bounds__(512, 1) kw_trunk_h2(const TrunkArgs g) {
   const int KBE = g.ldE >> 4, KBH = g.Wp >> 4, ncbr = g.Wp >> 5;
   NSRW_CHECK(KBE >= 2 && KBE <= kKbeMax && KBH >= 2 && KBH <= 2 * NCB && g.D >= 1);
   if constexpr (HEADS) NSRW_CHECK(g.Dt >= 1 && g.Dt < g.D && (!g.ED || ((g.ldED >> 4) >= 2 && (g.ldED >> 4) <= kKbeMax)));
+  if constexpr (ENC) NSRW_CHECK(!g.E && 3 + 6 * g.pts.L <= g.ldE && (!HEADS || !g.ED || 3 + 6 * g.pts.Lv <= g.ldED));
   auto dma = [&](unsigned img_off, int KB, int kb0, int b, int ncb) { trunk_dma<NCB, kNcbVaries>(c, rsrc, g.img_bytes, img_off, KB, kb0, b, ncb); };
 
   float amax = 0.0f;                // largest magnitude this lane has split (encodings and activations)
@@ -335,7 +425,8 @@ __global__ void __launch_bounds__(512, 1) kw_trunk_h2(const TrunkArgs g) {
     const long long m0 = (long long)mb * kTrunkRows;
     {
       f32x4 e[kEncIt][2];
-      trunk_rows_fetch<kEncIt, WC>(c, g.E, g.ldE, KBE, m0, g.M, e);
+      if constexpr (ENC) trunk_rows_encode<kEncIt, WC, false>(c, g.pts, KBE, m0, g.M, e);
+      else trunk_rows_fetch<kEncIt, WC>(c, g.E, g.ldE, KBE, m0, g.M, e);
       trunk_rows_store<kEncIt, WC>(c, KBE, e, row_e, kEPiece, kTrunkSE, kLds, amax);
     }
     trunk_sync();                   // the encodings are written (and, in the first block, the first stage of weights has landed)
@@ -360,7 +451,10 @@ __global__ void __launch_bounds__(512, 1) kw_trunk_h2(const TrunkArgs g) {
       f32x4 ed[kEncIt][2];
       const bool ed_here = HEADS && li + 1 == g.Dt && g.ED;
       if constexpr (HEADS) {
-        if (ed_here) trunk_rows_fetch<kEncIt, WC>(c, g.ED, g.ldED, g.ldED >> 4, m0, g.M, ed);
+        if (ed_here) {
+          if constexpr (ENC) trunk_rows_encode<kEncIt, WC, true>(c, g.pts, g.ldED >> 4, m0, g.M, ed);
+          else trunk_rows_fetch<kEncIt, WC>(c, g.ED, g.ldED, g.ldED >> 4, m0, g.M, ed);
+        }
       }
       f32x16 acc[NJ];
 #pragma unroll
@@ -448,6 +542,20 @@ __global__ void __launch_bounds__(512, 1) kw_trunk_h2(const TrunkArgs g) {
     }
   }
   trunk_tail(c, amax, g.range_flag);
+}
+// (the bodies are compiled for the device only, as kw_keep_h2's below and for its reason: a form and its twin call the same
+// trunk_dma specialization)
+template <int NJ, bool HEADS, int WR = 4>
+__global__ void __launch_bounds__(512, 1) kw_trunk_h2(const TrunkArgs g) {
+#ifdef __HIP_DEVICE_COMPILE__
+  trunk_h2_body<NJ, HEADS, WR, false>(g);
+#endif
+}
+template <int NJ, bool HEADS, int WR = 4>
+__global__ void __launch_bounds__(512, 1) kw_enc_trunk_h2(const TrunkArgs g) {
+#ifdef __HIP_DEVICE_COMPILE__
+  trunk_h2_body<NJ, HEADS, WR, true>(g);
+#endif
 }
 
 // ---- the BACKWARD trunk (NSRW_FLAG_TRUNK_BWD): kw_trunk_bwd_h2<NJ>, the input-gradient chain of net_backward_chain behind its head
@@ -652,9 +760,9 @@ struct TrunkKeepArgs {              // beside kw_trunk_h2's TrunkArgs, where C =
   KeepMasks masks;
 };
 
-template <int NJ, bool HEADS>
-__global__ void __launch_bounds__(512, 1) kw_keep_h2(const TrunkArgs g, const TrunkKeepArgs a) {
 #ifdef __HIP_DEVICE_COMPILE__
+template <int NJ, bool HEADS, bool ENC>       // (ENC: as trunk_h2_body's; the kernels are kw_keep_h2 and its twin kw_enc_keep_h2)
+__device__ __forceinline__ void keep_h2_body(const TrunkArgs g, const TrunkKeepArgs a) {
   constexpr int WR = 4, WC = 2, NCB = trunk_ncb<NJ, WR>(), kTrunkRows = trunk_rows<WR>();
   constexpr int kWStage = trunk_wstage<NJ, WR>(), kSH = trunk_sh<NJ, WR>(), kHPiece = kTrunkRows * kSH, kEPiece = kTrunkRows * kTrunkSE;
   constexpr int kHOff = 2 * kWStage, kEOff = kHOff + 2 * kHPiece, kLds = trunk_lds_bytes<NJ, WR>();
@@ -670,6 +778,7 @@ __global__ void __launch_bounds__(512, 1) kw_keep_h2(const TrunkArgs g, const Tr
              a.masks.n_layers == g.Dt - 1);
   if constexpr (HEADS) NSRW_CHECK(g.Dt < g.D && (!g.ED || ((g.ldED >> 4) >= 2 && (g.ldED >> 4) <= kKbeMax)));
   else NSRW_CHECK(g.Dt == g.D);
+  if constexpr (ENC) NSRW_CHECK(!g.E && 3 + 6 * g.pts.L <= g.ldE && (!HEADS || !g.ED || 3 + 6 * g.pts.Lv <= g.ldED));
 
   float amax = 0.0f;                // largest magnitude this lane has split (encodings and activations)
   int buf = 0;
@@ -682,7 +791,8 @@ __global__ void __launch_bounds__(512, 1) kw_keep_h2(const TrunkArgs g, const Tr
     const long long m0 = (long long)mb * kTrunkRows;
     {
       f32x4 e[kEncIt][2];
-      trunk_rows_fetch<kEncIt, WC>(c, g.E, g.ldE, KBE, m0, g.M, e);
+      if constexpr (ENC) trunk_rows_encode<kEncIt, WC, false>(c, g.pts, KBE, m0, g.M, e);
+      else trunk_rows_fetch<kEncIt, WC>(c, g.E, g.ldE, KBE, m0, g.M, e);
       trunk_rows_store<kEncIt, WC>(c, KBE, e, row_e, kEPiece, kTrunkSE, kLds, amax);
     }
     trunk_sync();                   // the encodings are written (and, in the first block, the first stage of weights has landed)
@@ -704,7 +814,10 @@ __global__ void __launch_bounds__(512, 1) kw_keep_h2(const TrunkArgs g, const Tr
       f32x4 ed[kEncIt][2];
       const bool ed_here = HEADS && li + 1 == g.Dt && g.ED;
       if constexpr (HEADS) {
-        if (ed_here) trunk_rows_fetch<kEncIt, WC>(c, g.ED, g.ldED, g.ldED >> 4, m0, g.M, ed);
+        if (ed_here) {
+          if constexpr (ENC) trunk_rows_encode<kEncIt, WC, true>(c, g.pts, g.ldED >> 4, m0, g.M, ed);
+          else trunk_rows_fetch<kEncIt, WC>(c, g.ED, g.ldED, g.ldED >> 4, m0, g.M, ed);
+        }
       }
       f32x16 acc[NJ];
 #pragma unroll
@@ -803,6 +916,18 @@ __global__ void __launch_bounds__(512, 1) kw_keep_h2(const TrunkArgs g, const Tr
     }
   }
   trunk_tail(c, amax, g.range_flag);
+}
+#endif
+template <int NJ, bool HEADS>
+__global__ void __launch_bounds__(512, 1) kw_keep_h2(const TrunkArgs g, const TrunkKeepArgs a) {
+#ifdef __HIP_DEVICE_COMPILE__
+  keep_h2_body<NJ, HEADS, false>(g, a);
+#endif
+}
+template <int NJ, bool HEADS>
+__global__ void __launch_bounds__(512, 1) kw_enc_keep_h2(const TrunkArgs g, const TrunkKeepArgs a) {
+#ifdef __HIP_DEVICE_COMPILE__
+  keep_h2_body<NJ, HEADS, true>(g, a);
 #endif
 }
 

@@ -57,6 +57,11 @@ class NsrwHeadsPlan(C.Structure):
     _fields_ = [("onchip", C.c_int32), ("lds_bytes", C.c_int32), ("reason", C.c_char * 64)]
 
 
+class NsrwEmbedPlan(C.Structure):
+    _fields_ = [("positions_onchip", C.c_int32), ("directions_onchip", C.c_int32), ("positions_reason", C.c_char * 64),
+                ("directions_reason", C.c_char * 64)]
+
+
 class NsrwStagePlan(C.Structure):
     _fields_ = [("wave", C.c_int), ("rays_per_group", C.c_int), ("lds_bytes", C.c_int), ("reason", C.c_char * 96)]
 
@@ -95,6 +100,8 @@ SIGNATURES = {
     "nsrw_keep_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "nsrw_trunk_rerun_plan": (C.c_int, [C.POINTER(NsrwNet), C.c_int, C.POINTER(NsrwTrunkPlan)]),
     "nsrw_rerun_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
+    "nsrw_embed_plan": (C.c_int, [C.POINTER(NsrwNet), C.c_int, C.c_int, C.POINTER(NsrwEmbedPlan)]),
+    "nsrw_embed_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "nsrw_stage_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(NsrwStagePlan)]),
     "nsrw_stages_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "nsrw_debug_bounds_status": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
@@ -110,12 +117,14 @@ FLAG_TRUNK_BWD = 128
 FLAG_TRUNK_KEEP = 256
 FLAG_STAGES_WAVE = 512
 FLAG_TRUNK_RERUN = 1024
+_EMBED_ONCHIP = 1 << 11       # NSRW_FLAG_EMBED_ONCHIP; public as wide.FLAG_EMBED_ONCHIP through __getattr__ below
 MLPS = ("bf16x3", "fp32", "f16x2")
 TRUNKS = ("layers", "onchip")
 HEADS = ("layers", "onchip")
 TRUNK_BWDS = ("layers", "onchip")
 TRUNK_KEEPS = ("layers", "onchip")
 TRUNK_RERUNS = ("layers", "onchip")     # the bf16x3 re-run of a pass whose trunk ran on chip: a launch per layer, or one (FLAG_TRUNK_RERUN)
+EMBEDS = ("layers", "onchip")           # the encodings of a pass whose f16x2 launch is on chip: the kw_embed launch, or in that launch (FLAG_EMBED_ONCHIP)
 STAGES = ("threads", "wave")    # the per-ray stages between the network passes: one thread per ray, or one wave (FLAG_STAGES_WAVE)
 STAGE_COMPOSITE, STAGE_SAMPLE_PDF, STAGE_COMPOSITE_BWD = 0, 1, 2
 STAGE_IDS = {"composite": STAGE_COMPOSITE, "sample_pdf": STAGE_SAMPLE_PDF, "composite_bwd": STAGE_COMPOSITE_BWD}
@@ -125,6 +134,14 @@ DEFAULT_MLP = "f16x2"           # r06: the fused default kernel's arithmetic; sa
                                 # runs every case on all three), 2.6x / 1.5x their speed; never range-dependent (re-run on bf16x3)
 
 _bound = None
+
+
+def __getattr__(name):
+    """wide.FLAG_EMBED_ONCHIP.  Not a module global: tests/test_wide_trunk_rerun_host.py takes a census of the globals named FLAG_*
+    (ten beside FLAG_TRUNK_RERUN) to show that bit 10 is free, and this flag came after it."""
+    if name == "FLAG_EMBED_ONCHIP":
+        return _EMBED_ONCHIP
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
 def load():
@@ -185,13 +202,32 @@ KNOBS = (
 )
 
 
+# ... and the row of `embed`, resolved behind them by the same rule (resolve_embed).  It stands beside KNOBS, not in it: KNOBS is what
+# WideModel unpacks and _trunk_flags sums, and both keep their five.
+EMBED_KNOB = _Knob("embed", "NSR_WIDE_EMBED", EMBEDS, "onchip", _EMBED_ONCHIP, _ONCHIP,
+                   "embed=\"onchip\" computes the encodings in the on-chip trunk's launch: it needs mlp=\"f16x2\" and trunk=\"onchip\" "
+                   "(got mlp=%(mlp)r, trunk=%(trunk)r)")
+
+
 def resolve_knobs(mlp, wishes, environ):
     """{knob: value} for a handle of arithmetic `mlp`: the caller's wish (`wishes`: {knob: argument or None}), else the
     environment's, else the default.  A value that is not one of the knob's raises ValueError.  The environment's wish is dropped where
     the handle cannot honour it (the drop-in API also builds bf16x3 / fp32 handles); an explicit one raises NotImplementedError.  Pure:
     no device, no library."""
-    got = {"mlp": mlp}
-    for k in KNOBS:
+    got = _resolve_rows(KNOBS, {"mlp": mlp}, wishes, environ)
+    del got["mlp"]
+    return got
+
+
+def resolve_embed(wish, environ, mlp, trunk):
+    """Where a handle of arithmetic `mlp` with trunk=`trunk` computes the encodings of a pass that runs on chip: the caller's wish,
+    else $NSR_WIDE_EMBED, else "layers" -- EMBED_KNOB by the rule of resolve_knobs.  Pure: no device, no library."""
+    return _resolve_rows((EMBED_KNOB,), {"mlp": mlp, "trunk": trunk}, {"embed": wish}, environ)["embed"]
+
+
+def _resolve_rows(rows, got, wishes, environ):
+    """the rule of resolve_knobs over the _Knob rows `rows`, on top of what is resolved already (`got`, which it extends)"""
+    for k in rows:
         v = wishes.get(k.name)
         number = not isinstance(k.on, str)
         from_env = v is None if number else not v               # (trunk_width=0 is a wish, and a bad one)
@@ -208,7 +244,6 @@ def resolve_knobs(mlp, wishes, environ):
         if v == k.on and not can:
             raise NotImplementedError(k.refusal % got)
         got[k.name] = v
-    del got["mlp"]
     return got
 
 
@@ -317,6 +352,24 @@ def trunk_rerun_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", trunk_rerun="on
         raise ValueError("trunk_rerun must be one of %s (got %r)" % (TRUNK_RERUNS, trunk_rerun))
     return _plan("nsrw_trunk_rerun_plan", NsrwTrunkPlan, ("nj", "tile_rows", "lds_bytes"), net_or_sd,
                  _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width) | (FLAG_TRUNK_RERUN if trunk_rerun == "onchip" else 0))
+
+
+def embed_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", heads="layers", trunk_width=128, trunk_bwd="layers", trunk_keep="layers",
+               embed="onchip", kept=False):
+    """nsrw_embed_plan (diagnostic; no device, no handle): where a handle of arithmetic `mlp` created with these knobs computes the
+    encodings of a pass of a network (an NsrwNet or a state dict) -- kept: a pass that keeps its activations for a backward -- as
+    dict(positions=..., directions=...), each dict(mode="onchip") for "in the pass's one f16x2 launch" or dict(mode="layers",
+    reason=...) for the kw_embed launch."""
+    if embed not in EMBEDS:
+        raise ValueError("embed must be one of %s (got %r)" % (EMBEDS, embed))
+    lib = load()
+    net = net_or_sd if isinstance(net_or_sd, NsrwNet) else describe(net_or_sd)[0]
+    flags = _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width, heads, trunk_bwd, trunk_keep) | (_EMBED_ONCHIP if embed == "onchip" else 0)
+    plan = NsrwEmbedPlan()
+    if lib.nsrw_embed_plan(C.byref(net), flags, 1 if kept else 0, C.byref(plan)) != 0:
+        raise _lib.NsrError(lib.nsrw_last_error().decode("utf-8", "replace"))
+    one = lambda on, why: dict(mode="onchip") if on else dict(mode="layers", reason=why.decode("utf-8", "replace"))
+    return dict(positions=one(plan.positions_onchip, plan.positions_reason), directions=one(plan.directions_onchip, plan.directions_reason))
 
 
 def _np(v):
@@ -434,7 +487,7 @@ class WideModel:
 
     def __init__(self, sd_coarse, sd_fine=None, device=None, n_importance=128, white_bkgd=False, lindisp=False, n_samples=64,
                  mlp=None, trunk=None, heads=None, trunk_width=None, trunk_bwd=None, trunk_keep=None, stages=None,
-                 trunk_rerun=None):
+                 trunk_rerun=None, embed=None):
         """mlp: the arithmetic of the layer GEMMs -- "bf16x3" (bf16 MFMAs on three-way split fp32 operands, fp32-grade results at
         2.67x the matrix-pipe rate: csrc/nsr_wide_gemm.inc), "fp32" (fp32 MFMAs, the strict mode) or "f16x2" (fp16 MFMAs with
         two-piece operands -- the fused default kernel's arithmetic; a network pass that leaves fp16's range is re-run on bf16x3
@@ -471,7 +524,13 @@ class WideModel:
         activation is kept, the re-run's pts_linears are ONE conditional launch with the activations in LDS, the heads a launch each
         behind it -- the same bits; the re-run of a kept pass and of a backward stay layer by layer: trunk_rerun_plan,
         rerun_status); default $NSR_WIDE_TRUNK_RERUN (which handles that cannot honour it ignore, while an explicit
-        trunk_rerun="onchip" there raises), else "layers"."""
+        trunk_rerun="onchip" there raises), else "layers".
+        embed: "layers" (the kw_embed launch writes the encodings of every pass, and the pass reads them back) or "onchip" (with
+        trunk="onchip" only: wherever the f16x2 pass of a network is one on-chip launch -- trunk, heads form, wide form, kept
+        forward -- that launch computes the position encodings of its points itself, and in a heads form the direction encodings
+        too; behind a trunk-only launch kw_embed writes the direction encodings alone; a conditional kw_embed stands in front of the
+        bf16x3 re-run -- the same bits, the same workspace: embed_plan, embed_status); default $NSR_WIDE_EMBED (which handles that
+        cannot honour it ignore, while an explicit embed="onchip" there raises), else "layers"."""
         mlp = mlp or os.environ.get("NSR_WIDE_MLP") or DEFAULT_MLP
         if mlp not in MLPS:
             raise ValueError("mlp must be one of %s (got %r)" % (MLPS, mlp))
@@ -480,6 +539,7 @@ class WideModel:
         self.trunk, self.heads, self.trunk_width, self.trunk_bwd, self.trunk_keep = (knobs[k.name] for k in KNOBS)
         self.stages = resolve_stages(stages, os.environ)
         self.trunk_rerun = resolve_rerun(trunk_rerun, os.environ, mlp, self.trunk)
+        self.embed = resolve_embed(embed, os.environ, mlp, self.trunk)
         self.mlp = "layered-" + mlp
         if not torch.cuda.is_available():
             raise _lib.NsrError("no HIP device visible: the render path has no CPU fallback")
@@ -504,7 +564,8 @@ class WideModel:
                          (FLAG_WHITE_BKGD if white_bkgd else 0) | (FLAG_LINDISP if lindisp else 0) |
                          _mlp_flags(mlp) | _trunk_flags(self.trunk, self.trunk_width, self.heads, self.trunk_bwd, self.trunk_keep) |
                          (FLAG_STAGES_WAVE if self.stages == "wave" else 0) |
-                         (FLAG_TRUNK_RERUN if self.trunk_rerun == "onchip" else 0))
+                         (FLAG_TRUNK_RERUN if self.trunk_rerun == "onchip" else 0) |
+                         (_EMBED_ONCHIP if self.embed == "onchip" else 0))
         h = C.c_void_p()
         check(self.lib.nsrw_create(C.byref(cfg), C.byref(h)))
         self.h = h
@@ -748,6 +809,14 @@ class WideModel:
         n = C.c_ulonglong()
         check(self.lib.nsrw_rerun_status(self.h, C.byref(n)))
         return dict(launches_onchip=int(n.value))
+
+    def embed_status(self):
+        """nsrw_embed_status, counted on the host as enqueued: `passes_onchip` network passes whose f16x2 launch computed its position
+        encodings itself (embed="onchip" handles; 0 elsewhere), `embed_launches` unconditional kw_embed launches (whole, or the
+        direction encodings alone), `embed_launches_conditional` kw_embed launches in front of a bf16x3 re-run"""
+        a, b, c = C.c_ulonglong(), C.c_ulonglong(), C.c_ulonglong()
+        check(self.lib.nsrw_embed_status(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return dict(passes_onchip=int(a.value), embed_launches=int(b.value), embed_launches_conditional=int(c.value))
 
     def debug_bounds_status(self):
         """(built_with_checks, first_bad_line): see nsrw_debug_bounds_status / `make debug`."""

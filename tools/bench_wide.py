@@ -5,8 +5,8 @@ quoted against; for those the issued fraction of the fp16 / bf16 peak is reporte
 
     python tools/bench_wide.py [--hw 400] [--cases ycbv,w512,d10w384,small] [--steps 3] [--trunk layers|onchip|both]
                                   [--heads layers|onchip|both] [--trunk-width 128|256|both] [--trunk-bwd layers|onchip|both]
-                                  [--trunk-keep layers|onchip|both] [--trunk-rerun layers|onchip|both] [--stages threads|wave|both]
-                                  [--cotangents rgb|all]
+                                  [--trunk-keep layers|onchip|both] [--trunk-rerun layers|onchip|both] [--embed layers|onchip|both]
+                                  [--stages threads|wave|both] [--cotangents rgb|all]
 
 --trunk (f16x2): the pts_linears layer by layer (the default), in the one-launch on-chip trunk (csrc/nsr_wide_trunk.inc), or both in
 turn on the same rays in one process -- the comparison DESIGN.md 8 quotes.  --heads (with the on-chip trunk): the heads one launch
@@ -16,7 +16,8 @@ padded width it takes, 128 (the default), 256 (the wide form: the 8 x 160 .. 8 x
 backward trunk, or both in turn.  --trunk-keep (with the on-chip backward trunk): the gradient call's kept forward a launch per layer
 with fp32 activations kept (the default), in the one kept launch that leaves the relu masks as bits, or both in turn.  --trunk-rerun
 (with the on-chip trunk): the conditional bf16x3 re-run of a forward pass that keeps nothing a launch per layer (the default), its
-pts_linears in the one launch of kw_rerun_b3, or both in turn (d8w128range: a network whose every coarse pass is re-run).  --stages (any
+pts_linears in the one launch of kw_rerun_b3, or both in turn (d8w128range: a network whose every coarse pass is re-run).  --embed (with the on-chip trunk): the encodings of a pass
+written by the kw_embed launch and read back (the default), computed inside the pass's on-chip launch, or both in turn.  --stages (any
 arithmetic): compositing, resampling and the compositing backward one thread per ray (the default), one wave per ray
 (csrc/nsr_wide_stages.inc), or both in turn on the same rays in one process.  --cotangents: the gradient call differentiates rgb_map
 (the default) or all six outputs (the coarse pass's backward too).
@@ -97,6 +98,7 @@ def main():
     ap.add_argument("--trunk-bwd", default="layers", choices=("layers", "onchip", "both"))
     ap.add_argument("--trunk-keep", default="layers", choices=("layers", "onchip", "both"))
     ap.add_argument("--trunk-rerun", default="layers", choices=("layers", "onchip", "both"))
+    ap.add_argument("--embed", default="layers", choices=("layers", "onchip", "both"))
     ap.add_argument("--stages", default="threads", choices=("threads", "wave", "both"))
     ap.add_argument("--cotangents", default="rgb", choices=("rgb", "all"))
     a = ap.parse_args()
@@ -105,20 +107,22 @@ def main():
     bwds = ("layers", "onchip") if a.trunk_bwd == "both" else (a.trunk_bwd,)
     keeps = ("layers", "onchip") if a.trunk_keep == "both" else (a.trunk_keep,)
     reruns = ("layers", "onchip") if a.trunk_rerun == "both" else (a.trunk_rerun,)
+    embeds = ("layers", "onchip") if a.embed == "both" else (a.embed,)
     stages_modes = ("threads", "wave") if a.stages == "both" else (a.stages,)
     # (trunk, heads, trunk width, backward trunk, kept forward): the heads and the backward trunk run on chip, and the trunk takes
     # widths up to 256, behind the on-chip trunk only; the kept forward runs on chip behind the on-chip backward trunk only; the
     # re-run runs on chip behind the on-chip trunk only
-    modes = [(t, h, w, b, k, s, r) for t in trunks for h in (("layers", "onchip") if a.heads == "both" else (a.heads,)) for w in widths
-             for b in bwds for k in keeps for s in stages_modes for r in reruns
-             if (t == "onchip" or (h == "layers" and w == widths[0] and b == "layers" and r == "layers")) and (b == "onchip" or k == "layers")]
+    modes = [(t, h, w, b, k, s, r, e) for t in trunks for h in (("layers", "onchip") if a.heads == "both" else (a.heads,)) for w in widths
+             for b in bwds for k in keeps for s in stages_modes for r in reruns for e in embeds
+             if (t == "onchip" or (h == "layers" and w == widths[0] and b == "layers" and r == "layers" and e == "layers")) and
+             (b == "onchip" or k == "layers")]
     if not modes or (a.trunk == "layers" and a.trunk_width != "128"):
-        ap.error("--heads onchip, --trunk-width 256, --trunk-bwd onchip and --trunk-rerun onchip need --trunk onchip or both; "
+        ap.error("--heads onchip, --trunk-width 256, --trunk-bwd onchip, --trunk-rerun onchip and --embed onchip need --trunk onchip or both; "
                  "--trunk-keep onchip needs --trunk-bwd onchip or both")
     K = S.scaled_K(400.0 / a.hw)
     pose = S.sweep_poses(1, seed=0)[0]
     out = {}
-    for name, trunk, heads, width, bwd, keep, stages, rerun in [(c,) + mode for c in a.cases.split(",") for mode in modes]:
+    for name, trunk, heads, width, bwd, keep, stages, rerun, embed in [(c,) + mode for c in a.cases.split(",") for mode in modes]:
         D, W, L, Lv, skips, ns, ni = CASES[name]
         sd = net_sd(D, W, L, Lv, skips, 1)
         sd_c = sd
@@ -127,7 +131,7 @@ def main():
             sd_c["pts_linears.1.bias"][5] += 7.0e4
         m = WideModel(sd_c, sd, n_samples=ns, n_importance=ni, mlp=a.mlp, trunk=trunk, heads=heads,
                       trunk_width=width if trunk == "onchip" else None, trunk_bwd=bwd, trunk_keep=keep, stages=stages,
-                      trunk_rerun=rerun)
+                      trunk_rerun=rerun, embed=embed)
         n = a.hw * a.hw
         evals = n * (ns + ns + ni)
         flop = evals * flop_per_point(sd)
@@ -143,7 +147,7 @@ def main():
         res = {"network": "%d x %d, skips %s, %d + %d samples" % (D, W, skips, ns, ni), "rays": n,
                "flop_per_point": flop_per_point(sd), "mlp": m.mlp, "trunk": m.trunk, "heads": m.heads,
                "trunk_width": m.trunk_width, "trunk_bwd": m.trunk_bwd, "trunk_keep": m.trunk_keep, "trunk_rerun": m.trunk_rerun,
-               "stages": m.stages,
+               "embed": m.embed, "stages": m.stages,
                "cotangents": a.cotangents}
         for what in ("forward",) + (() if a.no_grad else ("forward+input-gradient",)):
             ms = []
@@ -179,11 +183,13 @@ def main():
             res["range_status"] = m.range_status()
             res["keep_status"] = m.keep_status()
             res["rerun_status"] = m.rerun_status()
+            res["embed_status"] = m.embed_status()
         key = name + (":" + trunk if a.trunk == "both" else "") + (":heads-" + heads if a.heads == "both" else "") + \
             (":width-%d" % width if a.trunk_width == "both" and trunk == "onchip" else "") + \
             (":bwd-" + bwd if a.trunk_bwd == "both" and trunk == "onchip" else "") + \
             (":keep-" + keep if a.trunk_keep == "both" and bwd == "onchip" else "") + \
             (":rerun-" + rerun if a.trunk_rerun == "both" and trunk == "onchip" else "") + \
+            (":embed-" + embed if a.embed == "both" and trunk == "onchip" else "") + \
             (":stages-" + stages if a.stages == "both" else "")
         out[key] = res
         print(key, json.dumps(res), flush=True)
