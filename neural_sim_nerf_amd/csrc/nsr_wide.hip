@@ -1329,18 +1329,24 @@ std::vector<TrunkLayer> trunk_table(const Net& n, int* fwd_rows, int* bwd_rows, 
 // or (the heads form) the heads too: k.E, k.ED -> k.RAW, where net_forward_chain's head launches leave them
 // (src: the pass's points, where the launch computes its encodings itself -- the ENC twin of the form, n.onchip.embed; else nullptr)
 TrunkPoints trunk_points(const EmbedArgs& a) { return TrunkPoints{a.rays_o, a.rays_d, a.z, a.vd, a.pts, a.dirs, a.S, a.L, a.Lv}; }
-void trunk_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P, const EmbedArgs* src) {
-  const TrunkForm& f = src ? *n.onchip.embed[0].form : *n.onchip.forward();
+// What the one-launch forwards share of their TrunkArgs: image and bias of `arith`, `rows` rows of the table from `layers` on, the
+// network's shape, the P points and their encodings (k.E, or src's points).  A launch adds C and what else is its own.
+TrunkArgs trunk_args(const Net& n, const Chunk& k, long long P, int arith, const TrunkLayer* layers, int rows, const EmbedArgs* src) {
   TrunkArgs t{};
   t.E = src ? nullptr : k.E; t.ldE = n.Ci;
   if (src) t.pts = trunk_points(*src);
-  t.img = n.dImg[kH2]; t.img_bytes = (unsigned)n.img_bytes[kH2];
+  t.img = n.dImg[arith]; t.img_bytes = (unsigned)n.img_bytes[arith];
   t.bias = n.dBias; t.bias_floats = n.bias_floats;
-  t.layers = n.dTrunk; t.D = n.trunk_rows; t.Dt = n.d.D;
-  t.C = k.H[(n.d.D - 1) & 1]; t.Wp = n.Wp;
+  t.layers = layers; t.D = rows; t.Dt = n.d.D;
+  t.Wp = n.Wp; t.M = P;
+  return t;
+}
+void trunk_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P, const EmbedArgs* src) {
+  const TrunkForm& f = src ? *n.onchip.embed[0].form : *n.onchip.forward();
+  TrunkArgs t = trunk_args(n, k, P, kH2, n.dTrunk, n.trunk_rows, src);
+  t.C = k.H[(n.d.D - 1) & 1];
   t.ED = n.d.use_viewdirs ? k.ED : nullptr; t.ldED = n.Cv;
   t.RAW = k.RAW;
-  t.M = P;
   t.range_flag = cfg.d_range;
   hipLaunchKernelGGL(f.fwd, trunk_grid(cfg, f, P), dim3(kTrunkThreads), 0, st, t);
 }
@@ -1353,14 +1359,8 @@ bool rerun_pass(Run run, const Net& n, long long P) {
 }
 void rerun_launch(const GemmCfg& cfg, Run run, hipStream_t st, const Net& n, const Chunk& k, long long P) {
   const TrunkForm& f = *n.onchip.rerun.form;
-  TrunkArgs t{};
-  t.E = k.E; t.ldE = n.Ci;
-  t.img = n.dImg[kB3]; t.img_bytes = (unsigned)n.img_bytes[kB3];
-  t.bias = n.dBias; t.bias_floats = n.bias_floats;
-  t.layers = n.dTrunk + n.trunk_rows + n.trunk_bwd_rows; t.D = n.trunk_rerun_rows; t.Dt = n.d.D;
-  t.C = k.H[(n.d.D - 1) & 1]; t.Wp = n.Wp;
-  t.M = P;
-  t.range_flag = nullptr;             // (only read, as run_if)
+  TrunkArgs t = trunk_args(n, k, P, kB3, n.dTrunk + n.trunk_rows + n.trunk_bwd_rows, n.trunk_rerun_rows, nullptr);
+  t.C = k.H[(n.d.D - 1) & 1];         // (no range_flag: the range word is only read, as run_if)
   hipLaunchKernelGGL(f.rerun, trunk_grid(cfg, f, P), dim3(kTrunkThreads), 0, st, t, run.run_if);
   if (cfg.rerun_launches) ++*cfg.rerun_launches;
 }
@@ -1377,16 +1377,10 @@ int keep_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k
   const TrunkForm& f = src ? *n.onchip.embed[1].form : *n.onchip.keep.form;
   if (!k.MB) return fail("nsrw: internal error: a kept on-chip pass without a mask buffer");
   TrunkKeepArgs a{};
-  TrunkArgs t{};
-  t.E = src ? nullptr : k.E; t.ldE = n.Ci;
-  if (src) t.pts = trunk_points(*src);
-  t.img = n.dImg[kH2]; t.img_bytes = (unsigned)n.img_bytes[kH2];
-  t.bias = n.dBias; t.bias_floats = n.bias_floats;
-  t.layers = n.dTrunk; t.D = n.trunk_rows; t.Dt = n.d.D;
-  t.C = k.H[n.d.D - 1]; t.Wp = n.Wp;
+  TrunkArgs t = trunk_args(n, k, P, kH2, n.dTrunk, n.trunk_rows, src);
+  t.C = k.H[n.d.D - 1];
   t.ED = n.d.use_viewdirs ? k.ED : nullptr; t.ldED = n.Cv;
   t.RAW = k.RAW;
-  t.M = P;
   t.range_flag = cfg.d_range;
   a.HV = k.HV; a.ldHV = n.W2p;
   a.masks = keep_masks(n, k, P);
@@ -1395,11 +1389,19 @@ int keep_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k
   return 0;
 }
 
+// The kernels that read or write the kept activations k.H[0 .. D - 2] address them as one array of matrices, layer l at k.H[0] +
+// l * ldH: carve_chunk lays them out at one stride
+int kept_stride(const Net& n, const Chunk& k, long long* ldH) {
+  *ldH = k.H[1] - k.H[0];
+  for (int i = 0; i + 1 < n.d.D; ++i)
+    if (k.H[i] != k.H[0] + i * *ldH) return fail("nsrw: internal error: the kept activations are not equally spaced");
+  return 0;
+}
+
 // kw_mask_pack / kw_mask_unpack over the masks of a kept pass, conditional on the range flag like the bf16x3 chain's launches
 int mask_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P, bool pack) {
-  const long long ldH = k.H[1] - k.H[0];
-  for (int i = 0; i + 1 < n.d.D; ++i)
-    if (k.H[i] != k.H[0] + i * ldH) return fail("nsrw: internal error: the kept activations are not equally spaced");
+  long long ldH;
+  if (kept_stride(n, k, &ldH)) return 1;
   MaskArgs g{};
   g.H0 = k.H[0]; g.ldH = ldH; g.Wp = n.Wp; g.M = P;
   g.masks = keep_masks(n, k, P);
@@ -1510,10 +1512,8 @@ int net_forward(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k
 int trunk_bwd_launch(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P) {
   const int D = n.d.D;
   const TrunkForm& f = *n.onchip.bwd.form;
-  // the kernel addresses the kept activations as one array of D - 1 matrices: carve_chunk lays them out at one stride
-  const long long ldH = k.H[1] - k.H[0];
-  for (int i = 0; i + 1 < D; ++i)
-    if (k.H[i] != k.H[0] + i * ldH) return fail("nsrw: internal error: the kept activations are not equally spaced");
+  long long ldH;
+  if (kept_stride(n, k, &ldH)) return 1;
   TrunkBwdArgs t{};
   t.G = k.G0; t.Wp = n.Wp;
   t.img = n.dImg[kH2]; t.img_bytes = (unsigned)n.img_bytes[kH2];

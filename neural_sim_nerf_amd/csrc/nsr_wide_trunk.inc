@@ -1,10 +1,13 @@
 // nsr_wide_trunk.inc -- the ON-CHIP kernels of the layered renderer's f16x2 arithmetic: persistent launches that run a whole chain of
 // layers on a block of points, with the value between two layers in LDS instead of HBM.  Included inside namespace nsrw
 // (nsr_wide.hip), after nsr_wide_gemm.inc, whose arithmetic they restate per output element and must reproduce BIT FOR BIT
-// (tests/test_gpu_wide_trunk.py, test_gpu_wide_heads.py, test_gpu_wide_trunk_bwd.py).  Two __global__ templates, kw_trunk_h2<NJ,
-// HEADS, WR> (forward) and kw_trunk_bwd_h2<NJ> (input-gradient backward), made of ONE set of building blocks; a kernel body is a
-// prologue, the block loop, the row loop and its own epilogue.  (At the end of the file: kw_rerun_b3<NJ, WR>, the forward trunk once more
-// on the bf16x3 arithmetic, for the conditional re-run of a pass that left fp16's range; the blocks that count pieces take NP = 2 or 3.)
+// (tests/test_gpu_wide_trunk.py, test_gpu_wide_heads.py, test_gpu_wide_trunk_bwd.py).  TWO f16x2 bodies made of ONE set of building
+// blocks, each a prologue, the block loop, the row loop -- the next row's fields, the stages with trunk_dma one stage ahead, the
+// epilogue, the barrier -- stated once: trunk_h2_body (forward), behind the kernels kw_trunk_h2<NJ, HEADS, WR>, kw_keep_h2<NJ, HEADS>
+// and their kw_enc_ twins, and trunk_bwd_body (input-gradient backward), behind kw_trunk_bwd_h2<NJ> and kw_keep_bwd_h2<NJ>; what a
+// kernel of a body has of its own stands behind an `if constexpr` of the body.  (At the end of the file: kw_rerun_b3<NJ, WR>, the
+// forward trunk once more on the bf16x3 arithmetic, for the conditional re-run of a pass that left fp16's range: three pieces, no
+// cscale, no amax -- a body of its own on the same blocks; the blocks that count pieces take NP = 2 or 3.)
 //
 // The building blocks (above the kernels, each stated once):
 //   * the row table.  A launch walks a table of TrunkLayer rows (Net::dTrunk): per row the weight image, K as k16 blocks of the
@@ -35,6 +38,8 @@
 //   * trunk_rows_encode (NSRW_FLAG_EMBED_ONCHIP; the kw_enc_ twins of the forward and kept kernels): the same registers as
 //     trunk_rows_fetch, computed from the block's points by kw_embed's own functions instead of fetched -- kw_embed's bits, and
 //     trunk_rows_store behind it as it was.
+//   * NSRW_ROWS_OUT: the fp32 epilogue store of a lane's 16 accumulator rows to an [M, ld] matrix (C, the kept H[D - 1] and HV),
+//     without a look at the row inside M, guarded in the last block.
 //   * trunk_tail: no LDS-DMA outlives the workgroup; the range flag.
 //
 // kw_trunk_h2<NJ, HEADS, WR>: all D pts_linears layers (RH:99-107) of a network of packed width Wp <= 128 on a block of 128 points
@@ -62,11 +67,12 @@
 // issue no MFMA (their output would be dropped anyway: a column block behind Wp holds zero weights).  LDS: weights 2 x 32 KiB,
 // activation 2 x 64 x 528 B, encoding 2 x 64 x 208 B = 159 744 B.  Per output element nothing differs from WR = 4, hence the same bits.
 //
-// kw_trunk_bwd_h2<NJ> (NSRW_FLAG_TRUNK_BWD; at the end of this file, where its own rows and epilogue are described): the
+// kw_trunk_bwd_h2<NJ> (NSRW_FLAG_TRUNK_BWD; behind the forward, where its own rows and epilogue are described): the
 // input-gradient chain of net_backward_chain in the shape of the heads form, the gradient in the activation image, no encoding image.
 //
-// kw_keep_h2<NJ, HEADS>, kw_keep_bwd_h2<NJ>, kw_mask_pack, kw_mask_unpack (NSRW_FLAG_TRUNK_KEEP; behind kw_trunk_bwd_h2, where the bit
-// layout of the masks is described): the forward that KEEPS what a backward reads, as one launch, and the backward that reads it.
+// kw_keep_h2<NJ, HEADS>, kw_keep_bwd_h2<NJ>, kw_mask_pack, kw_mask_unpack (NSRW_FLAG_TRUNK_KEEP; the bit layout of the masks stands
+// in front of the forward body): the forward that KEEPS what a backward reads, as one launch -- the forward body with KEEP -- and the
+// backward that reads it -- the backward body with BITS.
 #undef NSRW_FILE_TAG
 #define NSRW_FILE_TAG 200000        /* a failed NSRW_CHECK of this file reports 200000 + its line (nsrw_debug_bounds_status) */
 
@@ -386,14 +392,72 @@ __device__ __forceinline__ void trunk_write_inplace(const TrunkCtx<LDS>& c, cons
   }
 }
 
+// The fp32 epilogue store of an accumulator column: v = the lane's 16 registers of column n -> rows m0 + trunk_acc_row(r, 32 wr,
+// 4 (lane / 32)) of X [M, ld]; a block inside M (`inside`) stores without a look at the row, the last block row by row.
+// A MACRO on purpose.  As a __forceinline__ function (tried: arguments by value and by reference, both paths in one function and
+// one function per path) the kernels that use it no longer compile to the code they had (tools/kernel_asm_diff.py): with both
+// paths in one function the two share their last store, otherwise the kept and the re-run kernels get another accumulator
+// offset and other branches, and the forms of two column blocks another instruction order.
+#define NSRW_ROWS_OUT(c, v, X, ld, n, m0, M, inside)                                                          \
+  do {                                                                                                        \
+    const long long mt = (m0) + 32 * (c).wr + 4 * (c).lh;                                                     \
+    NSRW_CHECK((n) < (ld) && (!(inside) || mt + 27 < (M)));                                                   \
+    float* xp = (X) + mt * (ld) + (n);                                                                        \
+    if (inside) {                                                                                             \
+      _Pragma("unroll") for (int r = 0; r < 16; ++r) xp[trunk_acc_row(r) * (ld)] = (v)[r >> 2][r & 3];        \
+    } else {                                                                                                  \
+      _Pragma("unroll") for (int r = 0; r < 16; ++r)                                                          \
+        if (mt + trunk_acc_row(r) < (M)) xp[trunk_acc_row(r) * (ld)] = (v)[r >> 2][r & 3];                    \
+    }                                                                                                         \
+  } while (0)
+
+// ---- the relu masks of a KEPT pass as bits (NSRW_FLAG_TRUNK_KEEP; written by the kept forward and kw_mask_pack, read by the kept
+// backward and kw_mask_unpack, all below) ------------------------------------------------------------------------------------------
+//
+// THE bit layout of the masks (keep_mask_word): per kept layer l = 0 .. D - 2, block b of 128 points and column block cb = 0 ..
+// Wp / 32 - 1 one 16-bit word per (wave row wr, lane) --
+//   word ((l nblk + b) Wp / 32 + cb) 256 + 64 wr + lane,   bit r = (x > 0) of row 128 b + trunk_acc_row(r, 32 wr, 4 (lane / 32)),
+//                                                                            column 32 cb + lane % 32
+// (x behind relu, so a NaN gives 0): Wp / 8 bytes per point and layer, over whole blocks (nblk = ceil(M / 128): a row >= M has a bit,
+// of its clamped input; the backward does not read it).  A word holds exactly the 16 accumulator registers of the lane that owns
+// (row, column) in either kernel, whichever column blocks cb_of deals to its wave.
+struct KeepMasks {
+  unsigned short* bits;             // the words of every kept layer
+  long long ld;                     // words per layer: nblk * (Wp / 32) * 256
+  int nblk, n_layers;               // blocks of 128 points; kept layers (D - 1)
+};
+__device__ __forceinline__ long long keep_mask_word(const KeepMasks& m, int layer, int blk, int ncb, int cb, int wr, int lane) {
+  NSRW_CHECK(layer >= 0 && layer < m.n_layers && blk >= 0 && blk < m.nblk && cb >= 0 && cb < ncb && wr >= 0 && wr < 4 && lane >= 0 &&
+             lane < 64 && (long long)m.nblk * ncb * 256 == m.ld);
+  return layer * m.ld + ((long long)blk * ncb + cb) * 256 + 64 * wr + lane;
+}
+
 // ---- the FORWARD trunk, and the heads behind it --------------------------------------------------------------------------------------
 
+// ONE body, trunk_h2_body<NJ, HEADS, WR, ENC, KEEP>, behind four kernels: kw_trunk_h2<NJ, HEADS, WR> (ENC = KEEP = false), its twin
+// kw_enc_trunk_h2 (ENC), and the kept pair kw_keep_h2<NJ, HEADS> / kw_enc_keep_h2 (KEEP; WR = 4).
+//
 // ENC (NSRW_FLAG_EMBED_ONCHIP): the block's encodings are computed from its points (trunk_rows_encode) where the other forms fetch
-// g.E -- and, in the heads form, g.ED -- from memory; nothing else differs.  The body is stated once, selected by that template
-// parameter, and has two kernels: kw_trunk_h2<NJ, HEADS, WR> (ENC = false: the code it was, under the name it had) and its twin
-// kw_enc_trunk_h2<NJ, HEADS, WR>.
-template <int NJ, bool HEADS, int WR, bool ENC>
-__device__ __forceinline__ void trunk_h2_body(const TrunkArgs g) {
+// g.E -- and, in the heads form, g.ED -- from memory; nothing else differs.
+//
+// KEEP (NSRW_FLAG_TRUNK_KEEP): a forward pass that keeps its activations for a backward, as ONE launch too.  Row for row the pass
+// that keeps nothing -- the same cadence, the same epilogue arithmetic, the same values split in place and fed to amax -- and in the epilogue it
+// leaves what the backward reads: of the pts_linears rows 0 .. Dt - 2 nothing but the SIGN of each activation, one bit (KeepMasks); of
+// the last pts_linears row the fp32 output in H[D - 1] = g.C (b_head masks by it through a GEMM launch), in either form; in the heads
+// form views_linears.0's fp32 output in HV (b_rgb masks by it).  FA is not written: no backward reads it.
+//
+// (The bodies of this file are compiled for the device only: the host pass of hipcc rejects a SECOND kernel's call of a trunk_dma
+// specialization that another kernel already uses -- the buffer descriptor in its signature is a device type -- and needs nothing
+// of a kernel but its name.)
+struct TrunkKeepArgs {              // beside a kept launch's TrunkArgs, where C = H[D - 1] and Dt = the pts_linears among the rows in either form
+  float* HV; int ldHV;              // heads form: views_linears.0's output [M, ldHV]
+  KeepMasks masks;
+};
+
+#ifdef __HIP_DEVICE_COMPILE__
+template <int NJ, bool HEADS, int WR, bool ENC, bool KEEP>
+__device__ __forceinline__ void trunk_h2_body(const TrunkArgs g, const TrunkKeepArgs a) {
+  static_assert(!KEEP || WR == 4, "the kept forms have blocks of 128 points: the layout of the masks");
   static_assert((WR == 4 || (WR == 2 && NJ == 2 && !HEADS)), "the wide form is trunk-only, two column blocks a wave");
   constexpr int WC = 8 / WR, NCB = trunk_ncb<NJ, WR>(), kTrunkRows = trunk_rows<WR>();
   constexpr int kWStage = trunk_wstage<NJ, WR>(), kSH = trunk_sh<NJ, WR>(), kHPiece = kTrunkRows * kSH, kEPiece = kTrunkRows * kTrunkSE;
@@ -412,6 +476,7 @@ __device__ __forceinline__ void trunk_h2_body(const TrunkArgs g) {
   NSRW_CHECK(KBE >= 2 && KBE <= kKbeMax && KBH >= 2 && KBH <= 2 * NCB && g.D >= 1);
   if constexpr (HEADS) NSRW_CHECK(g.Dt >= 1 && g.Dt < g.D && (!g.ED || ((g.ldED >> 4) >= 2 && (g.ldED >> 4) <= kKbeMax)));
   if constexpr (ENC) NSRW_CHECK(!g.E && 3 + 6 * g.pts.L <= g.ldE && (!HEADS || !g.ED || 3 + 6 * g.pts.Lv <= g.ldED));
+  if constexpr (KEEP) NSRW_CHECK(g.Dt >= 2 && (HEADS || g.Dt == g.D) && a.masks.nblk == mblocks && a.masks.n_layers == g.Dt - 1);
   auto dma = [&](unsigned img_off, int KB, int kb0, int b, int ncb) { trunk_dma<NCB, kNcbVaries>(c, rsrc, g.img_bytes, img_off, KB, kb0, b, ncb); };
 
   float amax = 0.0f;                // largest magnitude this lane has split (encodings and activations)
@@ -489,6 +554,11 @@ __device__ __forceinline__ void trunk_h2_body(const TrunkArgs g) {
       const int dest = HEADS ? trunk_form_dest(L.form) : (li + 1 == g.D ? kTrunkToC : kTrunkToLds);
       const int ncbo = HEADS ? L_ncbo : ncbr;
       const bool inside = m0 + kTrunkRows <= g.M;
+      // KEEP: what a kept pass leaves beside the raw outputs -- the bits of the pts_linears rows 0 .. Dt - 2, the fp32 rows of the last
+      // one (H[D - 1]) and, in the heads form, of views_linears.0 (HV: the one row whose K is [hidden | encoding])
+      const bool to_bits = li + 1 < g.Dt;
+      float* keep_to = li + 1 == g.Dt ? g.C : (HEADS && L_h_first) ? a.HV : nullptr;
+      const int keep_ld = li + 1 == g.Dt ? g.Wp : a.ldHV;
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         const int cb = cb_of(j);
@@ -503,6 +573,16 @@ __device__ __forceinline__ void trunk_h2_body(const TrunkArgs g) {
             if (!HEADS || L_relu) x = (x < 0.0f) ? 0.0f : x;             // NaN stays NaN, as through torch's relu
             v[r >> 2][r & 3] = x;
           }
+          if constexpr (KEEP) {
+            if (to_bits) {
+              unsigned bits = 0u;
+#pragma unroll
+              for (int r = 0; r < 16; ++r) bits |= (v[r >> 2][r & 3] > 0.0f ? 1u : 0u) << r;
+              NSRW_CHECK(cb < ncbr && dest == kTrunkToLds);
+              a.masks.bits[keep_mask_word(a.masks, li, mb, ncbr, cb, c.wr, c.lane)] = (unsigned short)bits;
+            }
+            if (keep_to) NSRW_ROWS_OUT(c, v, keep_to, keep_ld, n, m0, g.M, inside);
+          }
           if (dest == kTrunkToLds) {
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
@@ -510,18 +590,8 @@ __device__ __forceinline__ void trunk_h2_body(const TrunkArgs g) {
               split8_h2(v[2 * hf], v[2 * hf + 1], p, amax);
               trunk_write_inplace<NJ, WR>(c, p, hf, n, kEOff);
             }
-          } else if (!HEADS) {
-            const long long mt = m0 + 32 * c.wr + 4 * c.lh;
-            float* cp = g.C + mt * g.Wp + n;
-            if (inside) {
-              NSRW_CHECK(mt + 27 < g.M && n < g.Wp);
-#pragma unroll
-              for (int r = 0; r < 16; ++r) cp[trunk_acc_row(r) * g.Wp] = v[r >> 2][r & 3];
-            } else {
-#pragma unroll
-              for (int r = 0; r < 16; ++r)
-                if (mt + trunk_acc_row(r) < g.M) cp[trunk_acc_row(r) * g.Wp] = v[r >> 2][r & 3];
-            }
+          } else if (!HEADS) {                                           // (a kept pass has stored its last row above)
+            if constexpr (!KEEP) NSRW_ROWS_OUT(c, v, g.C, g.Wp, n, m0, g.M, inside);
           } else if (n < trunk_store_ncols(L.store)) {                   // a head's few columns of the raw outputs
             const int col0 = trunk_store_col0(L.store), ld = trunk_store_ld(L.store);
             const long long mt = m0 + 32 * c.wr + 4 * c.lh;
@@ -543,18 +613,29 @@ __device__ __forceinline__ void trunk_h2_body(const TrunkArgs g) {
   }
   trunk_tail(c, amax, g.range_flag);
 }
-// (the bodies are compiled for the device only, as kw_keep_h2's below and for its reason: a form and its twin call the same
-// trunk_dma specialization)
+#endif
 template <int NJ, bool HEADS, int WR = 4>
 __global__ void __launch_bounds__(512, 1) kw_trunk_h2(const TrunkArgs g) {
 #ifdef __HIP_DEVICE_COMPILE__
-  trunk_h2_body<NJ, HEADS, WR, false>(g);
+  trunk_h2_body<NJ, HEADS, WR, false, false>(g, TrunkKeepArgs{});
 #endif
 }
 template <int NJ, bool HEADS, int WR = 4>
 __global__ void __launch_bounds__(512, 1) kw_enc_trunk_h2(const TrunkArgs g) {
 #ifdef __HIP_DEVICE_COMPILE__
-  trunk_h2_body<NJ, HEADS, WR, true>(g);
+  trunk_h2_body<NJ, HEADS, WR, true, false>(g, TrunkKeepArgs{});
+#endif
+}
+template <int NJ, bool HEADS>
+__global__ void __launch_bounds__(512, 1) kw_keep_h2(const TrunkArgs g, const TrunkKeepArgs a) {
+#ifdef __HIP_DEVICE_COMPILE__
+  trunk_h2_body<NJ, HEADS, 4, false, true>(g, a);
+#endif
+}
+template <int NJ, bool HEADS>
+__global__ void __launch_bounds__(512, 1) kw_enc_keep_h2(const TrunkArgs g, const TrunkKeepArgs a) {
+#ifdef __HIP_DEVICE_COMPILE__
+  trunk_h2_body<NJ, HEADS, 4, true, true>(g, a);
 #endif
 }
 
@@ -587,8 +668,14 @@ struct TrunkBwdArgs {
 
 template <int NJ> constexpr int trunk_bwd_lds_bytes() { return 2 * trunk_wstage<NJ>() + 2 * trunk_rows<4>() * trunk_sh<NJ>(); }
 
-template <int NJ>
-__global__ void __launch_bounds__(512, 1) kw_trunk_bwd_h2(const TrunkBwdArgs g) {
+// ONE body, trunk_bwd_body<NJ, BITS>, behind two kernels: kw_trunk_bwd_h2<NJ> (BITS = false: the masks are the fp32 activations the
+// per-layer forward kept, as above) and kw_keep_bwd_h2<NJ> (BITS = true, NSRW_FLAG_TRUNK_KEEP: behind a forward kept on chip, which
+// left bits -- KeepMasks, above; g.H0 / g.ldH are not read).  Three things differ: the fetch -- NJ 16-bit words of a lane per row
+// where the fp32 form has 16 NJ dword buffer loads; `live`, the registers of the lane whose row lies inside M (a word has a bit for
+// a row >= M, of its clamped input, where the descriptor's extent gives the fp32 form its 0); and the select, bit r for mask > 0.
+#ifdef __HIP_DEVICE_COMPILE__
+template <int NJ, bool BITS>
+__device__ __forceinline__ void trunk_bwd_body(const TrunkBwdArgs g, const KeepMasks masks) {
   constexpr int NCB = trunk_ncb<NJ>(), kTrunkRows = trunk_rows<4>();
   constexpr int kWStage = trunk_wstage<NJ>(), kSH = trunk_sh<NJ>(), kHPiece = kTrunkRows * kSH;
   constexpr int kHOff = 2 * kWStage, kLds = trunk_bwd_lds_bytes<NJ>();
@@ -600,6 +687,7 @@ __global__ void __launch_bounds__(512, 1) kw_trunk_bwd_h2(const TrunkBwdArgs g) 
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)g.img, 0, (int)g.img_bytes, 0x00020000);
   const int KBH = g.Wp >> 4, ncbh = g.Wp >> 5, ncbe = g.Ci >> 5;
   NSRW_CHECK(KBH >= 2 && KBH <= 2 * NCB && (KBH & 1) == 0 && ncbe >= 1 && ncbe <= NCB && g.R >= 2 && g.n_masks >= 1);
+  if constexpr (BITS) NSRW_CHECK(masks.nblk == mblocks && masks.n_layers == g.n_masks);
   auto dma = [&](unsigned img_off, int kb0, int b, int ncb) { trunk_dma<NCB, true>(c, rsrc, g.img_bytes, img_off, KBH, kb0, b, ncb); };
 
   float amax = 0.0f;                // largest magnitude this lane has split (the incoming g and every masked g2)
@@ -614,6 +702,12 @@ __global__ void __launch_bounds__(512, 1) kw_trunk_bwd_h2(const TrunkBwdArgs g) 
     const int rows_in = g.M - m0 < kTrunkRows ? (int)(g.M - m0) : kTrunkRows;      // the block's rows inside M
     const int voff_m = (32 * c.wr + 4 * c.lh) * g.Wp + c.lrow;          // this lane's first element in a block of masks ...
     const int voff_e = (32 * c.wr + 4 * c.lh) * g.Ci + c.lrow;          // ... and of GEP, from column block 0 (floats)
+    // BITS: the registers of this lane whose row lies inside M: a row >= M has a bit of its clamped input, which must count for nothing
+    unsigned live = 0u;
+    if constexpr (BITS) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) live |= (trunk_acc_row(r, 32 * c.wr, 4 * c.lh) < rows_in ? 1u : 0u) << r;
+    }
     {
       f32x4 e[kGIt][2];
       trunk_rows_fetch<kGIt, 2>(c, g.G, g.Wp, KBH, m0, g.M, e);
@@ -639,11 +733,18 @@ __global__ void __launch_bounds__(512, 1) kw_trunk_bwd_h2(const TrunkBwdArgs g) 
                  (dest == kTrunkToLds ? L_ncbo == ncbh : (dest == kTrunkToGep && L_ncbo == ncbe)));
       // the accumulators of this wave that a column block of the row's output stands behind (cb_of(j) < ncbo: j < na)
       const int na = (L_ncbo - c.wc + 1) >> 1 > NJ ? NJ : (L_ncbo - c.wc + 1) >> 1;
-      // the relu mask of layer L.store at this lane's elements, through a descriptor of the block's rows inside M: branch-free, one
-      // vector offset per lane and a scalar one per element; a row >= M lies behind the extent and reads 0 (its g2 is then 0 and
-      // adds nothing to amax), a column block behind Wp re-reads block 0 (unused)
+      // the relu mask of layer L.store at this lane's elements, branch-free: a column block behind Wp re-reads block 0 (unused).
+      // BITS: one word per column block.  Else fp32, through a descriptor of the block's rows inside M: one vector offset per lane
+      // and a scalar one per element; a row >= M lies behind the extent and reads 0 (its g2 is then 0 and adds nothing to amax)
       float mk[NJ][16];
-      {
+      unsigned mkb[NJ];
+      if constexpr (BITS) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          const int cbm = cb_of(j) < ncbh ? cb_of(j) : 0;
+          mkb[j] = masks.bits[keep_mask_word(masks, L.store, mb, ncbh, cbm, c.wr, c.lane)] & live;
+        }
+      } else {
         const __amdgpu_buffer_rsrc_t mrs =
             __builtin_amdgcn_make_buffer_rsrc((void*)(g.H0 + L.store * g.ldH + m0 * g.Wp), 0, rows_in * g.Wp * 4, 0x00020000);
 #pragma unroll
@@ -683,7 +784,10 @@ __global__ void __launch_bounds__(512, 1) kw_trunk_bwd_h2(const TrunkBwdArgs g) 
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
               const float x = acc[j][r] * L.cscale + 0.0f;
-              v[r >> 2][r & 3] = (mk[j][r] > 0.0f) ? x : 0.0f;
+              bool on;
+              if constexpr (BITS) on = mkb[j] >> r & 1u;
+              else on = mk[j][r] > 0.0f;
+              v[r >> 2][r & 3] = on ? x : 0.0f;
             }
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
@@ -722,341 +826,17 @@ __global__ void __launch_bounds__(512, 1) kw_trunk_bwd_h2(const TrunkBwdArgs g) 
   }
   trunk_tail(c, amax, g.range_flag);
 }
-
-// ---- the KEPT forward and the backward that reads its masks (NSRW_FLAG_TRUNK_KEEP): kw_keep_h2<NJ, HEADS>, kw_keep_bwd_h2<NJ>, and the
-// two elementwise kernels between them and the per-layer chain, kw_mask_pack / kw_mask_unpack.  A forward pass that keeps its
-// activations for a backward runs as ONE launch too: kw_keep_h2 is kw_trunk_h2<NJ, HEADS, 4> row for row -- the same trunk_dma /
-// trunk_stage / trunk_sync cadence, the same epilogue arithmetic, the same values split in place and fed to amax -- and leaves what the
-// backward reads: of the pts_linears rows 0 .. D - 2 nothing but the SIGN of each activation, one bit; of the last pts_linears row the
-// fp32 output in H[D - 1] (b_head masks by it through a GEMM launch); in the heads form views_linears.0's fp32 output in HV (b_rgb
-// masks by it).  FA is not written: no backward reads it.  kw_keep_bwd_h2 is kw_trunk_bwd_h2 with the 16 NJ dword loads of a lane's fp32
-// masks per row replaced by NJ 16-bit loads.  (The bodies are restated, not shared with kw_trunk_h2 / kw_trunk_bwd_h2: those keep their
-// code.)
-//
-// THE bit layout of the masks (keep_mask_word; written by kw_keep_h2 and kw_mask_pack, read by kw_keep_bwd_h2 and kw_mask_unpack): per
-// kept layer l = 0 .. D - 2, block b of 128 points and column block cb = 0 .. Wp / 32 - 1 one 16-bit word per (wave row wr, lane) --
-//   word ((l nblk + b) Wp / 32 + cb) 256 + 64 wr + lane,   bit r = (x > 0) of row 128 b + trunk_acc_row(r, 32 wr, 4 (lane / 32)),
-//                                                                            column 32 cb + lane % 32
-// (x behind relu, so a NaN gives 0): Wp / 8 bytes per point and layer, over whole blocks (nblk = ceil(M / 128): a row >= M has a bit,
-// of its clamped input; the backward does not read it).  A word holds exactly the 16 accumulator registers of the lane that owns
-// (row, column) in either kernel, whichever column blocks cb_of deals to its wave.
-//
-// (The bodies of the two kernels are compiled for the device only: the host pass of hipcc rejects a SECOND kernel's call of a
-// trunk_dma specialization that another kernel already uses -- the buffer descriptor in its signature is a device type -- and needs
-// nothing of a kernel but its name.)
-struct KeepMasks {
-  unsigned short* bits;             // the words of every kept layer
-  long long ld;                     // words per layer: nblk * (Wp / 32) * 256
-  int nblk, n_layers;               // blocks of 128 points; kept layers (D - 1)
-};
-__device__ __forceinline__ long long keep_mask_word(const KeepMasks& m, int layer, int blk, int ncb, int cb, int wr, int lane) {
-  NSRW_CHECK(layer >= 0 && layer < m.n_layers && blk >= 0 && blk < m.nblk && cb >= 0 && cb < ncb && wr >= 0 && wr < 4 && lane >= 0 &&
-             lane < 64 && (long long)m.nblk * ncb * 256 == m.ld);
-  return layer * m.ld + ((long long)blk * ncb + cb) * 256 + 64 * wr + lane;
-}
-
-struct TrunkKeepArgs {              // beside kw_trunk_h2's TrunkArgs, where C = H[D - 1] and Dt = the pts_linears among the rows in either form
-  float* HV; int ldHV;              // heads form: views_linears.0's output [M, ldHV]
-  KeepMasks masks;
-};
-
-#ifdef __HIP_DEVICE_COMPILE__
-template <int NJ, bool HEADS, bool ENC>       // (ENC: as trunk_h2_body's; the kernels are kw_keep_h2 and its twin kw_enc_keep_h2)
-__device__ __forceinline__ void keep_h2_body(const TrunkArgs g, const TrunkKeepArgs a) {
-  constexpr int WR = 4, WC = 2, NCB = trunk_ncb<NJ, WR>(), kTrunkRows = trunk_rows<WR>();
-  constexpr int kWStage = trunk_wstage<NJ, WR>(), kSH = trunk_sh<NJ, WR>(), kHPiece = kTrunkRows * kSH, kEPiece = kTrunkRows * kTrunkSE;
-  constexpr int kHOff = 2 * kWStage, kEOff = kHOff + 2 * kHPiece, kLds = trunk_lds_bytes<NJ, WR>();
-  constexpr int kKbeMax = kTrunkCiMax / 16, kEncIt = (kKbeMax + WC - 1) / WC;
-  constexpr bool kNcbVaries = HEADS;
-  const TrunkCtx<kLds> c = trunk_ctx<WR, kLds>();
-  auto cb_of = [&](int j) { return HEADS ? 2 * j + c.wc : c.wc * NJ + j; };
-  const int mblocks = (int)((g.M + kTrunkRows - 1) / kTrunkRows);      // (the host refuses more than 2^31 - 1 blocks)
-  if ((int)blockIdx.x >= mblocks) return;
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)g.img, 0, (int)g.img_bytes, 0x00020000);
-  const int KBE = g.ldE >> 4, KBH = g.Wp >> 4, ncbr = g.Wp >> 5;
-  NSRW_CHECK(KBE >= 2 && KBE <= kKbeMax && KBH >= 2 && KBH <= 2 * NCB && g.D >= 2 && g.Dt >= 2 && a.masks.nblk == mblocks &&
-             a.masks.n_layers == g.Dt - 1);
-  if constexpr (HEADS) NSRW_CHECK(g.Dt < g.D && (!g.ED || ((g.ldED >> 4) >= 2 && (g.ldED >> 4) <= kKbeMax)));
-  else NSRW_CHECK(g.Dt == g.D);
-  if constexpr (ENC) NSRW_CHECK(!g.E && 3 + 6 * g.pts.L <= g.ldE && (!HEADS || !g.ED || 3 + 6 * g.pts.Lv <= g.ldED));
-
-  float amax = 0.0f;                // largest magnitude this lane has split (encodings and activations)
-  int buf = 0;
-  const int row_e = c.frag0(kEOff, kTrunkSE), row_h = c.frag0(kHOff, kSH);
-  {
-    const TrunkLayer l0 = g.layers[0];
-    trunk_dma<NCB, kNcbVaries>(c, rsrc, g.img_bytes, l0.img_off, l0.kbe + l0.kbh, 0, 0, trunk_form_ncb(l0.form));
-  }
-  for (int mb = blockIdx.x; mb < mblocks; mb += gridDim.x) {
-    const long long m0 = (long long)mb * kTrunkRows;
-    {
-      f32x4 e[kEncIt][2];
-      if constexpr (ENC) trunk_rows_encode<kEncIt, WC, false>(c, g.pts, KBE, m0, g.M, e);
-      else trunk_rows_fetch<kEncIt, WC>(c, g.E, g.ldE, KBE, m0, g.M, e);
-      trunk_rows_store<kEncIt, WC>(c, KBE, e, row_e, kEPiece, kTrunkSE, kLds, amax);
-    }
-    trunk_sync();                   // the encodings are written (and, in the first block, the first stage of weights has landed)
-    for (int li = 0; li < g.D; ++li) {
-      const TrunkLayer L = g.layers[li];
-      const int ln = li + 1 < g.D ? li + 1 : 0;                       // behind the last row: layer 0 of the next block
-      const unsigned img_next = g.layers[ln].img_off;
-      const int kb_next = g.layers[ln].kbe + g.layers[ln].kbh;
-      const int ncb_next = kNcbVaries ? trunk_form_ncb(g.layers[ln].form) : NCB;
-      const int KB = L.kbe + L.kbh, nst = KB >> 1;
-      const int L_ncb = trunk_form_ncb(L.form), L_ncbo = trunk_form_ncbo(L.form);
-      const bool L_h_first = trunk_form_h_first(L.form), L_relu = trunk_form_relu(L.form);
-      if constexpr (HEADS)
-        NSRW_CHECK(L.kbe >= 0 && L.kbe <= kKbeMax && (L.kbe & 1) == 0 && L.kbh >= 0 && L.kbh <= KBH && (L.kbh & 1) == 0 && KB >= 2 &&
-                   L_ncb >= 1 && L_ncb <= NCB && L_ncbo >= 1 && L_ncbo <= L_ncb);
-      else
-        NSRW_CHECK((L.kbe == 0 || L.kbe == KBE) && (L.kbh == 0 || L.kbh == KBH) && KB >= 2 && (KB & 1) == 0);
-      const int na = HEADS ? ((L_ncbo - c.wc + 1) >> 1 > NJ ? NJ : (L_ncbo - c.wc + 1) >> 1) : NJ;
-      f32x4 ed[kEncIt][2];
-      const bool ed_here = HEADS && li + 1 == g.Dt && g.ED;
-      if constexpr (HEADS) {
-        if (ed_here) {
-          if constexpr (ENC) trunk_rows_encode<kEncIt, WC, true>(c, g.pts, g.ldED >> 4, m0, g.M, ed);
-          else trunk_rows_fetch<kEncIt, WC>(c, g.ED, g.ldED, g.ldED >> 4, m0, g.M, ed);
-        }
-      }
-      f32x16 acc[NJ];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
-      for (int s = 0; s < nst; ++s) {
-        const bool last = s + 1 >= nst;
-        trunk_dma<NCB, kNcbVaries>(c, rsrc, g.img_bytes, last ? img_next : L.img_off, last ? kb_next : KB, last ? 0 : 2 * s + 2, buf ^ 1,
-                                   last ? ncb_next : L_ncb);
-        const int kb0 = 2 * s;
-        bool from_e;
-        int kbr;                                                         // kb0 within its image
-        if (HEADS && L_h_first) { from_e = kb0 >= L.kbh; kbr = from_e ? kb0 - L.kbh : kb0; }
-        else { from_e = kb0 < L.kbe; kbr = from_e ? kb0 : kb0 - L.kbe; }
-        const int aoff = (from_e ? row_e : row_h) + kbr * 32;
-        const int pstride = from_e ? kEPiece : kHPiece;
-        if constexpr (HEADS) NSRW_CHECK(kbr >= 0 && kbr + 1 < (from_e ? L.kbe : L.kbh));
-        else NSRW_CHECK(from_e ? (kb0 + 1 < KBE) : (kb0 - L.kbe >= 0 && kb0 - L.kbe + 1 < KBH));
-        NSRW_CHECK(aoff >= kHOff && aoff + pstride + 32 + 16 <= kLds);
-        if constexpr (HEADS) {
-          if (na >= NJ) trunk_stage<NJ>(c, cb_of, acc, buf * kWStage, aoff, pstride);
-          else if (NJ > 1 && na == 1) trunk_stage<1>(c, cb_of, acc, buf * kWStage, aoff, pstride);
-        } else {
-          trunk_stage<NJ>(c, cb_of, acc, buf * kWStage, aoff, pstride);
-        }
-        trunk_sync();
-        buf ^= 1;
-      }
-      // epilogue: acc * cscale + bias, relu, to the row's destination.  Column blocks behind Wp hold zero weights and are dropped.
-      const int dest = HEADS ? trunk_form_dest(L.form) : (li + 1 == g.D ? kTrunkToC : kTrunkToLds);
-      const int ncbo = HEADS ? L_ncbo : ncbr;
-      const bool inside = m0 + kTrunkRows <= g.M;
-      // what a kept pass leaves beside the raw outputs: the bits of the pts_linears rows 0 .. D - 2, the fp32 rows of the last one
-      // (H[D - 1]) and, in the heads form, of views_linears.0 (HV: the one row whose K is [hidden | encoding])
-      const bool to_bits = li + 1 < g.Dt;
-      float* keep_to = li + 1 == g.Dt ? g.C : (HEADS && L_h_first) ? a.HV : nullptr;
-      const int keep_ld = li + 1 == g.Dt ? g.Wp : a.ldHV;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int cb = cb_of(j);
-        if (cb < ncbo) {
-          const int n = cb * 32 + c.lrow;
-          NSRW_CHECK(n < (HEADS ? 32 * ncbo : g.Wp) && L.bias_off + (unsigned)n < g.bias_floats);
-          const float b = g.bias[L.bias_off + n];
-          f32x4 v[4];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            float x = acc[j][r] * L.cscale + b;
-            if (!HEADS || L_relu) x = (x < 0.0f) ? 0.0f : x;             // NaN stays NaN, as through torch's relu
-            v[r >> 2][r & 3] = x;
-          }
-          if (to_bits) {
-            unsigned bits = 0u;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) bits |= (v[r >> 2][r & 3] > 0.0f ? 1u : 0u) << r;
-            NSRW_CHECK(cb < ncbr && dest == kTrunkToLds);
-            a.masks.bits[keep_mask_word(a.masks, li, mb, ncbr, cb, c.wr, c.lane)] = (unsigned short)bits;
-          }
-          if (keep_to) {
-            const long long mt = m0 + 32 * c.wr + 4 * c.lh;
-            NSRW_CHECK(n < keep_ld && (inside ? mt + 27 < g.M : true));
-            float* cp = keep_to + mt * keep_ld + n;
-            if (inside) {
-#pragma unroll
-              for (int r = 0; r < 16; ++r) cp[trunk_acc_row(r) * keep_ld] = v[r >> 2][r & 3];
-            } else {
-#pragma unroll
-              for (int r = 0; r < 16; ++r)
-                if (mt + trunk_acc_row(r) < g.M) cp[trunk_acc_row(r) * keep_ld] = v[r >> 2][r & 3];
-            }
-          }
-          if (dest == kTrunkToLds) {
-#pragma unroll
-            for (int hf = 0; hf < 2; ++hf) {
-              u32x4 p[2];
-              split8_h2(v[2 * hf], v[2 * hf + 1], p, amax);
-              trunk_write_inplace<NJ, WR>(c, p, hf, n, kEOff);
-            }
-          } else if (HEADS && n < trunk_store_ncols(L.store)) {          // a head's few columns of the raw outputs
-            const int col0 = trunk_store_col0(L.store), ld = trunk_store_ld(L.store);
-            const long long mt = m0 + 32 * c.wr + 4 * c.lh;
-            NSRW_CHECK(dest == kTrunkToRaw && col0 + n < ld);
-            float* rp = g.RAW + mt * ld + col0 + n;
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-              if (inside || mt + trunk_acc_row(r) < g.M) rp[trunk_acc_row(r) * ld] = v[r >> 2][r & 3];
-          }
-        }
-      }
-      if constexpr (HEADS) {
-        // behind the last pts_linears layer the encoding image is dead: the block's direction encodings take its place
-        if (ed_here) trunk_rows_store<kEncIt, WC>(c, g.ldED >> 4, ed, row_e, kEPiece, kTrunkSE, kLds, amax);
-      }
-      if (dest == kTrunkToLds) trunk_lds_barrier();
-    }
-  }
-  trunk_tail(c, amax, g.range_flag);
-}
 #endif
-template <int NJ, bool HEADS>
-__global__ void __launch_bounds__(512, 1) kw_keep_h2(const TrunkArgs g, const TrunkKeepArgs a) {
-#ifdef __HIP_DEVICE_COMPILE__
-  keep_h2_body<NJ, HEADS, false>(g, a);
-#endif
-}
-template <int NJ, bool HEADS>
-__global__ void __launch_bounds__(512, 1) kw_enc_keep_h2(const TrunkArgs g, const TrunkKeepArgs a) {
-#ifdef __HIP_DEVICE_COMPILE__
-  keep_h2_body<NJ, HEADS, true>(g, a);
-#endif
-}
-
-
 template <int NJ>
-__global__ void __launch_bounds__(512, 1) kw_keep_bwd_h2(const TrunkBwdArgs g, const KeepMasks masks) {      // (g.H0 / g.ldH are not read)
+__global__ void __launch_bounds__(512, 1) kw_trunk_bwd_h2(const TrunkBwdArgs g) {
 #ifdef __HIP_DEVICE_COMPILE__
-  constexpr int NCB = trunk_ncb<NJ>(), kTrunkRows = trunk_rows<4>();
-  constexpr int kWStage = trunk_wstage<NJ>(), kSH = trunk_sh<NJ>(), kHPiece = kTrunkRows * kSH;
-  constexpr int kHOff = 2 * kWStage, kLds = trunk_bwd_lds_bytes<NJ>();
-  constexpr int kGIt = NCB;         // k16 blocks of g one wave column splits: kb = 2 i + wc < 2 NCB
-  const TrunkCtx<kLds> c = trunk_ctx<4, kLds>();
-  auto cb_of = [&](int j) { return 2 * j + c.wc; };
-  const int mblocks = (int)((g.M + kTrunkRows - 1) / kTrunkRows);      // (the host refuses more than 2^31 - 1 blocks)
-  if ((int)blockIdx.x >= mblocks) return;
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)g.img, 0, (int)g.img_bytes, 0x00020000);
-  const int KBH = g.Wp >> 4, ncbh = g.Wp >> 5, ncbe = g.Ci >> 5;
-  NSRW_CHECK(KBH >= 2 && KBH <= 2 * NCB && (KBH & 1) == 0 && ncbe >= 1 && ncbe <= NCB && g.R >= 2 && g.n_masks >= 1 &&
-             masks.nblk == mblocks && masks.n_layers == g.n_masks);
-
-  float amax = 0.0f;                // largest magnitude this lane has split (the incoming g and every masked g2)
-  int buf = 0;
-  const int row_h = c.frag0(kHOff, kSH);
-  const auto rows = (const __attribute__((address_space(4))) TrunkLayer*)(uintptr_t)g.rows;      // scalar loads, as kw_trunk_bwd_h2
-  trunk_dma<NCB, true>(c, rsrc, g.img_bytes, rows[0].img_off, KBH, 0, 0, trunk_form_ncb(rows[0].form));
-  for (int mb = blockIdx.x; mb < mblocks; mb += gridDim.x) {
-    const long long m0 = (long long)mb * kTrunkRows;
-    const int rows_in = g.M - m0 < kTrunkRows ? (int)(g.M - m0) : kTrunkRows;      // the block's rows inside M
-    const int voff_e = (32 * c.wr + 4 * c.lh) * g.Ci + c.lrow;          // this lane's first element of GEP, from column block 0 (floats)
-    // the registers of this lane whose row lies inside M: a row >= M has a bit of its clamped input, which must count for nothing
-    unsigned live = 0u;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) live |= (trunk_acc_row(r, 32 * c.wr, 4 * c.lh) < rows_in ? 1u : 0u) << r;
-    {
-      f32x4 e[kGIt][2];
-      trunk_rows_fetch<kGIt, 2>(c, g.G, g.Wp, KBH, m0, g.M, e);
-      trunk_rows_store<kGIt, 2>(c, KBH, e, row_h, kHPiece, kSH, kLds, amax);
-    }
-    trunk_sync();                   // g is written (and, in the first block, the first stage of weights has landed)
-    float gep[NJ][16];              // dL/d encoding of this lane's elements: the sum over the encoding rows so far
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) gep[j][r] = 0.0f;
-    for (int li = 0; li < g.R; ++li) {
-      TrunkLayer L{};
-      L.img_off = rows[li].img_off; L.kbe = rows[li].kbe; L.kbh = rows[li].kbh; L.cscale = rows[li].cscale;
-      L.form = rows[li].form; L.store = rows[li].store;
-      const int ln = li + 1 < g.R ? li + 1 : 0;                       // behind the last row: row 0 of the next block
-      const unsigned img_next = rows[ln].img_off;
-      const int ncb_next = trunk_form_ncb(rows[ln].form);
-      const int nst = KBH >> 1;
-      const int L_ncb = trunk_form_ncb(L.form), L_ncbo = trunk_form_ncbo(L.form), dest = trunk_form_dest(L.form);
-      const bool accum = trunk_form_accum(L.form);
-      NSRW_CHECK(L.kbe == 0 && L.kbh == KBH && L_ncb >= 1 && L_ncb <= NCB && L_ncbo == L_ncb && L.store >= 0 && L.store < g.n_masks &&
-                 (dest == kTrunkToLds ? L_ncbo == ncbh : (dest == kTrunkToGep && L_ncbo == ncbe)));
-      const int na = (L_ncbo - c.wc + 1) >> 1 > NJ ? NJ : (L_ncbo - c.wc + 1) >> 1;
-      // the relu mask of layer L.store at this lane's elements: one word per column block (branch-free: an encoding row fetches the
-      // mask of the hidden row behind it, a column block behind Wp re-reads block 0; neither is used)
-      unsigned mk[NJ];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int cbm = cb_of(j) < ncbh ? cb_of(j) : 0;
-        mk[j] = masks.bits[keep_mask_word(masks, L.store, mb, ncbh, cbm, c.wr, c.lane)] & live;
-      }
-      f32x16 acc[NJ];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
-      for (int s = 0; s < nst; ++s) {
-        const bool last = s + 1 >= nst;
-        trunk_dma<NCB, true>(c, rsrc, g.img_bytes, last ? img_next : L.img_off, KBH, last ? 0 : 2 * s + 2, buf ^ 1, last ? ncb_next : L_ncb);
-        const int aoff = row_h + 2 * s * 32;
-        NSRW_CHECK(2 * s + 1 < KBH && aoff >= kHOff && aoff + kHPiece + 32 + 16 <= kLds);
-        if (na >= NJ) trunk_stage<NJ>(c, cb_of, acc, buf * kWStage, aoff, kHPiece);
-        else if (NJ > 1 && na == 1) trunk_stage<1>(c, cb_of, acc, buf * kWStage, aoff, kHPiece);
-        trunk_sync();
-        buf ^= 1;
-      }
-      // epilogue: the masked product to the activation image, or the product into the GEP sum
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int cb = cb_of(j);
-        if (cb < L_ncbo) {
-          if (dest == kTrunkToLds) {
-            const int n = cb * 32 + c.lrow;
-            f32x4 v[4];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const float x = acc[j][r] * L.cscale + 0.0f;
-              v[r >> 2][r & 3] = (mk[j] >> r & 1u) ? x : 0.0f;
-            }
-#pragma unroll
-            for (int hf = 0; hf < 2; ++hf) {
-              u32x4 p[2];
-              split8_h2(v[2 * hf], v[2 * hf + 1], p, amax);
-              trunk_write_inplace<NJ, 4>(c, p, hf, n, kLds);
-            }
-          } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const float x = acc[j][r] * L.cscale + 0.0f;
-              gep[j][r] = accum ? gep[j][r] + x : x;
-            }
-          }
-        }
-      }
-      if (dest == kTrunkToLds) trunk_lds_barrier();
-    }
-    // behind layer 0's row the sum is complete: GEP through a descriptor of the block's rows inside M (a row >= M lies behind the
-    // extent: its store is dropped)
-    {
-      const __amdgpu_buffer_rsrc_t ers = __builtin_amdgcn_make_buffer_rsrc((void*)(g.GEP + m0 * g.Ci), 0, rows_in * g.Ci * 4, 0x00020000);
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int cb = cb_of(j);
-        if (cb < ncbe) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int ro = trunk_acc_row(r);
-            NSRW_CHECK(rows_in >= 1 && m0 + rows_in <= g.M && 32 * c.wr + 4 * c.lh + ro < kTrunkRows && cb * 32 + c.lrow < g.Ci);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, gep[j][r]), ers, voff_e * 4, (ro * g.Ci + cb * 32) * 4, 0);
-          }
-        }
-      }
-    }
-  }
-  trunk_tail(c, amax, g.range_flag);
+  trunk_bwd_body<NJ, false>(g, KeepMasks{});
+#endif
+}
+template <int NJ>
+__global__ void __launch_bounds__(512, 1) kw_keep_bwd_h2(const TrunkBwdArgs g, const KeepMasks masks) {
+#ifdef __HIP_DEVICE_COMPILE__
+  trunk_bwd_body<NJ, true>(g, masks);
 #endif
 }
 
@@ -1201,17 +981,7 @@ __global__ void __launch_bounds__(512, 1) kw_rerun_b3(const TrunkArgs g, const u
               trunk_write_inplace<NJ, WR>(c, p, hf, n, kEOff);
             }
           } else {
-            const long long mt = m0 + 32 * c.wr + 4 * c.lh;
-            float* cp = g.C + mt * g.Wp + n;
-            if (inside) {
-              NSRW_CHECK(mt + 27 < g.M && n < g.Wp);
-#pragma unroll
-              for (int r = 0; r < 16; ++r) cp[trunk_acc_row(r) * g.Wp] = v[r >> 2][r & 3];
-            } else {
-#pragma unroll
-              for (int r = 0; r < 16; ++r)
-                if (mt + trunk_acc_row(r) < g.M) cp[trunk_acc_row(r) * g.Wp] = v[r >> 2][r & 3];
-            }
+            NSRW_ROWS_OUT(c, v, g.C, g.Wp, n, m0, g.M, inside);
           }
         }
       }
