@@ -16,7 +16,10 @@
  * Conventions are those of include/nsr.h: int status (0 = OK, message via nsrw_last_error), caller-owned DEVICE buffers passed
  * as raw pointers, stream-ordered, no hidden synchronisation in the launch calls, one handle per (model, stream); a handle is
  * not thread-safe, distinct handles are.  The scratch memory is the CALLER's too: nsrw_workspace_bytes says how much one
- * chunk of rays needs, the launch calls split the rays into as many chunks as the workspace they are handed allows.
+ * chunk of rays needs, the launch calls split the rays into as many chunks as the workspace they are handed allows.  Chunking never
+ * changes a result on fp32 and bf16x3 handles, nor on an f16x2 handle while no pass leaves fp16's range; an f16x2 pass that does is
+ * re-run on bf16x3 over its whole chunk, so there the results are arithmetic-equivalent (fp32-grade either way) but not bit-stable
+ * across chunkings -- unless the handle has NSRW_FLAG_RERUN_ROWS, whose re-run is per point and whose results are bit-stable.
  */
 #ifndef NSR_WIDE_H_
 #define NSR_WIDE_H_
@@ -42,7 +45,11 @@ enum { NSRW_FLAG_WHITE_BKGD = 1,     /* RN:384-385 */
                                       * (the arithmetic of the fused default kernel, csrc/nsr_h2.inc: |error| <= 2^-22 per product;
                                       * weights pre-scaled per matrix, gradients normalised per point).  A network pass -- forward or
                                       * backward -- in which a value reaches fp16's largest number is run again on bf16x3 inside the
-                                      * same call (nsrw_range_status counts them), so no result depends on the range. */
+                                      * same call (nsrw_range_status counts them), so no result depends on the range: a re-run pass has
+                                      * bf16x3's bits, which are fp32-grade like f16x2's but not the same.  The unit of that re-run is
+                                      * the pass over a chunk, so once a pass re-runs a ray's BITS depend on its chunk's other rays and
+                                      * on the chunk size (arithmetic-equivalent, not bit-stable); NSRW_FLAG_RERUN_ROWS makes the unit
+                                      * the point, and the bits a ray's own. */
 enum { NSRW_FLAG_TRUNK_ONCHIP = 16 };/* opt-in, f16x2 handles only (nsrw_create refuses it without NSRW_FLAG_MLP_F16X2): a network of padded width
                                       * <= 128 and depth >= 2 runs ALL its pts_linears in one launch with the activations in LDS
                                       * (csrc/nsr_wide_trunk.inc) wherever no activation is kept for a backward -- the same arithmetic per
@@ -112,6 +119,18 @@ enum { NSRW_FLAG_EMBED_ONCHIP = (1 << 11) }; /* opt-in, with NSRW_FLAG_TRUNK_ONC
                                       * encoding launch conditional on the range word stands in front of it.  A pass that runs layer
                                       * by layer is encoded as without the flag.  The workspace and the chunking are unchanged
                                       * (nsrw_embed_plan says which encodings of which pass; nsrw_embed_status counts). */
+
+enum { NSRW_FLAG_RERUN_ROWS = (1 << 12) }; /* opt-in, f16x2 handles without NSRW_FLAG_TRUNK_ONCHIP only (nsrw_create refuses it otherwise) */
+                                     /* The range safety net per POINT instead of per pass: the f16x2 GEMMs of a pass set one bit per row
+                                      * (point) in which a value they split reaches fp16's largest number; a small kernel lists the
+                                      * 256-row and 128-row tile blocks that hold such a row; the bf16x3 chain then walks the listed
+                                      * blocks alone and stores only the flagged rows -- with the sums of a whole-pass bf16x3 re-run, so a
+                                      * flagged point has a bf16x3 handle's bits and every other point keeps its f16x2 bits.  Which of
+                                      * the two a point gets depends on that point's own values, so a ray's bits depend on the ray alone:
+                                      * not on its neighbours, not on the chunk size.  Stream-ordered and capturable like the per-pass
+                                      * form.  nsrw_range_status keeps its meaning (a pass counts as re-run when any row was flagged),
+                                      * nsrw_range_rows_status counts rows.  The workspace grows by the bits and the two lists, about
+                                      * 0.2 bytes per point. */
 
 typedef struct NsrwConfig {
   int32_t device;
@@ -191,7 +210,7 @@ int nsrw_upload_tables(nsrw_handle h, const float* t_coarse, int n_coarse, const
 /* Bytes of workspace ONE chunk of `rays` rays needs (with_grad = 1: for nsrw_render_rays_vjp, which keeps every activation of the
  * last network; with_grad = 2: for nsrw_render_rays_vjp_cot with a coarse cotangent and N_importance > 0, whose gradient
  * buffers hold either network).  The launch calls accept any workspace that holds a chunk of at least 64 rays; the chunk
- * size decides nothing but how many rays one f16x2 re-run covers. */
+ * size decides nothing but how many rays one f16x2 re-run covers (per-pass re-run; with NSRW_FLAG_RERUN_ROWS nothing at all). */
 int nsrw_workspace_bytes(nsrw_handle h, int64_t rays, int with_grad, size_t* bytes);
 
 /* render_rays (RN:390-501) over n_rays rays.  near / far: scalars, overridden per ray by ex->d_near / d_far. */
@@ -248,6 +267,24 @@ int nsrw_embed_vjp(int device, const float* d_x, const float* d_grad_out, int64_
 /* NSRW_FLAG_MLP_F16X2 handles: network passes (forward and backward) launched so far and how many of them were re-run on bf16x3
  * because an activation or a gradient left fp16's range (both 0 for the other arithmetics).  Synchronises the device. */
 int nsrw_range_status(nsrw_handle h, unsigned long long* passes, unsigned long long* passes_rerun);
+
+/* NSRW_FLAG_RERUN_ROWS handles: rows (points) of the network passes launched so far and how many of them were flagged and re-computed
+ * on bf16x3 (both 0 on every other handle).  Synchronises the device. */
+int nsrw_range_rows_status(nsrw_handle h, unsigned long long* rows, unsigned long long* rows_rerun);
+
+/* DIAGNOSTIC; needs no device and no handle.  The host restatement of the list kernel of NSRW_FLAG_RERUN_ROWS: from the row bits
+ * `words` (n_words 32-bit words; bit r % 32 of word r / 32 = row r; rows >= M and words behind n_words count as clear) the ascending
+ * tile blocks of tile_rows (128 or 256) rows of an M-row pass that hold a flagged row.  Writes the first `max` of them to list_out
+ * and returns how many there are; -1 for an argument out of range.  (The device list holds the same blocks in no fixed order.) */
+int nsrw_rerun_rows_plan(const uint32_t* words, int64_t n_words, int64_t M, int tile_rows, int32_t* list_out, int64_t max);
+
+/* DIAGNOSTIC stage entry; needs no handle (a stream-ordered launch on `device`).  The list kernel of NSRW_FLAG_RERUN_ROWS on the
+ * caller's row bits: d_words [(M + 31) / 32] as above -> d_list [1 + max] int32, which the caller has zeroed at [0]: [0] receives the
+ * number of tile blocks of tile_rows rows that hold a flagged row below M, [1 ..] the blocks, in no fixed order; max >= the number of
+ * blocks of the pass.  d_range (nullable): 8 zeroed uint32 of which [0] receives (count > 0) and, as two 64-bit counters at [4..7],
+ * M and the number of flagged rows are added.  The tests hold it to nsrw_rerun_rows_plan. */
+int nsrw_rerun_rows_list(int device, const uint32_t* d_words, int64_t M, int tile_rows, int32_t* d_list, int64_t max, uint32_t* d_range,
+                         void* stream);
 
 /* Device time of the last launch call (ms; synchronises on its closing event) and the number of chunks it ran. */
 int nsrw_last_ms(nsrw_handle h, float* ms, int* chunks);

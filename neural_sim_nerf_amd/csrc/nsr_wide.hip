@@ -812,7 +812,17 @@ struct GemmCfg {
   unsigned long long* keep_passes = nullptr;      // host: kept forward passes launched on chip so far (Handle::keep_passes)
   unsigned long long* rerun_launches = nullptr;   // host: kw_rerun_b3 launches enqueued so far (Handle::rerun_launches)
   unsigned long long* embed_counts = nullptr;     // host: Handle::embed_counts (nsrw_embed_status)
-  unsigned* d_range = nullptr;          // device: [0] flag of the f16x2 pass in flight, [1] passes run, [2] passes re-run on bf16x3
+  unsigned* d_range = nullptr;          // device: [0] flag of the f16x2 pass in flight, [1] passes run, [2] passes re-run on bf16x3;
+                                        // [4..7] two 64-bit counters of NSRW_FLAG_RERUN_ROWS: rows seen, rows flagged (kw_rows_list)
+  bool rows = false;                    // NSRW_FLAG_RERUN_ROWS: the f16x2 passes of net_forward / net_backward re-run per row
+};
+
+// The row-granular re-run's buffers of one pass (Chunk::RW / RL, in the workspace): the row bits and, per tile height -- [0]: 128 rows,
+// [1]: 256 -- the list of M-blocks with a flagged row ([0] the count) and the entries it has room for.  words == nullptr: not that mode.
+struct RowsRun {
+  unsigned* words = nullptr;
+  int* list[2] = {nullptr, nullptr};
+  int list_max[2] = {0, 0};
 };
 
 // One chain of GEMM launches (a network pass): the arithmetic it runs on and, nullable, the device word its launches are conditional
@@ -821,6 +831,7 @@ struct GemmCfg {
 struct Run {
   Arith arith;
   const unsigned* run_if;
+  RowsRun rows{};                       // NSRW_FLAG_RERUN_ROWS: the kH2 chain sets row bits, the kB3 chain walks the lists (gemm)
 };
 
 struct Handle {
@@ -940,7 +951,25 @@ struct Chunk {
   std::vector<float*> H;
   float *DRAW, *GV, *G0, *G1, *GEP, *GED, *gscale;
   unsigned short* MB = nullptr;     // NSRW_FLAG_TRUNK_KEEP, grad >= 1: the relu masks of a kept pass as bits (keep_masks)
+  RowsRun rows{};                   // NSRW_FLAG_RERUN_ROWS: the row bits and the two lists of the pass in flight (carve_rows)
 };
+
+// the row bits of up to P points and the lists of their 128-row and 256-row blocks, ONE contiguous region from rows.words on (cleared
+// as one: rows_bytes) -- behind everything else, and only on a handle with the flag: without it the carve is what it was
+size_t rows_bytes(long long P) { return (size_t)((P + 31) / 32 + 2 + (P + 127) / 128 + (P + 255) / 256) * sizeof(unsigned); }
+void carve_rows(int flags, long long P, Carve& c, Chunk& k) {
+  k.rows = RowsRun{};
+  if (!(flags & NSRW_FLAG_RERUN_ROWS) || P <= 0) return;
+  unsigned* base = reinterpret_cast<unsigned*>(c.f(rows_bytes(P) / sizeof(unsigned)));
+  const long long nw = (P + 31) / 32;
+  k.rows.list_max[0] = (int)std::min<long long>((P + 127) / 128, 0x7fffffff);
+  k.rows.list_max[1] = (int)std::min<long long>((P + 255) / 256, 0x7fffffff);
+  k.rows.words = base;
+  if (base) {
+    k.rows.list[0] = reinterpret_cast<int*>(base + nw);
+    k.rows.list[1] = k.rows.list[0] + 1 + k.rows.list_max[0];
+  }
+}
 
 // grad: 0 = forward only, 1 = + the last pass's backward (nsrw_render_rays_vjp), 2 = + the coarse pass's backward as well
 // (nsrw_render_rays_vjp_cot with coarse cotangents and N_importance > 0: the gradient buffers hold either network)
@@ -981,6 +1010,7 @@ void carve_chunk(const Handle& h, long long R, int grad, Carve& c, Chunk& k) {
       if (n->onchip.keep.form) words = std::max(words, (size_t)(n->d.D - 1) * (size_t)((P + 127) / 128) * (n->Wp / 32) * 256);
     if (words) k.MB = reinterpret_cast<unsigned short*>(c.f((words + 1) / 2));
   }
+  carve_rows(h.cfg.flags, P, c, k);
 }
 
 // The launch plan of one GEMM -- pure host arithmetic, no HIP call (nsrw_gemm_plan exposes it).  The N extent of a matrix whose image
@@ -1041,7 +1071,36 @@ const GemmForm* gemm_forms() {
                                              gemm_form<NP, 4, 2>(), gemm_form<NP, 2, 2>(), gemm_form<NP, 1, 2>()};
   return forms;
 }
-const GemmForm* find_form(Arith a, int nj, int wm) {
+// ... and their row-granular twins (kw_gemm_h2_rows / kw_gemm_b3_rows), a table of its own behind the 72: the same forms, f16x2 and
+// bf16x3 only
+template <int NP, int NJ, int EPI, int WM>
+GemmKernel gemm_rows_kernel() {
+  if constexpr (NP == kB3) return kw_gemm_b3_rows<NJ, EPI, WM>;
+  else return kw_gemm_h2_rows<NJ, EPI, WM>;
+}
+template <int NP, int NJ, int WM>
+GemmForm gemm_rows_form() {
+  GemmForm f{NJ, WM, wgs_per_cu<NJ, WM>(), {}};
+  f.epi[kRelu] = gemm_rows_kernel<NP, NJ, kRelu, WM>();
+  f.epi[kMaskEpi] = gemm_rows_kernel<NP, NJ, kMaskEpi, WM>();
+  f.epi[kAccum] = gemm_rows_kernel<NP, NJ, kAccum, WM>();
+  f.epi[0] = gemm_rows_kernel<NP, NJ, 0, WM>();
+  return f;
+}
+template <int NP>
+const GemmForm* gemm_rows_forms() {
+  static const GemmForm forms[kGemmForms] = {gemm_rows_form<NP, 4, 4>(), gemm_rows_form<NP, 3, 4>(), gemm_rows_form<NP, 2, 4>(),
+                                             gemm_rows_form<NP, 4, 2>(), gemm_rows_form<NP, 2, 2>(), gemm_rows_form<NP, 1, 2>()};
+  return forms;
+}
+const GemmForm* find_form(Arith a, int nj, int wm, bool rows = false) {
+  if (rows) {
+    if (a == kF32) return nullptr;
+    const GemmForm* forms = a == kH2 ? gemm_rows_forms<kH2>() : gemm_rows_forms<kB3>();
+    for (int i = 0; i < kGemmForms; ++i)
+      if (forms[i].nj == nj && forms[i].wm == wm) return &forms[i];
+    return nullptr;
+  }
   const GemmForm* forms = a == kF32 ? gemm_forms<kF32>() : a == kH2 ? gemm_forms<kH2>() : gemm_forms<kB3>();
   for (int i = 0; i < kGemmForms; ++i)
     if (forms[i].nj == nj && forms[i].wm == wm) return &forms[i];
@@ -1058,12 +1117,14 @@ int gemm(const GemmCfg& cfg, Run run, hipStream_t st, const Net& net, const Mat&
   g.A1 = A1; g.A2 = m.K2p ? A2 : nullptr; g.lda1 = lda1; g.lda2 = lda2; g.K1 = m.K1p; g.K2 = m.K2p;
   g.M = M; g.ldc = ldc; g.ldm = ldm;
   g.cscale = run.arith == kH2 ? m.cscale : 1.0f; g.range_flag = cfg.d_range; g.run_if = run.run_if;
+  const bool rows = run.rows.words != nullptr;
+  if (rows) { g.row_words = run.rows.words; g.n_words = (int)((M + 31) / 32); }
   const int kfrag = frag_bytes(run.arith), KB = (m.K1p + m.K2p) / 16;
   NsrwGemmPart parts[kMaxGemmParts];
   const int n_parts = gemm_plan(m.ncb, N, cfg.tile_wm, parts);
   for (int i = 0; i < n_parts; ++i) {
     const NsrwGemmPart& p = parts[i];
-    const GemmForm* form = find_form(run.arith, p.nj, p.wm);
+    const GemmForm* form = find_form(run.arith, p.nj, p.wm, rows);
     if (!form) return fail("nsrw: internal error: the launch plan names a tile form that is not compiled");
     const int tm = 64 * p.wm, cb = p.col_block;
     const long long mblocks = (M + tm - 1) / tm, mgroups = (mblocks + 7) / 8;
@@ -1075,6 +1136,7 @@ int gemm(const GemmCfg& cfg, Run run, hipStream_t st, const Net& net, const Mat&
     t.C = C + cb * 32; t.N = N - cb * 32;
     t.mask = mask ? mask + cb * 32 : nullptr;
     t.n_tiles = p.tiles;
+    if (rows) { t.row_list = run.rows.list[p.wm == 4 ? 1 : 0]; t.list_max = run.rows.list_max[p.wm == 4 ? 1 : 0]; }
     const long long all = mgroups * 8 * p.tiles;
     const unsigned grid = (unsigned)std::max<long long>(8, std::min<long long>(all, (long long)cfg.cus * form->wgs_per_cu / 8 * 8));
     hipLaunchKernelGGL(form->epi[epi], dim3(grid), dim3(128 * p.wm), 0, st, t);
@@ -1232,7 +1294,11 @@ constexpr FlagNeeds kFlagNeeds[] = {
      "nsrw_create: NSRW_FLAG_TRUNK_RERUN needs NSRW_FLAG_TRUNK_ONCHIP (the on-chip bf16x3 re-run serves the passes whose f16x2 trunk ran on chip)"},
     {NSRW_FLAG_EMBED_ONCHIP, NSRW_FLAG_TRUNK_ONCHIP,
      "nsrw_create: NSRW_FLAG_EMBED_ONCHIP needs NSRW_FLAG_TRUNK_ONCHIP (the encodings are computed in the on-chip trunk's launch)"},
+    {NSRW_FLAG_RERUN_ROWS, NSRW_FLAG_MLP_F16X2,
+     "nsrw_create: NSRW_FLAG_RERUN_ROWS needs NSRW_FLAG_MLP_F16X2 (only the f16x2 arithmetic has a range to leave and a re-run)"},
 };
+constexpr const char* kRowsNoOnchip =
+    "nsrw_create: NSRW_FLAG_RERUN_ROWS does not combine with NSRW_FLAG_TRUNK_ONCHIP (the on-chip forms feed one range word per pass)";
 
 // the decisions as the diagnostic entries report them (no form: every figure 0, and the reason)
 NsrwTrunkPlan as_trunk_plan(const Onchip& c) {
@@ -1472,6 +1538,90 @@ __global__ void kw_range_tally(unsigned* r) {
   }
 }
 
+// ---- the row-granular re-run (NSRW_FLAG_RERUN_ROWS) between the f16x2 chain and the bf16x3 chain of a pass over M rows.
+// kw_rows_list, one thread per M-block of tile_rows rows: a block with a flagged row (bits of rows >= M do not count) appends itself
+// to list[1 ..] at the position the wave's one atomicAdd on list[0] hands out -- the blocks of a list stand in no fixed order, which
+// no result depends on (a tile's sums do not know its neighbours).  The launch with `tally` set -- one per pass -- also sets
+// range[0] = (count > 0), so that every run_if consumer and kw_rows_tally see what the per-pass form would show them, and adds to the two
+// 64-bit counters behind range[4]: rows seen, rows flagged.  nsrw_rerun_rows_plan is its host restatement.
+struct RowsListArgs {
+  const unsigned* words; long long M; int n_words, tile_rows;
+  int* list; int list_max;
+  unsigned* range; int tally;
+};
+__global__ void __launch_bounds__(256) kw_rows_list(const RowsListArgs a) {
+  const long long mb = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long mblocks = (a.M + a.tile_rows - 1) / a.tile_rows;
+  const int wpb = a.tile_rows >> 5, lane = threadIdx.x & 63;
+  unsigned n = 0u;
+  if (mb < mblocks)
+    for (int q = 0; q < wpb; ++q) {
+      const long long wi = mb * wpb + q;
+      if (wi >= a.n_words) break;
+      NSRW_CHECK(wi >= 0 && wi < a.n_words && wi * 32 < a.M);
+      unsigned w = a.words[wi];
+      const long long left = a.M - wi * 32;
+      if (left < 32) w &= (1u << (int)left) - 1u;
+      n += (unsigned)__builtin_popcount(w);
+    }
+  const unsigned long long any = __builtin_amdgcn_ballot_w64(n != 0u);
+  if (any == 0ull) {
+    if (a.tally && mb == 0) atomicAdd(reinterpret_cast<unsigned long long*>(a.range + 4), (unsigned long long)a.M);
+    return;
+  }
+  const int leader = __builtin_ctzll(any);
+  int base = 0;
+  if (lane == leader) base = atomicAdd(a.list, __builtin_popcountll(any));
+  base = __shfl(base, leader, 64);
+  if (n != 0u) {
+    const int pos = base + __builtin_popcountll(any & ((1ull << lane) - 1ull));
+    NSRW_CHECK(pos >= 0 && pos < a.list_max && mb * a.tile_rows < a.M);
+    if (pos < a.list_max) a.list[1 + pos] = (int)mb;
+  }
+  if (a.tally) {
+    unsigned sum = n;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    if (lane == leader) {
+      atomicAdd(reinterpret_cast<unsigned long long*>(a.range + 4) + 1, (unsigned long long)sum);
+      atomicOr(a.range, 1u);
+    }
+    if (mb == 0) atomicAdd(reinterpret_cast<unsigned long long*>(a.range + 4), (unsigned long long)a.M);
+  }
+}
+
+// kw_range_tally's sibling behind such a pass: the same bookkeeping, and the row words and both list counts cleared for the next pass
+__global__ void __launch_bounds__(256) kw_rows_tally(unsigned* r, unsigned* words, int n_words, int* count128, int* count256) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n_words) words[i] = 0u;
+  if (i == 0) {
+    r[1] += 1u;
+    if (r[0]) { r[2] += 1u; r[0] = 0u; }
+    *count128 = 0;
+    *count256 = 0;
+  }
+}
+
+RowsListArgs rows_list_args(const GemmCfg& cfg, const RowsRun& rr, long long M, int which) {
+  RowsListArgs a{};
+  a.words = rr.words; a.M = M; a.n_words = (int)((M + 31) / 32); a.tile_rows = which ? 256 : 128;
+  a.list = rr.list[which]; a.list_max = rr.list_max[which];
+  a.range = cfg.d_range; a.tally = which == 0;
+  return a;
+}
+// the two lists of a pass over M rows (the 128-row one serves the 64-column forms on every handle, and every form under NSRW_B3_WM = 2)
+void rows_list_launch(const GemmCfg& cfg, hipStream_t st, const RowsRun& rr, long long M) {
+  for (int which = 0; which < 2; ++which) {
+    const RowsListArgs a = rows_list_args(cfg, rr, M, which);
+    const long long mblocks = (M + a.tile_rows - 1) / a.tile_rows;
+    hipLaunchKernelGGL(kw_rows_list, dim3((unsigned)((mblocks + 255) / 256)), dim3(256), 0, st, a);
+  }
+}
+void rows_tally_launch(const GemmCfg& cfg, hipStream_t st, const RowsRun& rr, long long M) {
+  const int n_words = (int)((M + 31) / 32);
+  hipLaunchKernelGGL(kw_rows_tally, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, st, cfg.d_range, rr.words, n_words, rr.list[0], rr.list[1]);
+}
+
 // kw_embed over the points of `src` (EmbedArgs::E / ED are set here): E nullable -- the direction rows alone; run_if nullable
 void embed_launch(const GemmCfg& cfg, hipStream_t st, EmbedArgs a, float* E, float* ED, const unsigned* run_if) {
   a.E = E; a.ED = ED; a.run_if = run_if;
@@ -1496,6 +1646,15 @@ int net_forward(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k
   if (cfg.arith != kH2) return net_forward_chain(cfg, Run{cfg.arith, nullptr}, st, n, k, P, keep, sigma, ld_sigma);
   // f16x2: the pass on fp16 MFMAs; then the same pass on bf16x3 in launches that are empty unless an activation left fp16's
   // range (its inputs -- the encodings -- are untouched, every buffer it writes is written again); then the tally
+  if (cfg.rows) {
+    // row-granular: the f16x2 chain sets a bit per row that leaves the range, the lists name the blocks that hold one, and the bf16x3
+    // chain stores those rows alone (every launch of it reads its count on the device: nothing listed, nothing done)
+    if (net_forward_chain(cfg, Run{kH2, nullptr, k.rows}, st, n, k, P, keep, sigma, ld_sigma)) return 1;
+    rows_list_launch(cfg, st, k.rows, P);
+    if (net_forward_chain(cfg, Run{kB3, cfg.d_range, k.rows}, st, n, k, P, keep, sigma, ld_sigma)) return 1;
+    rows_tally_launch(cfg, st, k.rows, P);
+    return 0;
+  }
   if (net_forward_chain(cfg, Run{kH2, nullptr}, st, n, k, P, keep, sigma, ld_sigma, enc ? &src : nullptr)) return 1;
   if (enc) {
     embed_launch(cfg, st, src, k.E, eo.dirs ? ED : nullptr, cfg.d_range);
@@ -1564,6 +1723,13 @@ int net_backward_chain(const GemmCfg& cfg, Run run, hipStream_t st, const Net& n
 // only; the first write of k.GEP does not accumulate), then the tally
 int net_backward(const GemmCfg& cfg, hipStream_t st, const Net& n, const Chunk& k, long long P) {
   if (cfg.arith != kH2 || P <= 0) return net_backward_chain(cfg, Run{cfg.arith, nullptr}, st, n, k, P);
+  if (cfg.rows) {                     // row-granular, as in net_forward: the bits are this backward's own (the tally cleared the forward's)
+    if (net_backward_chain(cfg, Run{kH2, nullptr, k.rows}, st, n, k, P)) return 1;
+    rows_list_launch(cfg, st, k.rows, P);
+    if (net_backward_chain(cfg, Run{kB3, cfg.d_range, k.rows}, st, n, k, P)) return 1;
+    rows_tally_launch(cfg, st, k.rows, P);
+    return 0;
+  }
   if (net_backward_chain(cfg, Run{kH2, nullptr}, st, n, k, P)) return 1;
   // a forward kept on chip left bits: the re-run masks by fp32 H > 0, so H[0 .. D - 2] = 1 / 0 from the bits first
   if (keep_pass(n, P) && mask_launch(cfg, st, n, k, P, false)) return 1;
@@ -1668,6 +1834,8 @@ int render_impl(Handle* h, const float* ro, const float* rd, long long n, float 
     Chunk k;
     carve_chunk(*h, R, mode, c, k);
     if (c.off > ws_bytes) return fail("nsrw: internal error: the chunk's carve exceeds the workspace");      // (chunk_rays sized it)
+    // (the workspace is the caller's memory: whatever it holds, the first pass starts from clear bits and empty lists; kw_rows_tally keeps them so)
+    if (k.rows.words) NSRW_HIP(hipMemsetAsync(k.rows.words, 0, rows_bytes(R * std::max(S0, S1)), st));
     const unsigned rb = (Rc + 255) / 256;
     RayArgs ra{};
     ra.rays_o = ro + r0 * 3; ra.rays_d = rd + r0 * 3;
@@ -1804,12 +1972,14 @@ int nsrw_create(const NsrwConfig* cfg, nsrw_handle* out) {
   if (cfg->device < 0 || cfg->device >= count) return fail("nsrw_create: no such device");
   for (const FlagNeeds& r : kFlagNeeds)
     if ((cfg->flags & r.flag) && !(cfg->flags & r.needs)) return fail(r.refusal);
+  if ((cfg->flags & NSRW_FLAG_RERUN_ROWS) && (cfg->flags & NSRW_FLAG_TRUNK_ONCHIP)) return fail(kRowsNoOnchip);
   GemmCfg gc;
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess && prop.multiProcessorCount > 0) gc.cus = prop.multiProcessorCount;
   }
   gc.flags = cfg->flags;
+  gc.rows = (cfg->flags & NSRW_FLAG_RERUN_ROWS) != 0;
   gc.arith = (cfg->flags & NSRW_FLAG_MLP_F16X2) ? kH2 : (cfg->flags & NSRW_FLAG_MLP_BF16X3) ? kB3 : kF32;
   if (const char* wm = getenv("NSRW_B3_WM")) gc.tile_wm = atoi(wm) == 2 ? 2 : 4;
   Handle* h = new Handle();
@@ -1818,7 +1988,7 @@ int nsrw_create(const NsrwConfig* cfg, nsrw_handle* out) {
   DeviceGuard guard(cfg->device);
   if (guard.err != hipSuccess) { delete h; return fail("nsrw_create: hipSetDevice failed"); }
   if (hipMalloc(&h->d_tab, (size_t)(cfg->n_samples + std::max(cfg->n_importance, 1)) * 4) != hipSuccess ||
-      hipMalloc(&h->d_range, 4 * sizeof(unsigned)) != hipSuccess || hipMemset(h->d_range, 0, 4 * sizeof(unsigned)) != hipSuccess ||
+      hipMalloc(&h->d_range, 8 * sizeof(unsigned)) != hipSuccess || hipMemset(h->d_range, 0, 8 * sizeof(unsigned)) != hipSuccess ||
       hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) {
     if (h->d_tab) (void)hipFree(h->d_tab);
     if (h->d_range) (void)hipFree(h->d_range);
@@ -1844,6 +2014,44 @@ int nsrw_range_status(nsrw_handle hh, unsigned long long* passes, unsigned long 
   if (passes) *passes = r[1];
   if (passes_rerun) *passes_rerun = r[2];
   return 0;
+}
+
+int nsrw_range_rows_status(nsrw_handle hh, unsigned long long* rows, unsigned long long* rows_rerun) {
+  Handle* h = reinterpret_cast<Handle*>(hh);
+  if (!h) return fail("nsrw_range_rows_status: null handle");
+  NSRW_DEVICE(h);
+  unsigned long long r[2] = {0, 0};
+  NSRW_HIP(hipDeviceSynchronize());
+  NSRW_HIP(hipMemcpy(r, h->d_range + 4, sizeof r, hipMemcpyDeviceToHost));
+  if (rows) *rows = r[0];
+  if (rows_rerun) *rows_rerun = r[1];
+  return 0;
+}
+
+int nsrw_rerun_rows_plan(const uint32_t* words, int64_t n_words, int64_t M, int tile_rows, int32_t* list_out, int64_t max) {
+  if (n_words < 0 || (n_words > 0 && !words) || M < 0 || (tile_rows != 128 && tile_rows != 256) || max < 0 || (max > 0 && !list_out)) {
+    fail("nsrw_rerun_rows_plan: n_words, M, max >= 0 with their buffers, tile_rows 128 or 256");
+    return -1;
+  }
+  const int64_t mblocks = (M + tile_rows - 1) / tile_rows, wpb = tile_rows / 32;
+  if (mblocks > 0x7fffffff) { fail("nsrw_rerun_rows_plan: more tile blocks than an int32 names"); return -1; }
+  int64_t count = 0;
+  for (int64_t mb = 0; mb < mblocks; ++mb) {
+    bool any = false;
+    for (int64_t q = 0; q < wpb && !any; ++q) {
+      const int64_t wi = mb * wpb + q;
+      if (wi >= n_words || wi * 32 >= M) break;
+      uint32_t w = words[wi];
+      const int64_t left = M - wi * 32;
+      if (left < 32) w &= (1u << (int)left) - 1u;
+      any = w != 0u;
+    }
+    if (any) {
+      if (count < max) list_out[count] = (int32_t)mb;
+      ++count;
+    }
+  }
+  return (int)count;
 }
 
 int nsrw_destroy(nsrw_handle hh) {
@@ -2089,7 +2297,9 @@ int nsrw_run_network(nsrw_handle hh, int net_id, const float* d_pts, const float
   NSRW_DEVICE(h);
   hipStream_t st = static_cast<hipStream_t>(stream);
   // points per pass: what the workspace holds of [E | ED | FA | HV | RAW | H0 | H1]
-  const size_t per_pt = (size_t)(n.Ci + n.Cv + n.ldfa + n.W2p + 32 + 2 * n.Wp) * 4 + 64;
+  // (+ 1 byte a point on a handle with NSRW_FLAG_RERUN_ROWS: rows_bytes is 4 (1 / 32 + 1 / 128 + 1 / 256) = 0.18 bytes a point and 20
+  // bytes; the 4096 below cover the eight 256-byte roundings of the carve)
+  const size_t per_pt = (size_t)(n.Ci + n.Cv + n.ldfa + n.W2p + 32 + 2 * n.Wp) * 4 + 64 + ((h->cfg.flags & NSRW_FLAG_RERUN_ROWS) ? 1 : 0);
   long long PB = (long long)((ws_bytes > 4096 ? ws_bytes - 4096 : 0) / per_pt) / 128 * 128;
   if (PB < 128) return fail("nsrw_run_network: workspace too small");
   PB = std::min<long long>(PB, (n_pts + 127) / 128 * 128);
@@ -2097,7 +2307,9 @@ int nsrw_run_network(nsrw_handle hh, int net_id, const float* d_pts, const float
   Chunk k;
   k.E = c.f(PB * n.Ci); k.ED = c.f(PB * n.Cv); k.FA = c.f(PB * n.ldfa); k.HV = c.f(PB * n.W2p); k.RAW = c.f(PB * 32);
   k.H = {c.f(PB * n.Wp), c.f(PB * n.Wp)};
+  carve_rows(h->cfg.flags, PB, c, k);       // (per_pt counts it)
   if (c.off > ws_bytes) return fail("nsrw_run_network: workspace too small");
+  if (k.rows.words) NSRW_HIP(hipMemsetAsync(k.rows.words, 0, rows_bytes(PB), st));
   const bool cap = capturing(st);
   if (!cap) NSRW_HIP(hipEventRecord(h->ev0, st));
   h->chunks = 0;
@@ -2275,6 +2487,23 @@ int nsrw_embed_vjp(int device, const float* d_x, const float* d_grad_out, int64_
   NSRW_HIP(guard_.err);
   hipLaunchKernelGGL(kw_embed_vjp, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), d_x, d_grad_out,
                      (long long)n_points, multires, d_grad_x);
+  NSRW_HIP(hipGetLastError());
+  return 0;
+}
+
+int nsrw_rerun_rows_list(int device, const uint32_t* d_words, int64_t M, int tile_rows, int32_t* d_list, int64_t max, uint32_t* d_range,
+                         void* stream) {
+  if (!d_words || !d_list) return fail("nsrw_rerun_rows_list: null argument");
+  if (M < 1 || (tile_rows != 128 && tile_rows != 256) || M / tile_rows >= 0x7fffffffll || max < (M + tile_rows - 1) / tile_rows)
+    return fail("nsrw_rerun_rows_list: M >= 1, tile_rows 128 or 256, and room for every block of the pass in the list");
+  DeviceGuard guard_(device);
+  NSRW_HIP(guard_.err);
+  RowsListArgs a{};
+  a.words = d_words; a.M = M; a.n_words = (int)((M + 31) / 32); a.tile_rows = tile_rows;
+  a.list = d_list; a.list_max = (int)std::min<int64_t>(max, 0x7fffffff);
+  a.range = d_range; a.tally = d_range != nullptr;
+  const long long mblocks = (M + tile_rows - 1) / tile_rows;
+  hipLaunchKernelGGL(kw_rows_list, dim3((unsigned)((mblocks + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   NSRW_HIP(hipGetLastError());
   return 0;
 }

@@ -43,6 +43,10 @@ struct GemmArgs {
   float cscale;                            // f16x2: 2^-sw, the weight scale of this matrix undone in the epilogue (bf16x3: 1)
   unsigned* range_flag;                    // f16x2: set when an activation leaves fp16's range (the caller re-runs the pass on bf16x3)
   const unsigned* run_if;                  // nullable: the launch does nothing unless *run_if != 0 (the bf16x3 re-run of such a pass)
+  // the row-granular re-run (NSRW_FLAG_RERUN_ROWS; the *_rows kernels below read these, the others never do):
+  unsigned* row_words;                     // [n_words] one bit per row of the pass, word = row / 32, bit = row % 32: f16x2 sets, bf16x3 reads
+  const int* row_list;                     // bf16x3: [0] how many M-blocks of this launch's tile height hold a flagged row, [1 ..] which (kw_rows_list)
+  int n_words, list_max;                   // (M + 31) / 32; entries the list has room for
 };
 
 constexpr unsigned kPermHi16 = 0x07060302u;          // V_PERM_B32(y, x): {y.hi16, x.hi16}
@@ -122,8 +126,22 @@ template <int NJ, int WM> constexpr int wgs_per_cu() { return WM == 4 ? (NJ >= 3
 template <int NP> constexpr int split_chunks() { return NP == 1 ? 2 : NP; }
 template <int NJ, int WM, int NP> constexpr int split_lds_bytes() { return 2 * (2 * WM + 2 * NJ) * split_chunks<NP>() * 1024; }
 
-template <int NJ, int EPI, int WM, int NP>
+// ROWS: the row-granular re-run (DESIGN.md 8).  The bodies without it are what they were.
+//   f16x2 (kBits): a lane stages the SAME row in every k16 block of a tile (am below), so the magnitude it has seen is that row's.  Per
+//     tile, one ballot folded to 32 bits (both k halves of a row sit on lanes l and l + 32) and one atomicOr by one lane into the word of
+//     the wave's 32 aligned rows, when it is non-zero; clamped rows set no bit; *range_flag is not touched (kw_rows_list sets it).
+//     The A prefetch and astore run across tile boundaries -- the odd stage of a tile's LAST k pair splits the NEXT tile's stage 0 before
+//     this tile's epilogue -- so there are TWO accumulators, amax (this tile's rows) and amax_nxt (the next tile's), and that one astore
+//     goes to amax_nxt by a select on `last` (two v_cndmask around the stage: the steady state stays branch-free); the epilogue
+//     folds amax, then amax = amax_nxt, amax_nxt = 0.
+//   bf16x3 (kList): the M-blocks come from row_list -- position p of the XCD-aware walk is M-block row_list[1 + p], p < row_list[0], read
+//     on the device -- and the epilogue stores / accumulates only the rows whose bit is set in row_words.  The other rows of a listed
+//     tile are computed (from whatever their input rows hold) and dropped: rows do not mix.  A stored element's sum is the one of the
+//     whole-pass bf16x3 kernel: k16 blocks ascending, the six products in their order.
+template <int NJ, int EPI, int WM, int NP, bool ROWS = false>
 __device__ __forceinline__ void gemm_split_body(const GemmArgs& g, char* const smem) {
+  constexpr bool kBits = ROWS && NP == 2, kList = ROWS && NP == 3;
+  static_assert(!ROWS || NP == 2 || NP == 3, "the row-granular re-run is f16x2's (bits) and bf16x3's (list)");
   constexpr int TN = 64 * NJ, NCB = 2 * NJ;                        // columns / col-blocks of a tile
   constexpr int kTM = 64 * WM, NW = 2 * WM;                        // rows of a tile / waves
   constexpr int NPC = split_chunks<NP>();
@@ -134,7 +152,11 @@ __device__ __forceinline__ void gemm_split_body(const GemmArgs& g, char* const s
   const int wm = wave % WM, wn = wave / WM;
   const int KB = (g.K1 + g.K2) >> 4, KB1 = g.K1 >> 4;
   const int lrow = lane & 31, lh = lane >> 5;
-  const long long mblocks = (g.M + kTM - 1) / kTM;
+  long long mblocks = (g.M + kTM - 1) / kTM;
+  if constexpr (kList) {
+    NSRW_CHECK(g.row_list[0] >= 0 && g.row_list[0] <= g.list_max && g.row_list[0] <= mblocks);
+    mblocks = g.row_list[0];
+  }
   const long long total = ((mblocks + 7) / 8) * 8 * g.n_tiles;
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)g.Wb, 0, (int)g.wb_bytes, 0x00020000);
 
@@ -142,7 +164,13 @@ __device__ __forceinline__ void gemm_split_body(const GemmArgs& g, char* const s
   auto coords = [&](long long t, Tile& tl) -> bool {               // the XCD-aware walk
     const int xcd = (int)(t & 7);
     const long long j = t >> 3;
-    const long long mb = (j / g.n_tiles) * 8 + xcd;
+    long long mb = (j / g.n_tiles) * 8 + xcd;
+    if constexpr (kList) {                                         // mb is a list position: the XCD-aware order runs over those
+      if (mb >= mblocks) return false;
+      NSRW_CHECK(mb < g.list_max);
+      mb = g.row_list[1 + mb];
+      NSRW_CHECK(mb >= 0 && mb * kTM < g.M);
+    }
     tl.m0 = mb * kTM;
     if (tl.m0 >= g.M) return false;
     tl.n0 = (int)(j % g.n_tiles) * TN;
@@ -191,14 +219,15 @@ __device__ __forceinline__ void gemm_split_body(const GemmArgs& g, char* const s
     }
   };
   float amax = 0.0f;                                               // f16x2: largest activation magnitude this lane has split
-  auto astore = [&](int buf, const f32x4 (&r)[2]) {
+  [[maybe_unused]] float amax_nxt = 0.0f;                          // kBits: ... of the NEXT tile's rows (amax: of this tile's)
+  auto astore = [&](int buf, const f32x4 (&r)[2], float& am) {
     u32x4 p[NPC];
 #ifdef NSRW_EXP_NOSPLIT
     p[0] = __builtin_bit_cast(u32x4, r[0]); p[1] = __builtin_bit_cast(u32x4, r[1]);
     if constexpr (NPC == 3) p[2] = p[0];
 #else
     if constexpr (NP == 3) split8_b3(r[0], r[1], p);
-    else if constexpr (NP == 2) split8_h2(r[0], r[1], p, amax);
+    else if constexpr (NP == 2) split8_h2(r[0], r[1], p, am);
     else { p[0] = __builtin_bit_cast(u32x4, r[0]); p[1] = __builtin_bit_cast(u32x4, r[1]); }
 #endif
     char* l = smem + buf * kStage + wave * kFrag + lane * 16;
@@ -210,7 +239,7 @@ __device__ __forceinline__ void gemm_split_body(const GemmArgs& g, char* const s
   // (sched_group_barrier): the B fragments of column block j + 1 are read behind the first MFMAs of block j, and the split's
   // 44 VALU instructions run four per MFMA in the shadow of the last block's twelve -- left alone, hipcc reads every fragment
   // just in time (an exposed LDS latency per column block) and runs the whole split behind the last MFMA with an idle pipe.
-  auto stage = [&](int buf, f32x16 (&acc)[2][NJ], const f32x4 (&r)[2]) {
+  auto stage = [&](int buf, f32x16 (&acc)[2][NJ], const f32x4 (&r)[2], float& am) {
     const char* pa = smem + buf * kStage + (wm * 2) * kFrag + lane * 16;
     const char* pb = smem + buf * kStage + kABytes + (wn * NJ) * kFrag + lane * 16;
     u32x4 fa[2][NPC], fb[2][NPC];
@@ -260,7 +289,7 @@ __device__ __forceinline__ void gemm_split_body(const GemmArgs& g, char* const s
       }
     }
 #undef NSRW_FRAG
-    astore(buf ^ 1, r);
+    astore(buf ^ 1, r, am);
 #ifndef NSRW_EXP_NOFRAG
     NSRW_SGB(NSRW_MASK_DSRD, 3 * NPC);
 #pragma unroll
@@ -305,7 +334,7 @@ __device__ __forceinline__ void gemm_split_body(const GemmArgs& g, char* const s
   __builtin_amdgcn_sched_barrier(0);
   gload(cur, 1, ra[1]);
   __builtin_amdgcn_sched_barrier(0);
-  astore(0, ra[0]);
+  astore(0, ra[0], amax);
   stage_end();
   while (true) {
     long long tn = t + gridDim.x;
@@ -329,14 +358,21 @@ __device__ __forceinline__ void gemm_split_body(const GemmArgs& g, char* const s
       __builtin_amdgcn_sched_barrier(0);                           // the A loads are the stage's YOUNGEST two VMEM operations:
       gload(nx, k2, ra[0]);                                        // stage_end's vmcnt(2) leaves exactly them in flight
       __builtin_amdgcn_sched_barrier(0);                           // ... and the fetches stay at the head of the stage
-      stage(0, acc, ra[1]);
+      stage(0, acc, ra[1], amax);
       stage_end();
       // odd stage: MFMAs on buffer 1; weights of stage kb + 2 -> buffer 0; A of kb + 3 -> ra[1]; A pieces of kb + 2 -> buffer 0
       dma(nx, k2, 0);
       __builtin_amdgcn_sched_barrier(0);
       gload(nx, k2 + 1, ra[1]);
       __builtin_amdgcn_sched_barrier(0);
-      stage(1, acc, ra[0]);
+      if constexpr (kBits) {                                       // this astore splits stage k2 of nx: the next tile's rows when `last`
+        float am = last ? amax_nxt : amax;
+        stage(1, acc, ra[0], am);
+        amax_nxt = last ? am : amax_nxt;
+        amax = last ? amax : am;
+      } else {
+        stage(1, acc, ra[0], amax);
+      }
       stage_end();
     }
 
@@ -344,7 +380,19 @@ __device__ __forceinline__ void gemm_split_body(const GemmArgs& g, char* const s
     // the matrix -- all of them but the last M-block's and a ragged N edge -- takes the predicate-free form: 16 stores per
     // block back to back.  (Per-row predicates put every store into a conditional block of its own, and hipcc then waits
     // vmcnt(0) in front of each: the stores of a tile serialise on the memory round trip.)
-    const bool inside = cur.m0 + kTM <= g.M && cur.n0 + TN <= g.N;
+    if constexpr (kBits) {
+      // the rows of THIS tile that left fp16's range -> their word (N-tiles of one M-block set the same bits again: harmless)
+      const unsigned long long out = __builtin_amdgcn_ballot_w64(!(amax < 65504.0f) && cur.m0 + 32 * wave + lrow < g.M);
+      const unsigned w = (unsigned)out | (unsigned)(out >> 32);
+      if (w != 0u && lane == 0) {
+        const long long wi = (cur.m0 >> 5) + wave;
+        NSRW_CHECK(wi >= 0 && wi < g.n_words);
+        atomicOr(&g.row_words[wi], w);
+      }
+      amax = amax_nxt;
+      amax_nxt = 0.0f;
+    }
+    const bool inside = !kList && cur.m0 + kTM <= g.M && cur.n0 + TN <= g.N;
     if (inside) {
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
@@ -395,13 +443,20 @@ __device__ __forceinline__ void gemm_split_body(const GemmArgs& g, char* const s
           const long long mt = cur.m0 + wm * 64 + i * 32 + 4 * lh;
           float* cb = g.C + mt * g.ldc + n;
           const int rows_left = (int)(g.M - mt < 32 ? g.M - mt : 32);
+          [[maybe_unused]] unsigned rowbits = 0u;                  // kList: the bits of this lane's 28 rows from mt on
+          if constexpr (kList) {
+            const long long wi = (cur.m0 >> 5) + wm * 2 + i;
+            NSRW_CHECK(wi >= 0);
+            rowbits = wi < g.n_words ? g.row_words[wi] >> (4 * lh) : 0u;    // (no word behind row M: no bit)
+          }
+          auto rowok = [&](int ro) { return !kList || ((rowbits >> ro) & 1u) != 0u; };
           float aux[16];
           if constexpr (EPI == kMaskEpi) {
             const float* sb = g.mask + mt * g.ldm + n;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
               const int ro = 8 * (r >> 2) + (r & 3);
-              aux[r] = (ncol && (full_rows || ro < rows_left)) ? sb[ro * g.ldm] : 0.0f;
+              aux[r] = (ncol && (full_rows || ro < rows_left) && rowok(ro)) ? sb[ro * g.ldm] : 0.0f;
             }
           }
 #pragma unroll
@@ -410,7 +465,7 @@ __device__ __forceinline__ void gemm_split_body(const GemmArgs& g, char* const s
             float v = (NP == 2 ? acc[i][j][r] * g.cscale : acc[i][j][r]) + b;
             if constexpr (EPI == kRelu) v = (v < 0.0f) ? 0.0f : v;
             if constexpr (EPI == kMaskEpi) v = (aux[r] > 0.0f) ? v : 0.0f;
-            if (ncol && (full_rows || ro < rows_left)) {
+            if (ncol && (full_rows || ro < rows_left) && rowok(ro)) {
               NSRW_CHECK(mt + ro < g.M && n < g.ldc);
               if constexpr (EPI == kAccum) v = cb[ro * g.ldc] + v;
               cb[ro * g.ldc] = v;
@@ -424,7 +479,7 @@ __device__ __forceinline__ void gemm_split_body(const GemmArgs& g, char* const s
     cur = nxt;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // no LDS-DMA may outlive the workgroup
-  if constexpr (NP == 2) {
+  if constexpr (NP == 2 && !kBits) {
     // (NaN compares false on both sides and passes through the pieces as NaN, as through an fp32 GEMM; inf is out of range)
     if (__builtin_amdgcn_ballot_w64(!(amax < 65504.0f)) != 0ull && lane == 0) atomicOr(g.range_flag, 1u);
   }
@@ -446,4 +501,18 @@ template <int NJ, int EPI, int WM>
 __global__ void __launch_bounds__(128 * WM, (wgs_per_cu<NJ, WM>())) kw_gemm_h2(const GemmArgs g) {
   __shared__ __attribute__((aligned(1024))) char smem[split_lds_bytes<NJ, WM, 2>()];
   gemm_split_body<NJ, EPI, WM, 2>(g, smem);
+}
+
+// the row-granular twins (GemmArgs::row_words / row_list): f16x2 sets a bit per row that leaves the range, bf16x3 walks the listed
+// M-blocks and stores the flagged rows alone
+template <int NJ, int EPI, int WM>
+__global__ void __launch_bounds__(128 * WM, (wgs_per_cu<NJ, WM>())) kw_gemm_b3_rows(const GemmArgs g) {
+  __shared__ __attribute__((aligned(1024))) char smem[split_lds_bytes<NJ, WM, 3>()];
+  gemm_split_body<NJ, EPI, WM, 3, true>(g, smem);
+}
+
+template <int NJ, int EPI, int WM>
+__global__ void __launch_bounds__(128 * WM, (wgs_per_cu<NJ, WM>())) kw_gemm_h2_rows(const GemmArgs g) {
+  __shared__ __attribute__((aligned(1024))) char smem[split_lds_bytes<NJ, WM, 2>()];
+  gemm_split_body<NJ, EPI, WM, 2, true>(g, smem);
 }

@@ -171,13 +171,21 @@ def _note_range(model, network_fn=None):
         if st["passes_rerun"] and not getattr(model, "_range_warned", False):
             import warnings
             model._range_warned = True
-            switch = network_fn is not None and st["passes_rerun"] > _RANGE_SWITCH_FRAC * max(1, st["passes"])
+            # (a rerun="rows" handle re-computes the flagged points alone: what it pays twice for is its share of ROWS, not of passes)
+            rows = getattr(model, "rerun", "pass") == "rows"
+            part, whole = (st["rows_rerun"], st["rows"]) if rows else (st["passes_rerun"], st["passes"])
+            switch = network_fn is not None and part > _RANGE_SWITCH_FRAC * max(1, whole)
             if switch:
                 network_fn.__dict__["_nsr_force_mlp"] = (_RANGE_SWITCH_MLP, getattr(model, "weights_version", None))
-            warnings.warn("neural_sim_nerf_amd: %d of %d network passes of the layered renderer left the fp16 range of its f16x2 GEMMs "
-                          "and were run again on bf16x3 inside the call (the results are that arithmetic's).%s"
-                          % (st["passes_rerun"], st["passes"], "  This network now gets the bf16x3 GEMMs outright." if switch else
-                             "  NSR_WIDE_MLP=bf16x3 selects them outright."), RuntimeWarning)
+            tail = "  This network now gets the bf16x3 GEMMs outright." if switch else "  NSR_WIDE_MLP=bf16x3 selects them outright."
+            if rows:
+                warnings.warn("neural_sim_nerf_amd: %d of %d points of the layered renderer's network passes left the fp16 range of its "
+                              "f16x2 GEMMs and were computed again on bf16x3 inside the call, in %d of %d passes (those points' results "
+                              "are that arithmetic's).%s" % (part, whole, st["passes_rerun"], st["passes"], tail), RuntimeWarning)
+            else:
+                warnings.warn("neural_sim_nerf_amd: %d of %d network passes of the layered renderer left the fp16 range of its f16x2 GEMMs "
+                              "and were run again on bf16x3 inside the call (the results are that arithmetic's).%s"
+                              % (st["passes_rerun"], st["passes"], tail), RuntimeWarning)
         return
     if getattr(model, "mlp", None) != "f16x2":
         return

@@ -106,6 +106,9 @@ SIGNATURES = {
     "nsrw_stages_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "nsrw_debug_bounds_status": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
     "nsrw_range_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
+    "nsrw_range_rows_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
+    "nsrw_rerun_rows_list": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "nsrw_rerun_rows_plan": (C.c_int, [C.POINTER(C.c_uint32), C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int32), C.c_int64]),
     "nsrw_sample_pdf": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
     "nsrw_embed_vjp": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
@@ -118,6 +121,7 @@ FLAG_TRUNK_KEEP = 256
 FLAG_STAGES_WAVE = 512
 FLAG_TRUNK_RERUN = 1024
 _EMBED_ONCHIP = 1 << 11       # NSRW_FLAG_EMBED_ONCHIP; public as wide.FLAG_EMBED_ONCHIP through __getattr__ below
+_RERUN_ROWS = 1 << 12         # NSRW_FLAG_RERUN_ROWS; public as wide.FLAG_RERUN_ROWS, the same way
 MLPS = ("bf16x3", "fp32", "f16x2")
 TRUNKS = ("layers", "onchip")
 HEADS = ("layers", "onchip")
@@ -125,6 +129,7 @@ TRUNK_BWDS = ("layers", "onchip")
 TRUNK_KEEPS = ("layers", "onchip")
 TRUNK_RERUNS = ("layers", "onchip")     # the bf16x3 re-run of a pass whose trunk ran on chip: a launch per layer, or one (FLAG_TRUNK_RERUN)
 EMBEDS = ("layers", "onchip")           # the encodings of a pass whose f16x2 launch is on chip: the kw_embed launch, or in that launch (FLAG_EMBED_ONCHIP)
+RERUNS = ("pass", "rows")               # the unit of an f16x2 handle's bf16x3 re-run: the pass over a chunk, or the point (FLAG_RERUN_ROWS)
 STAGES = ("threads", "wave")    # the per-ray stages between the network passes: one thread per ray, or one wave (FLAG_STAGES_WAVE)
 STAGE_COMPOSITE, STAGE_SAMPLE_PDF, STAGE_COMPOSITE_BWD = 0, 1, 2
 STAGE_IDS = {"composite": STAGE_COMPOSITE, "sample_pdf": STAGE_SAMPLE_PDF, "composite_bwd": STAGE_COMPOSITE_BWD}
@@ -137,10 +142,12 @@ _bound = None
 
 
 def __getattr__(name):
-    """wide.FLAG_EMBED_ONCHIP.  Not a module global: tests/test_wide_trunk_rerun_host.py takes a census of the globals named FLAG_*
-    (ten beside FLAG_TRUNK_RERUN) to show that bit 10 is free, and this flag came after it."""
+    """wide.FLAG_EMBED_ONCHIP, wide.FLAG_RERUN_ROWS.  Not module globals: tests/test_wide_trunk_rerun_host.py takes a census of the
+    globals named FLAG_* (ten beside FLAG_TRUNK_RERUN) to show that bit 10 is free, and these flags came after it."""
     if name == "FLAG_EMBED_ONCHIP":
         return _EMBED_ONCHIP
+    if name == "FLAG_RERUN_ROWS":
+        return _RERUN_ROWS
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
@@ -282,6 +289,53 @@ def resolve_rerun(wish, environ, mlp, trunk):
     return v
 
 
+def resolve_rerun_unit(wish, environ, mlp, trunk):
+    """The unit of the bf16x3 re-run on a handle of arithmetic `mlp` with trunk=`trunk`: the caller's wish, else $NSR_WIDE_RERUN, else
+    "pass".  Resolved beside `stages` / `trunk_rerun`, by their rule: only an f16x2 handle with trunk="layers" has the row-granular
+    form, so the environment's wish is dropped elsewhere and an explicit "rows" there raises NotImplementedError.  Pure: no device, no
+    library."""
+    v = wish or environ.get("NSR_WIDE_RERUN") or RERUNS[0]
+    if v not in RERUNS:
+        raise ValueError("rerun must be one of %s (got %r)" % (RERUNS, v))
+    can = mlp == "f16x2" and trunk == "layers"
+    if not wish and not can:
+        v = RERUNS[0]
+    if v == "rows" and not can:
+        raise NotImplementedError("rerun=\"rows\" re-runs the flagged rows of a per-layer f16x2 pass: it needs mlp=\"f16x2\" and "
+                                  "trunk=\"layers\" (got mlp=%r, trunk=%r)" % (mlp, trunk))
+    return v
+
+
+def rerun_rows_plan(words, M, tile_rows=256):
+    """nsrw_rerun_rows_plan (diagnostic; no device, no handle): the ascending tile blocks of `tile_rows` (128 or 256) rows of an M-row
+    pass that hold a flagged row, from the row bits `words` (uint32; bit r % 32 of word r // 32 = row r; rows >= M do not count) -- the
+    host restatement of the list kernel of rerun="rows"."""
+    lib = load()
+    w = np.ascontiguousarray(words, dtype=np.uint32)
+    out = np.zeros(max(1, (int(M) + int(tile_rows) - 1) // max(int(tile_rows), 1)), dtype=np.int32)
+    count = lib.nsrw_rerun_rows_plan(w.ctypes.data_as(C.POINTER(C.c_uint32)), w.size, int(M), int(tile_rows),
+                                     out.ctypes.data_as(C.POINTER(C.c_int32)), out.size)
+    if count < 0:
+        raise _lib.NsrError(lib.nsrw_last_error().decode("utf-8", "replace"))
+    return [int(x) for x in out[:count]]
+
+
+def rerun_rows_list(words, M, tile_rows=256, device=None):
+    """nsrw_rerun_rows_list (diagnostic stage entry; no handle): the list kernel of rerun="rows" on the row bits `words` -> (the
+    listed blocks in the order the kernel wrote them, rows seen, rows flagged, the range word)."""
+    lib = load()
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else int(device))
+    w = torch.as_tensor(np.ascontiguousarray(words, dtype=np.uint32).view(np.int32), device=dev)
+    blocks = (int(M) + int(tile_rows) - 1) // int(tile_rows)
+    lst = torch.zeros(1 + max(blocks, 1), dtype=torch.int32, device=dev)
+    rng = torch.zeros(8, dtype=torch.int32, device=dev)
+    check(lib.nsrw_rerun_rows_list(dev.index, _dev(w), int(M), int(tile_rows), _dev(lst), blocks, _dev(rng), _stream_ptr(dev)))
+    torch.cuda.synchronize(dev)
+    l, r = lst.cpu().numpy(), rng.cpu().numpy().view(np.uint32)
+    counts = r[4:8].view(np.uint64)
+    return [int(x) for x in l[1:1 + int(l[0])]], int(counts[0]), int(counts[1]), int(r[0])
+
+
 def stage_plan(stage, samples, n_importance=0, flags=FLAG_STAGES_WAVE):
     """nsrw_stage_plan (diagnostic; no device, no handle): how a handle created with `flags` runs the per-ray stage `stage`
     (STAGE_COMPOSITE / STAGE_SAMPLE_PDF / STAGE_COMPOSITE_BWD, or its name in STAGE_IDS) of a pass with `samples` samples per ray
@@ -413,7 +467,11 @@ def workspace_cap_env():
     """Upper bound of the workspace a launch call may use: $NSR_WIDE_WORKSPACE_GB, else 64 GiB (r06: of 288 GB; 16 GiB cost a 400x400 forward + gradient call
     6-8 % in chunk overheads, profiles/r06/extra/ab_wide_h2_w512.txt) -- and never more than half of the free memory
     (workspace_cap_bytes).  A smaller workspace means more,
-    smaller chunks of rays -- never another result."""
+    smaller chunks of rays.  On fp32 and bf16x3 handles that is never another result, and on an f16x2 handle neither while no pass
+    leaves fp16's range.  An f16x2 pass that does is re-run on bf16x3 over its whole chunk (rerun="pass", the default): results then
+    stay arithmetic-equivalent -- fp32-grade either way -- but are not bit-stable across chunkings, since which rays share a re-run
+    pass depends on the chunk.  With rerun="rows" only the points that left the range are re-computed, and the bits are a ray's own:
+    stable across chunkings and neighbours."""
     return int(float(os.environ.get("NSR_WIDE_WORKSPACE_GB", "64")) * (1 << 30))
 
 
@@ -487,7 +545,7 @@ class WideModel:
 
     def __init__(self, sd_coarse, sd_fine=None, device=None, n_importance=128, white_bkgd=False, lindisp=False, n_samples=64,
                  mlp=None, trunk=None, heads=None, trunk_width=None, trunk_bwd=None, trunk_keep=None, stages=None,
-                 trunk_rerun=None, embed=None):
+                 trunk_rerun=None, embed=None, rerun=None):
         """mlp: the arithmetic of the layer GEMMs -- "bf16x3" (bf16 MFMAs on three-way split fp32 operands, fp32-grade results at
         2.67x the matrix-pipe rate: csrc/nsr_wide_gemm.inc), "fp32" (fp32 MFMAs, the strict mode) or "f16x2" (fp16 MFMAs with
         two-piece operands -- the fused default kernel's arithmetic; a network pass that leaves fp16's range is re-run on bf16x3
@@ -530,7 +588,14 @@ class WideModel:
         forward -- that launch computes the position encodings of its points itself, and in a heads form the direction encodings
         too; behind a trunk-only launch kw_embed writes the direction encodings alone; a conditional kw_embed stands in front of the
         bf16x3 re-run -- the same bits, the same workspace: embed_plan, embed_status); default $NSR_WIDE_EMBED (which handles that
-        cannot honour it ignore, while an explicit embed="onchip" there raises), else "layers"."""
+        cannot honour it ignore, while an explicit embed="onchip" there raises), else "layers".
+        rerun: the unit of the f16x2 safety net -- "pass" (a network pass over a chunk in which any value reaches fp16's largest number
+        is run again on bf16x3 as a whole: every ray of the chunk then has bf16x3's bits, so bits depend on the neighbours and on the
+        chunk size once a pass re-runs) or "rows" (mlp="f16x2" with trunk="layers" only: the f16x2 GEMMs flag the points that leave the
+        range, and the bf16x3 chain walks the tile blocks that hold one and stores those points alone -- a flagged point has a bf16x3
+        handle's bits, every other point keeps its f16x2 bits, and a ray's bits depend on that ray only; range_status() counts
+        `rows` / `rows_rerun`); default $NSR_WIDE_RERUN (which handles that cannot honour it ignore, while an explicit rerun="rows"
+        there raises), else "pass"."""
         mlp = mlp or os.environ.get("NSR_WIDE_MLP") or DEFAULT_MLP
         if mlp not in MLPS:
             raise ValueError("mlp must be one of %s (got %r)" % (MLPS, mlp))
@@ -540,6 +605,7 @@ class WideModel:
         self.stages = resolve_stages(stages, os.environ)
         self.trunk_rerun = resolve_rerun(trunk_rerun, os.environ, mlp, self.trunk)
         self.embed = resolve_embed(embed, os.environ, mlp, self.trunk)
+        self.rerun = resolve_rerun_unit(rerun, os.environ, mlp, self.trunk)
         self.mlp = "layered-" + mlp
         if not torch.cuda.is_available():
             raise _lib.NsrError("no HIP device visible: the render path has no CPU fallback")
@@ -565,7 +631,8 @@ class WideModel:
                          _mlp_flags(mlp) | _trunk_flags(self.trunk, self.trunk_width, self.heads, self.trunk_bwd, self.trunk_keep) |
                          (FLAG_STAGES_WAVE if self.stages == "wave" else 0) |
                          (FLAG_TRUNK_RERUN if self.trunk_rerun == "onchip" else 0) |
-                         (_EMBED_ONCHIP if self.embed == "onchip" else 0))
+                         (_EMBED_ONCHIP if self.embed == "onchip" else 0) |
+                         (_RERUN_ROWS if self.rerun == "rows" else 0))
         h = C.c_void_p()
         check(self.lib.nsrw_create(C.byref(cfg), C.byref(h)))
         self.h = h
@@ -783,12 +850,17 @@ class WideModel:
     def range_status(self):
         """fp32 / bf16x3: no range to leave.  f16x2: `passes` network passes launched so far, `passes_rerun` of them re-run on
         bf16x3 because an activation reached fp16's largest number; nothing is ever dropped.  (The keys of NsrModel.range_status
-        are kept: `points` / `rays` stay 0 -- the unit of the layered renderer's safety net is a pass over a chunk of rays.)"""
-        out = dict(last_items=0, points=0, rays=0, dropped_items=0, passes=0, passes_rerun=0)
+        are kept: `points` / `rays` stay 0 -- the unit of the layered renderer's safety net is a pass over a chunk of rays.)
+        rerun="rows" handles: `rows` points those passes covered and `rows_rerun` of them re-computed on bf16x3 (a pass counts in
+        `passes_rerun` when any of its rows was); both 0 on every other handle."""
+        out = dict(last_items=0, points=0, rays=0, dropped_items=0, passes=0, passes_rerun=0, rows=0, rows_rerun=0)
         if self.mlp == "layered-f16x2":
             a, b = C.c_ulonglong(), C.c_ulonglong()
             check(self.lib.nsrw_range_status(self.h, C.byref(a), C.byref(b)))
             out["passes"], out["passes_rerun"] = int(a.value), int(b.value)
+            if self.rerun == "rows":
+                check(self.lib.nsrw_range_rows_status(self.h, C.byref(a), C.byref(b)))
+                out["rows"], out["rows_rerun"] = int(a.value), int(b.value)
         return out
 
     def keep_status(self):
