@@ -193,6 +193,9 @@ typedef struct NsrwOut {
 
 const char* nsrw_last_error(void);
 
+/* Which opt-in flags go together is stated once on each side of this interface: the table kFlagNeeds in csrc/nsr_wide.hip (what each
+ * flag needs and excludes; nsrw_create refuses the first row that is not met, nsrw_flags_refusal says which) and wide.KNOBS in
+ * neural_sim_nerf_amd/wide.py (the same for WideModel's arguments).  tests/test_wide_options_host.py holds the two to each other. */
 int nsrw_create(const NsrwConfig* cfg, nsrw_handle* out);
 int nsrw_destroy(nsrw_handle h);
 
@@ -300,6 +303,10 @@ typedef struct NsrwGemmPart {
   int32_t nj, wm, tiles, col_block;
 } NsrwGemmPart;
 int nsrw_gemm_plan(int n_packed_rows, int n_stored_columns, int tile_wm, NsrwGemmPart* parts_out, int max_parts);
+
+/* DIAGNOSTIC; needs no device and no handle.  NULL when nsrw_create accepts the flag word `flags`, else the words it refuses it with
+ * (static storage).  Leaves nsrw_last_error alone. */
+const char* nsrw_flags_refusal(int flags);
 
 /* DIAGNOSTIC; needs no device and no handle.  How a handle created with `flags` runs the pts_linears of `net`: onchip = 1
  * -- one kw_trunk_h2<nj> launch over tiles of tile_rows points with lds_bytes of LDS per workgroup -- or onchip = 0 (layer by layer;

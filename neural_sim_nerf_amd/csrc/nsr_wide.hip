@@ -1274,31 +1274,38 @@ OnchipPlan onchip_plan(const NsrwNet& d, int flags) {
   return p;
 }
 
-// the opt-in flags of the on-chip forms and the flag each needs beside it: nsrw_create refuses the first row that is not met
+// the opt-in flags and what each takes of the rest of the flag word: `needs` (0: nothing) must be set beside it, `excludes` must not.
+// The first row that is not met refuses the word (flags_refusal).  wide.KNOBS (neural_sim_nerf_amd/wide.py) states the same
+// dependencies for WideModel's arguments; tests/test_wide_options_host.py holds the two to each other on every combination.
 struct FlagNeeds {
-  int flag, needs;
+  int flag, needs, excludes;
   const char* refusal;
 };
 constexpr FlagNeeds kFlagNeeds[] = {
-    {NSRW_FLAG_TRUNK_ONCHIP, NSRW_FLAG_MLP_F16X2,
+    {NSRW_FLAG_TRUNK_ONCHIP, NSRW_FLAG_MLP_F16X2, 0,
      "nsrw_create: NSRW_FLAG_TRUNK_ONCHIP needs NSRW_FLAG_MLP_F16X2 (the on-chip trunk exists for the f16x2 arithmetic only)"},
-    {NSRW_FLAG_TRUNK_WIDE, NSRW_FLAG_TRUNK_ONCHIP,
+    {NSRW_FLAG_TRUNK_WIDE, NSRW_FLAG_TRUNK_ONCHIP, 0,
      "nsrw_create: NSRW_FLAG_TRUNK_WIDE needs NSRW_FLAG_TRUNK_ONCHIP (it extends the on-chip trunk to padded widths up to 256)"},
-    {NSRW_FLAG_HEADS_ONCHIP, NSRW_FLAG_TRUNK_ONCHIP,
+    {NSRW_FLAG_HEADS_ONCHIP, NSRW_FLAG_TRUNK_ONCHIP, 0,
      "nsrw_create: NSRW_FLAG_HEADS_ONCHIP needs NSRW_FLAG_TRUNK_ONCHIP (the on-chip heads run behind the on-chip trunk, in its launch)"},
-    {NSRW_FLAG_TRUNK_BWD, NSRW_FLAG_TRUNK_ONCHIP,
+    {NSRW_FLAG_TRUNK_BWD, NSRW_FLAG_TRUNK_ONCHIP, 0,
      "nsrw_create: NSRW_FLAG_TRUNK_BWD needs NSRW_FLAG_TRUNK_ONCHIP (the on-chip backward trunk serves the networks the on-chip trunk serves)"},
-    {NSRW_FLAG_TRUNK_KEEP, NSRW_FLAG_TRUNK_BWD,
+    {NSRW_FLAG_TRUNK_KEEP, NSRW_FLAG_TRUNK_BWD, 0,
      "nsrw_create: NSRW_FLAG_TRUNK_KEEP needs NSRW_FLAG_TRUNK_BWD (the kept on-chip forward leaves its relu masks as bits, which only the on-chip backward trunk reads)"},
-    {NSRW_FLAG_TRUNK_RERUN, NSRW_FLAG_TRUNK_ONCHIP,
+    {NSRW_FLAG_TRUNK_RERUN, NSRW_FLAG_TRUNK_ONCHIP, 0,
      "nsrw_create: NSRW_FLAG_TRUNK_RERUN needs NSRW_FLAG_TRUNK_ONCHIP (the on-chip bf16x3 re-run serves the passes whose f16x2 trunk ran on chip)"},
-    {NSRW_FLAG_EMBED_ONCHIP, NSRW_FLAG_TRUNK_ONCHIP,
+    {NSRW_FLAG_EMBED_ONCHIP, NSRW_FLAG_TRUNK_ONCHIP, 0,
      "nsrw_create: NSRW_FLAG_EMBED_ONCHIP needs NSRW_FLAG_TRUNK_ONCHIP (the encodings are computed in the on-chip trunk's launch)"},
-    {NSRW_FLAG_RERUN_ROWS, NSRW_FLAG_MLP_F16X2,
+    {NSRW_FLAG_RERUN_ROWS, NSRW_FLAG_MLP_F16X2, 0,
      "nsrw_create: NSRW_FLAG_RERUN_ROWS needs NSRW_FLAG_MLP_F16X2 (only the f16x2 arithmetic has a range to leave and a re-run)"},
+    {NSRW_FLAG_RERUN_ROWS, 0, NSRW_FLAG_TRUNK_ONCHIP,
+     "nsrw_create: NSRW_FLAG_RERUN_ROWS does not combine with NSRW_FLAG_TRUNK_ONCHIP (the on-chip forms feed one range word per pass)"},
 };
-constexpr const char* kRowsNoOnchip =
-    "nsrw_create: NSRW_FLAG_RERUN_ROWS does not combine with NSRW_FLAG_TRUNK_ONCHIP (the on-chip forms feed one range word per pass)";
+const char* flags_refusal(int flags) {
+  for (const FlagNeeds& r : kFlagNeeds)
+    if ((flags & r.flag) && ((r.needs && !(flags & r.needs)) || (flags & r.excludes))) return r.refusal;
+  return nullptr;
+}
 
 // the decisions as the diagnostic entries report them (no form: every figure 0, and the reason)
 NsrwTrunkPlan as_trunk_plan(const Onchip& c) {
@@ -1970,9 +1977,7 @@ int nsrw_create(const NsrwConfig* cfg, nsrw_handle* out) {
   int count = 0;
   NSRW_HIP(hipGetDeviceCount(&count));
   if (cfg->device < 0 || cfg->device >= count) return fail("nsrw_create: no such device");
-  for (const FlagNeeds& r : kFlagNeeds)
-    if ((cfg->flags & r.flag) && !(cfg->flags & r.needs)) return fail(r.refusal);
-  if ((cfg->flags & NSRW_FLAG_RERUN_ROWS) && (cfg->flags & NSRW_FLAG_TRUNK_ONCHIP)) return fail(kRowsNoOnchip);
+  if (const char* refusal = flags_refusal(cfg->flags)) return fail(refusal);
   GemmCfg gc;
   {
     hipDeviceProp_t prop;
@@ -2345,6 +2350,8 @@ int nsrw_gemm_plan(int n_packed_rows, int n_stored_columns, int tile_wm, NsrwGem
   for (int i = 0; i < std::min(count, max_parts); ++i) parts_out[i] = parts[i];
   return count;
 }
+
+const char* nsrw_flags_refusal(int flags) { return flags_refusal(flags); }
 
 // the views of onchip_plan: 0 and the decision, or -1 for an invalid description (nsrw_last_error says why)
 static int plan_entry(const char* name, const NsrwNet* net, const void* plan_out, int flags, OnchipPlan* p) {

@@ -93,6 +93,7 @@ SIGNATURES = {
                                    C.c_void_p]),
     "nsrw_last_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "nsrw_gemm_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(NsrwGemmPart), C.c_int]),
+    "nsrw_flags_refusal": (C.c_char_p, [C.c_int]),
     "nsrw_trunk_plan": (C.c_int, [C.POINTER(NsrwNet), C.c_int, C.POINTER(NsrwTrunkPlan)]),
     "nsrw_heads_plan": (C.c_int, [C.POINTER(NsrwNet), C.c_int, C.POINTER(NsrwHeadsPlan)]),
     "nsrw_trunk_bwd_plan": (C.c_int, [C.POINTER(NsrwNet), C.c_int, C.POINTER(NsrwTrunkPlan)]),
@@ -120,8 +121,8 @@ FLAG_TRUNK_BWD = 128
 FLAG_TRUNK_KEEP = 256
 FLAG_STAGES_WAVE = 512
 FLAG_TRUNK_RERUN = 1024
-_EMBED_ONCHIP = 1 << 11       # NSRW_FLAG_EMBED_ONCHIP; public as wide.FLAG_EMBED_ONCHIP through __getattr__ below
-_RERUN_ROWS = 1 << 12         # NSRW_FLAG_RERUN_ROWS; public as wide.FLAG_RERUN_ROWS, the same way
+FLAG_EMBED_ONCHIP = 1 << 11
+FLAG_RERUN_ROWS = 1 << 12
 MLPS = ("bf16x3", "fp32", "f16x2")
 TRUNKS = ("layers", "onchip")
 HEADS = ("layers", "onchip")
@@ -136,19 +137,10 @@ STAGE_IDS = {"composite": STAGE_COMPOSITE, "sample_pdf": STAGE_SAMPLE_PDF, "comp
 TRUNK_WIDTHS = (128, 256)       # the largest padded width trunk="onchip" takes: 256 adds the wide form (FLAG_TRUNK_WIDE)
 
 DEFAULT_MLP = "f16x2"           # r06: the fused default kernel's arithmetic; same parity bounds as the fp32 MFMAs and bf16x3 (tests/test_gpu_wide.py
-                                # runs every case on all three), 2.6x / 1.5x their speed; never range-dependent (re-run on bf16x3)
+                                # runs every case on all three), 2.6x / 1.5x their speed; a pass that leaves fp16's range is re-run on
+                                # bf16x3, so the bits are chunk-dependent once a pass re-runs, unless rerun="rows" (workspace_cap_env)
 
 _bound = None
-
-
-def __getattr__(name):
-    """wide.FLAG_EMBED_ONCHIP, wide.FLAG_RERUN_ROWS.  Not module globals: tests/test_wide_trunk_rerun_host.py takes a census of the
-    globals named FLAG_* (ten beside FLAG_TRUNK_RERUN) to show that bit 10 is free, and these flags came after it."""
-    if name == "FLAG_EMBED_ONCHIP":
-        return _EMBED_ONCHIP
-    if name == "FLAG_RERUN_ROWS":
-        return _RERUN_ROWS
-    raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
 
 def load():
@@ -187,10 +179,11 @@ def _mlp_flags(mlp):
     return (FLAG_MLP_BF16X3 if mlp == "bf16x3" else 0) | (FLAG_MLP_F16X2 if mlp == "f16x2" else 0)
 
 
-# The opt-in knobs of the on-chip forms, in the order they are resolved -- a knob may need the ones before it.  name: WideModel's
-# argument and attribute; env: where the wish comes from when the argument is not given; values: what it may be, values[0] the
-# default; on: the value that asks for something; flag: what `on` sets in NsrwConfig.flags; needs: what `on` takes of mlp and of the
-# knobs before it; refusal: NotImplementedError's words for an explicit `on` that cannot be honoured (% the resolved options).
+# The opt-in knobs of a handle, in the order they are resolved -- a knob may need the ones before it.  name: WideModel's argument and
+# attribute; env: where the wish comes from when the argument is not given; values: what it may be, values[0] the default; on: the
+# value that asks for something; flag: what `on` sets in NsrwConfig.flags; needs: what `on` takes of mlp and of the knobs before it;
+# refusal: NotImplementedError's words for an explicit `on` that cannot be honoured (% the resolved options).  The library states the
+# same dependencies for the flags (kFlagNeeds in csrc/nsr_wide.hip); tests/test_wide_options_host.py holds the two to each other.
 _Knob = collections.namedtuple("_Knob", "name env values on flag needs refusal")
 _ONCHIP = {"mlp": "f16x2", "trunk": "onchip"}
 KNOBS = (
@@ -206,14 +199,17 @@ KNOBS = (
     _Knob("trunk_keep", "NSR_WIDE_TRUNK_KEEP", TRUNK_KEEPS, "onchip", FLAG_TRUNK_KEEP, dict(_ONCHIP, trunk_bwd="onchip"),
           "trunk_keep=\"onchip\" leaves the relu masks as bits for the on-chip backward trunk: it needs mlp=\"f16x2\", "
           "trunk=\"onchip\" and trunk_bwd=\"onchip\" (got mlp=%(mlp)r, trunk=%(trunk)r, trunk_bwd=%(trunk_bwd)r)"),
+    _Knob("stages", "NSR_WIDE_STAGES", STAGES, "wave", FLAG_STAGES_WAVE, {}, ""),       # any arithmetic, any other knob: never refused
+    _Knob("trunk_rerun", "NSR_WIDE_TRUNK_RERUN", TRUNK_RERUNS, "onchip", FLAG_TRUNK_RERUN, _ONCHIP,
+          "trunk_rerun=\"onchip\" re-runs a pass of the on-chip trunk: it needs mlp=\"f16x2\" and "
+          "trunk=\"onchip\" (got mlp=%(mlp)r, trunk=%(trunk)r)"),
+    _Knob("embed", "NSR_WIDE_EMBED", EMBEDS, "onchip", FLAG_EMBED_ONCHIP, _ONCHIP,
+          "embed=\"onchip\" computes the encodings in the on-chip trunk's launch: it needs mlp=\"f16x2\" and trunk=\"onchip\" "
+          "(got mlp=%(mlp)r, trunk=%(trunk)r)"),
+    _Knob("rerun", "NSR_WIDE_RERUN", RERUNS, "rows", FLAG_RERUN_ROWS, {"mlp": "f16x2", "trunk": "layers"},
+          "rerun=\"rows\" re-runs the flagged rows of a per-layer f16x2 pass: it needs mlp=\"f16x2\" and "
+          "trunk=\"layers\" (got mlp=%(mlp)r, trunk=%(trunk)r)"),
 )
-
-
-# ... and the row of `embed`, resolved behind them by the same rule (resolve_embed).  It stands beside KNOBS, not in it: KNOBS is what
-# WideModel unpacks and _trunk_flags sums, and both keep their five.
-EMBED_KNOB = _Knob("embed", "NSR_WIDE_EMBED", EMBEDS, "onchip", _EMBED_ONCHIP, _ONCHIP,
-                   "embed=\"onchip\" computes the encodings in the on-chip trunk's launch: it needs mlp=\"f16x2\" and trunk=\"onchip\" "
-                   "(got mlp=%(mlp)r, trunk=%(trunk)r)")
 
 
 def resolve_knobs(mlp, wishes, environ):
@@ -221,20 +217,8 @@ def resolve_knobs(mlp, wishes, environ):
     environment's, else the default.  A value that is not one of the knob's raises ValueError.  The environment's wish is dropped where
     the handle cannot honour it (the drop-in API also builds bf16x3 / fp32 handles); an explicit one raises NotImplementedError.  Pure:
     no device, no library."""
-    got = _resolve_rows(KNOBS, {"mlp": mlp}, wishes, environ)
-    del got["mlp"]
-    return got
-
-
-def resolve_embed(wish, environ, mlp, trunk):
-    """Where a handle of arithmetic `mlp` with trunk=`trunk` computes the encodings of a pass that runs on chip: the caller's wish,
-    else $NSR_WIDE_EMBED, else "layers" -- EMBED_KNOB by the rule of resolve_knobs.  Pure: no device, no library."""
-    return _resolve_rows((EMBED_KNOB,), {"mlp": mlp, "trunk": trunk}, {"embed": wish}, environ)["embed"]
-
-
-def _resolve_rows(rows, got, wishes, environ):
-    """the rule of resolve_knobs over the _Knob rows `rows`, on top of what is resolved already (`got`, which it extends)"""
-    for k in rows:
+    got = {"mlp": mlp}
+    for k in KNOBS:
         v = wishes.get(k.name)
         number = not isinstance(k.on, str)
         from_env = v is None if number else not v               # (trunk_width=0 is a wish, and a bad one)
@@ -251,59 +235,23 @@ def _resolve_rows(rows, got, wishes, environ):
         if v == k.on and not can:
             raise NotImplementedError(k.refusal % got)
         got[k.name] = v
+    del got["mlp"]
     return got
 
 
-def _trunk_flags(trunk, trunk_width=128, heads="layers", trunk_bwd="layers", trunk_keep="layers"):
-    """the NsrwConfig.flags of the knobs (a trunk_width of 256 says nothing without trunk="onchip")"""
-    if trunk_width not in TRUNK_WIDTHS:
-        raise ValueError("trunk_width must be one of %s (got %r)" % (TRUNK_WIDTHS, trunk_width))
-    got = dict(trunk=trunk, heads=heads, trunk_width=trunk_width if trunk == "onchip" else 128, trunk_bwd=trunk_bwd,
-               trunk_keep=trunk_keep)
+def knob_flags(**values):
+    """the NsrwConfig.flags of the knobs `values` ({knob: value}; a knob not named is at its default): the flags of the rows whose
+    value is `on` (a trunk_width of 256 says nothing without trunk="onchip").  A value that is not one of its knob's raises
+    ValueError.  What goes together is resolve_knobs' to say, not this sum's."""
+    got = {k.name: values.pop(k.name, k.values[0]) for k in KNOBS}
+    if values:
+        raise TypeError("knob_flags: no such knob: %s" % ", ".join(sorted(values)))
+    for k in KNOBS:
+        if got[k.name] not in k.values:
+            raise ValueError("%s must be one of %s (got %r)" % (k.name, k.values, got[k.name]))
+    if got["trunk"] != "onchip":
+        got["trunk_width"] = TRUNK_WIDTHS[0]
     return sum(k.flag for k in KNOBS if got[k.name] == k.on)
-
-
-def resolve_stages(wish, environ):
-    """How a handle runs its per-ray stages: the caller's wish, else $NSR_WIDE_STAGES, else "threads".  Not an on-chip form -- any
-    arithmetic takes it and it needs no other knob -- so it is not a row of KNOBS.  Pure: no device, no library."""
-    v = wish or environ.get("NSR_WIDE_STAGES") or STAGES[0]
-    if v not in STAGES:
-        raise ValueError("stages must be one of %s (got %r)" % (STAGES, v))
-    return v
-
-
-def resolve_rerun(wish, environ, mlp, trunk):
-    """How a handle of arithmetic `mlp` with trunk=`trunk` runs the bf16x3 re-run of a forward pass whose trunk ran on chip: the
-    caller's wish, else $NSR_WIDE_TRUNK_RERUN, else "layers".  Resolved beside `stages`, not a row of KNOBS.  Only an f16x2 handle
-    with trunk="onchip" has such a re-run: the environment's wish is dropped elsewhere, an explicit "onchip" there raises
-    NotImplementedError.  Pure: no device, no library."""
-    v = wish or environ.get("NSR_WIDE_TRUNK_RERUN") or TRUNK_RERUNS[0]
-    if v not in TRUNK_RERUNS:
-        raise ValueError("trunk_rerun must be one of %s (got %r)" % (TRUNK_RERUNS, v))
-    can = mlp == "f16x2" and trunk == "onchip"
-    if not wish and not can:
-        v = TRUNK_RERUNS[0]
-    if v == "onchip" and not can:
-        raise NotImplementedError("trunk_rerun=\"onchip\" re-runs a pass of the on-chip trunk: it needs mlp=\"f16x2\" and "
-                                  "trunk=\"onchip\" (got mlp=%r, trunk=%r)" % (mlp, trunk))
-    return v
-
-
-def resolve_rerun_unit(wish, environ, mlp, trunk):
-    """The unit of the bf16x3 re-run on a handle of arithmetic `mlp` with trunk=`trunk`: the caller's wish, else $NSR_WIDE_RERUN, else
-    "pass".  Resolved beside `stages` / `trunk_rerun`, by their rule: only an f16x2 handle with trunk="layers" has the row-granular
-    form, so the environment's wish is dropped elsewhere and an explicit "rows" there raises NotImplementedError.  Pure: no device, no
-    library."""
-    v = wish or environ.get("NSR_WIDE_RERUN") or RERUNS[0]
-    if v not in RERUNS:
-        raise ValueError("rerun must be one of %s (got %r)" % (RERUNS, v))
-    can = mlp == "f16x2" and trunk == "layers"
-    if not wish and not can:
-        v = RERUNS[0]
-    if v == "rows" and not can:
-        raise NotImplementedError("rerun=\"rows\" re-runs the flagged rows of a per-layer f16x2 pass: it needs mlp=\"f16x2\" and "
-                                  "trunk=\"layers\" (got mlp=%r, trunk=%r)" % (mlp, trunk))
-    return v
 
 
 def rerun_rows_plan(words, M, tile_rows=256):
@@ -368,14 +316,15 @@ def trunk_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", trunk_width=128):
     lds_bytes) for the one-launch trunk of csrc/nsr_wide_trunk.inc (tile_rows = 64: its wide form), or dict(mode="layers",
     reason=...) for a GEMM launch per layer."""
     return _plan("nsrw_trunk_plan", NsrwTrunkPlan, ("nj", "tile_rows", "lds_bytes"), net_or_sd,
-                 _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width))
+                 _mlp_flags(mlp) | knob_flags(trunk=trunk, trunk_width=trunk_width))
 
 
 def heads_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", heads="onchip", trunk_width=128):
     """nsrw_heads_plan (diagnostic; no device, no handle): how a handle of arithmetic `mlp` created with trunk=`trunk`,
     heads=`heads`, trunk_width=`trunk_width` runs the heads of a network (an NsrwNet or a state dict) behind its pts_linears -- dict(mode="onchip",
     lds_bytes) for the heads form of the one-launch trunk, or dict(mode="layers", reason=...) for a GEMM launch per head."""
-    return _plan("nsrw_heads_plan", NsrwHeadsPlan, ("lds_bytes",), net_or_sd, _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width, heads))
+    return _plan("nsrw_heads_plan", NsrwHeadsPlan, ("lds_bytes",), net_or_sd,
+                 _mlp_flags(mlp) | knob_flags(trunk=trunk, trunk_width=trunk_width, heads=heads))
 
 
 def trunk_bwd_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", trunk_bwd="onchip", trunk_width=128):
@@ -384,7 +333,7 @@ def trunk_bwd_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", trunk_bwd="onchip
     gradient calls -- dict(mode="onchip", nj, tile_rows, lds_bytes) for the one-launch backward trunk of csrc/nsr_wide_trunk.inc, or
     dict(mode="layers", reason=...) for a GEMM launch per product."""
     return _plan("nsrw_trunk_bwd_plan", NsrwTrunkPlan, ("nj", "tile_rows", "lds_bytes"), net_or_sd,
-                 _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width, trunk_bwd=trunk_bwd))
+                 _mlp_flags(mlp) | knob_flags(trunk=trunk, trunk_width=trunk_width, trunk_bwd=trunk_bwd))
 
 
 def trunk_keep_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", trunk_bwd="onchip", trunk_keep="onchip", heads="layers", trunk_width=128):
@@ -393,7 +342,8 @@ def trunk_keep_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", trunk_bwd="onchi
     dict(mode="onchip", nj, tile_rows, lds_bytes) for the one kept launch of csrc/nsr_wide_trunk.inc (the relu masks as bits, read by
     the bit-reading backward launch), or dict(mode="layers", reason=...) for a GEMM launch per layer with fp32 activations kept."""
     return _plan("nsrw_trunk_keep_plan", NsrwTrunkPlan, ("nj", "tile_rows", "lds_bytes"), net_or_sd,
-                 _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width, heads, trunk_bwd, trunk_keep))
+                 _mlp_flags(mlp) | knob_flags(trunk=trunk, trunk_width=trunk_width, heads=heads, trunk_bwd=trunk_bwd,
+                                              trunk_keep=trunk_keep))
 
 
 def trunk_rerun_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", trunk_rerun="onchip", trunk_width=128):
@@ -402,10 +352,8 @@ def trunk_rerun_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", trunk_rerun="on
     keeps no activations, on a network (an NsrwNet or a state dict) -- dict(mode="onchip", nj, tile_rows, lds_bytes) for the one
     launch of kw_rerun_b3 (csrc/nsr_wide_trunk.inc; tile_rows = 128 up to a padded width of 64, 64 for 96 and 128), or
     dict(mode="layers", reason=...) for a conditional GEMM launch per layer."""
-    if trunk_rerun not in TRUNK_RERUNS:
-        raise ValueError("trunk_rerun must be one of %s (got %r)" % (TRUNK_RERUNS, trunk_rerun))
     return _plan("nsrw_trunk_rerun_plan", NsrwTrunkPlan, ("nj", "tile_rows", "lds_bytes"), net_or_sd,
-                 _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width) | (FLAG_TRUNK_RERUN if trunk_rerun == "onchip" else 0))
+                 _mlp_flags(mlp) | knob_flags(trunk=trunk, trunk_width=trunk_width, trunk_rerun=trunk_rerun))
 
 
 def embed_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", heads="layers", trunk_width=128, trunk_bwd="layers", trunk_keep="layers",
@@ -414,11 +362,10 @@ def embed_plan(net_or_sd, mlp=DEFAULT_MLP, trunk="onchip", heads="layers", trunk
     encodings of a pass of a network (an NsrwNet or a state dict) -- kept: a pass that keeps its activations for a backward -- as
     dict(positions=..., directions=...), each dict(mode="onchip") for "in the pass's one f16x2 launch" or dict(mode="layers",
     reason=...) for the kw_embed launch."""
-    if embed not in EMBEDS:
-        raise ValueError("embed must be one of %s (got %r)" % (EMBEDS, embed))
+    flags = _mlp_flags(mlp) | knob_flags(trunk=trunk, trunk_width=trunk_width, heads=heads, trunk_bwd=trunk_bwd, trunk_keep=trunk_keep,
+                                         embed=embed)
     lib = load()
     net = net_or_sd if isinstance(net_or_sd, NsrwNet) else describe(net_or_sd)[0]
-    flags = _mlp_flags(mlp) | _trunk_flags(trunk, trunk_width, heads, trunk_bwd, trunk_keep) | (_EMBED_ONCHIP if embed == "onchip" else 0)
     plan = NsrwEmbedPlan()
     if lib.nsrw_embed_plan(C.byref(net), flags, 1 if kept else 0, C.byref(plan)) != 0:
         raise _lib.NsrError(lib.nsrw_last_error().decode("utf-8", "replace"))
@@ -599,13 +546,10 @@ class WideModel:
         mlp = mlp or os.environ.get("NSR_WIDE_MLP") or DEFAULT_MLP
         if mlp not in MLPS:
             raise ValueError("mlp must be one of %s (got %r)" % (MLPS, mlp))
-        knobs = resolve_knobs(mlp, dict(trunk=trunk, heads=heads, trunk_width=trunk_width, trunk_bwd=trunk_bwd, trunk_keep=trunk_keep),
-                              os.environ)
-        self.trunk, self.heads, self.trunk_width, self.trunk_bwd, self.trunk_keep = (knobs[k.name] for k in KNOBS)
-        self.stages = resolve_stages(stages, os.environ)
-        self.trunk_rerun = resolve_rerun(trunk_rerun, os.environ, mlp, self.trunk)
-        self.embed = resolve_embed(embed, os.environ, mlp, self.trunk)
-        self.rerun = resolve_rerun_unit(rerun, os.environ, mlp, self.trunk)
+        knobs = resolve_knobs(mlp, dict(trunk=trunk, heads=heads, trunk_width=trunk_width, trunk_bwd=trunk_bwd, trunk_keep=trunk_keep,
+                                        stages=stages, trunk_rerun=trunk_rerun, embed=embed, rerun=rerun), os.environ)
+        for k in KNOBS:
+            setattr(self, k.name, knobs[k.name])
         self.mlp = "layered-" + mlp
         if not torch.cuda.is_available():
             raise _lib.NsrError("no HIP device visible: the render path has no CPU fallback")
@@ -628,11 +572,7 @@ class WideModel:
         self._ws_need = {}                                # (rays, grad) -> bytes one chunk of that many rays needs
         cfg = NsrwConfig(self.device.index, n_samples, n_importance,
                          (FLAG_WHITE_BKGD if white_bkgd else 0) | (FLAG_LINDISP if lindisp else 0) |
-                         _mlp_flags(mlp) | _trunk_flags(self.trunk, self.trunk_width, self.heads, self.trunk_bwd, self.trunk_keep) |
-                         (FLAG_STAGES_WAVE if self.stages == "wave" else 0) |
-                         (FLAG_TRUNK_RERUN if self.trunk_rerun == "onchip" else 0) |
-                         (_EMBED_ONCHIP if self.embed == "onchip" else 0) |
-                         (_RERUN_ROWS if self.rerun == "rows" else 0))
+                         _mlp_flags(mlp) | knob_flags(**knobs))
         h = C.c_void_p()
         check(self.lib.nsrw_create(C.byref(cfg), C.byref(h)))
         self.h = h

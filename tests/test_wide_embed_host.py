@@ -88,33 +88,6 @@ def test_embed_plan_reads_state_dicts_and_refuses_bad_arguments(wide, oracle):
         wide.embed_plan(_net(wide, 3, 1))
 
 
-def test_the_knob_resolves_from_a_wish_and_from_the_environment():
-    """resolve_embed is pure: no device, no library.  The environment's wish is dropped where the handle cannot honour it, an explicit
-    one raises NotImplementedError naming what is missing, a value that is not one of the knob's raises ValueError."""
-    from neural_sim_nerf_amd import wide
-    env = {"NSR_WIDE_EMBED": "onchip"}
-    assert wide.EMBEDS == ("layers", "onchip") and wide.FLAG_EMBED_ONCHIP == 1 << 11
-    assert wide.resolve_embed(None, {}, "f16x2", "onchip") == "layers"
-    assert wide.resolve_embed(None, env, "f16x2", "onchip") == "onchip"
-    assert wide.resolve_embed("layers", env, "f16x2", "onchip") == "layers"
-    assert wide.resolve_embed("onchip", {}, "f16x2", "onchip") == "onchip"
-    for mlp, trunk in (("bf16x3", "layers"), ("fp32", "layers"), ("f16x2", "layers")):
-        assert wide.resolve_embed(None, env, mlp, trunk) == "layers", (mlp, trunk)
-        with pytest.raises(NotImplementedError, match="embed=\"onchip\".*mlp=%r, trunk=%r" % (mlp, trunk)):
-            wide.resolve_embed("onchip", {}, mlp, trunk)
-    for bad in ("lds", "on", 1):
-        with pytest.raises(ValueError, match="embed must be one of"):
-            wide.resolve_embed(bad, {}, "f16x2", "onchip")
-    with pytest.raises(ValueError, match="embed must be one of"):
-        wide.resolve_embed(None, {"NSR_WIDE_EMBED": "chip"}, "f16x2", "onchip")
-    # a _Knob row like the five of KNOBS, resolved by their rule, beside them: what WideModel unpacks and _trunk_flags sums is unchanged
-    row = wide.EMBED_KNOB
-    assert (row.name, row.env, row.values, row.on, row.flag) == ("embed", "NSR_WIDE_EMBED", wide.EMBEDS, "onchip", wide.FLAG_EMBED_ONCHIP)
-    assert row.needs == {"mlp": "f16x2", "trunk": "onchip"} and row not in wide.KNOBS
-    assert not any(k.flag & wide.FLAG_EMBED_ONCHIP for k in wide.KNOBS)
-    assert "embed" not in wide.resolve_knobs("f16x2", {}, env)
-
-
 def test_the_interface_is_declared_and_exported(wide):
     hdr = open(os.path.join(ROOT, "include", "nsr_wide.h")).read()
     assert re.search(r"NSRW_FLAG_EMBED_ONCHIP = \(1 << 11\)", hdr)
@@ -128,6 +101,5 @@ def test_the_interface_is_declared_and_exported(wide):
     assert lib.nsrw_embed_status(None, ctypes.byref(a), ctypes.byref(a), ctypes.byref(a)) != 0
     assert b"nsrw_embed_status: null argument" in lib.nsrw_last_error()
     # the drop-in API builds its handles without the argument: the environment decides, as for the other options
-    src = open(os.path.join(ROOT, "neural_sim_nerf_amd", "wide.py")).read()
-    assert "resolve_embed(embed, os.environ, mlp, self.trunk)" in src
+    assert wide.resolve_knobs("f16x2", {"trunk": "onchip"}, {"NSR_WIDE_EMBED": "onchip"})["embed"] == "onchip"
     assert "NSR_WIDE_EMBED" in open(os.path.join(ROOT, "INTEGRATION.md")).read()

@@ -32,56 +32,16 @@ def words_of(rows, n_words):
     return w
 
 
-def test_resolve_rerun_unit():
-    """pure: no device, no library.  The values and the default; the environment's wish is dropped on bf16x3 / fp32 handles and under
-    trunk="onchip", an explicit one there raises with the resolved options in the message; an unknown value raises ValueError."""
-    from neural_sim_nerf_amd import wide
-    env = {"NSR_WIDE_RERUN": "rows"}
-    assert wide.RERUNS == ("pass", "rows")
-    assert wide.resolve_rerun_unit(None, {}, "f16x2", "layers") == "pass"
-    assert wide.resolve_rerun_unit("rows", {}, "f16x2", "layers") == "rows"
-    assert wide.resolve_rerun_unit(None, env, "f16x2", "layers") == "rows"
-    assert wide.resolve_rerun_unit("", env, "f16x2", "layers") == "rows"
-    assert wide.resolve_rerun_unit("pass", env, "f16x2", "layers") == "pass"
-    for mlp, trunk in (("bf16x3", "layers"), ("fp32", "layers"), ("f16x2", "onchip"), ("bf16x3", "onchip")):
-        assert wide.resolve_rerun_unit(None, env, mlp, trunk) == "pass", (mlp, trunk)
-        assert wide.resolve_rerun_unit("pass", env, mlp, trunk) == "pass", (mlp, trunk)
-        with pytest.raises(NotImplementedError, match="rerun=\"rows\".*mlp=%r, trunk=%r" % (mlp, trunk)):
-            wide.resolve_rerun_unit("rows", {}, mlp, trunk)
-    for bad in ("row", "chunk", 1):
-        with pytest.raises(ValueError, match="rerun must be"):
-            wide.resolve_rerun_unit(bad, {}, "f16x2", "layers")
-    for mlp, trunk in (("f16x2", "layers"), ("bf16x3", "layers")):
-        with pytest.raises(ValueError, match="rerun must be"):
-            wide.resolve_rerun_unit(None, {"NSR_WIDE_RERUN": "row"}, mlp, trunk)
-    # (the arguments are judged before a device is asked for; stages="wave" combines freely)
-    with pytest.raises(ValueError, match="rerun must be"):
-        wide.WideModel(None, None, n_samples=3, n_importance=0, mlp="f16x2", rerun="row")
-    with pytest.raises(NotImplementedError, match="rerun=\"rows\".*mlp='f16x2', trunk='onchip'"):
-        wide.WideModel(None, None, n_samples=3, n_importance=0, mlp="f16x2", trunk="onchip", rerun="rows")
-    with pytest.raises(NotImplementedError, match="rerun=\"rows\".*mlp='bf16x3', trunk='layers'"):
-        wide.WideModel(None, None, n_samples=3, n_importance=0, mlp="bf16x3", rerun="rows", stages="wave")
-    with pytest.raises(NotImplementedError, match="rerun=\"rows\".*mlp='fp32'"):
-        wide.WideModel(None, None, n_samples=3, n_importance=0, mlp="fp32", rerun="rows")
-    # not a row of KNOBS: _trunk_flags keeps its values
-    assert [k.name for k in wide.KNOBS] == ["trunk", "heads", "trunk_width", "trunk_bwd", "trunk_keep"]
-
-
 def test_flag_and_signatures_are_declared(wide):
     hdr = open(os.path.join(ROOT, "include", "nsr_wide.h")).read()
     assert re.search(r"enum\s*\{\s*NSRW_FLAG_RERUN_ROWS\s*=\s*\(?\s*1 << 12\s*\)?\s*\}", hdr) and wide.FLAG_RERUN_ROWS == 4096 == 1 << 12
     assert "int nsrw_range_rows_status(nsrw_handle h, unsigned long long* rows, unsigned long long* rows_rerun);" in hdr
     assert "int nsrw_rerun_rows_plan(const uint32_t* words, int64_t n_words, int64_t M, int tile_rows, int32_t* list_out, int64_t max);" in hdr
     assert {"nsrw_range_rows_status", "nsrw_rerun_rows_plan"} <= set(wide.SIGNATURES)
-    # the bit collides with no other flag, of the module's globals or behind __getattr__, and the census of
-    # test_wide_trunk_rerun_host.py (ten FLAG_* globals beside FLAG_TRUNK_RERUN) still holds
-    flags = {k: v for k, v in vars(wide).items() if k.startswith("FLAG_")}
-    assert len(flags) == 11 and "FLAG_RERUN_ROWS" not in flags
-    flags["FLAG_EMBED_ONCHIP"] = wide.FLAG_EMBED_ONCHIP
-    assert not any(v & 4096 for v in flags.values()), flags
+    # the bit collides with no other flag of the module (tests/test_wide_options_host.py takes the census of all thirteen)
+    flags = {k: v for k, v in vars(wide).items() if k.startswith("FLAG_") and k != "FLAG_RERUN_ROWS"}
+    assert len(flags) == 12 and not any(v & 4096 for v in flags.values()), flags
     assert sorted(flags.values()) == [1 << i for i in range(12)]
-    with pytest.raises(AttributeError):
-        wide.FLAG_RERUN_ROW
     n = wide.C.c_ulonglong(7)
     lib = wide.load()
     assert lib.nsrw_range_rows_status(None, wide.C.byref(n), wide.C.byref(n)) != 0 and "null" in lib.nsrw_last_error().decode()

@@ -51,31 +51,6 @@ def test_header_and_module_state_the_option():
     assert len(others) == 9 and not any(v & 512 for v in others), others
 
 
-def test_resolve_stages():
-    from neural_sim_nerf_amd import wide
-    assert wide.resolve_stages(None, {}) == "threads"
-    assert wide.resolve_stages(None, {"NSR_WIDE_STAGES": "wave"}) == "wave"
-    assert wide.resolve_stages(None, {"NSR_WIDE_STAGES": ""}) == "threads"
-    assert wide.resolve_stages("threads", {"NSR_WIDE_STAGES": "wave"}) == "threads"       # the argument beats the environment
-    assert wide.resolve_stages("wave", {"NSR_WIDE_STAGES": "threads"}) == "wave"
-    assert wide.resolve_stages("wave", {}) == "wave"
-    for wish, env in (("waves", {}), (None, {"NSR_WIDE_STAGES": "onchip"}), ("onchip", {"NSR_WIDE_STAGES": "wave"}), (1, {})):
-        with pytest.raises(ValueError, match="stages must be one of"):
-            wide.resolve_stages(wish, env)
-    # a bad wish is refused before a device is asked for (this test runs without one)
-    with pytest.raises(ValueError, match="stages must be one of"):
-        wide.WideModel(None, None, n_samples=3, n_importance=0, stages="waves")
-
-
-def test_the_onchip_knobs_are_what_they_were():
-    """the new option is not a row of KNOBS: WideModel.__init__ unpacks five"""
-    from neural_sim_nerf_amd import wide
-    assert len(wide.KNOBS) == 5 and [k.name for k in wide.KNOBS] == ["trunk", "heads", "trunk_width", "trunk_bwd", "trunk_keep"]
-    assert wide._trunk_flags("onchip", trunk_bwd="onchip", trunk_keep="onchip") == 16 | 128 | 256
-    assert not any(k.flag & wide.FLAG_STAGES_WAVE for k in wide.KNOBS)
-    assert "stages" not in wide.resolve_knobs("f16x2", {}, {"NSR_WIDE_STAGES": "wave"})
-
-
 @pytest.mark.parametrize("stage,samples,ni", list(cases()))
 def test_stage_plan_is_the_stated_rule(stage, samples, ni):
     from neural_sim_nerf_amd import wide

@@ -120,38 +120,6 @@ def test_the_plans_lds_bytes_are_those_of_the_kernels_they_select(wide):
         assert res[k]["vgpr_spill_count"] == 0 and res[k]["private_segment_fixed_size"] == 0, (k, res[k])
 
 
-def test_knob_resolution():
-    """resolve_knobs is pure: no device, no library.  The environment's wish is dropped where trunk_bwd is not on chip, an explicit
-    one raises, a value that is not one of the knob's raises ValueError."""
-    from neural_sim_nerf_amd import wide
-    env = {"NSR_WIDE_TRUNK_KEEP": "onchip"}
-    full = dict(trunk="onchip", heads=None, trunk_width=None, trunk_bwd="onchip", trunk_keep=None)
-    assert wide.resolve_knobs("f16x2", full, env)["trunk_keep"] == "onchip"
-    assert wide.resolve_knobs("f16x2", full, {})["trunk_keep"] == "layers"
-    assert wide.resolve_knobs("f16x2", dict(full, trunk_keep="layers"), env)["trunk_keep"] == "layers"
-    assert wide.resolve_knobs("f16x2", dict(full, trunk_keep="onchip"), {}) == \
-        dict(trunk="onchip", heads="layers", trunk_width=128, trunk_bwd="onchip", trunk_keep="onchip")
-    for mlp, wishes in (("f16x2", dict(full, trunk_bwd=None)), ("f16x2", dict(full, trunk_bwd="layers")),
-                        ("f16x2", dict(full, trunk=None, trunk_bwd=None)), ("bf16x3", dict.fromkeys(full)), ("fp32", dict.fromkeys(full))):
-        assert wide.resolve_knobs(mlp, wishes, env)["trunk_keep"] == "layers", (mlp, wishes)
-        with pytest.raises(NotImplementedError, match="trunk_keep"):
-            wide.resolve_knobs(mlp, dict(wishes, trunk_keep="onchip"), {})
-    assert wide.resolve_knobs("f16x2", dict(full, trunk_bwd=None), dict(env, NSR_WIDE_TRUNK_BWD="onchip"))["trunk_keep"] == "onchip"
-    for bad in ("bits", "on", 1):
-        with pytest.raises(ValueError, match="trunk_keep must be"):
-            wide.resolve_knobs("f16x2", dict(full, trunk_keep=bad), {})
-    with pytest.raises(ValueError, match="trunk_keep must be"):
-        wide.resolve_knobs("f16x2", full, {"NSR_WIDE_TRUNK_KEEP": "bits"})
-    row = wide.KNOBS[-1]
-    assert (row.name, row.env, row.values, row.on, row.flag) == ("trunk_keep", "NSR_WIDE_TRUNK_KEEP", ("layers", "onchip"), "onchip", 256)
-    assert row.needs == dict(mlp="f16x2", trunk="onchip", trunk_bwd="onchip")
-    f = wide._trunk_flags
-    assert f("onchip", trunk_bwd="onchip", trunk_keep="onchip") == 16 | 128 | 256 and f("onchip", trunk_bwd="onchip") == 16 | 128
-    # (the arguments are judged before a device is asked for)
-    with pytest.raises(NotImplementedError, match="trunk_keep=\"onchip\""):
-        wide.WideModel(None, None, n_samples=3, n_importance=0, mlp="f16x2", trunk="onchip", trunk_bwd="layers", trunk_keep="onchip")
-
-
 def test_flag_and_signatures_are_declared(wide):
     hdr = open(os.path.join(ROOT, "include", "nsr_wide.h")).read()
     assert "NSRW_FLAG_TRUNK_KEEP = 256" in hdr and wide.FLAG_TRUNK_KEEP == 256

@@ -161,39 +161,6 @@ def test_the_plans_lds_bytes_are_those_of_the_kernels_they_select(wide):
         assert res[k]["vgpr_count"] <= 256 and res[k]["vgpr_spill_count"] == 0 and res[k]["private_segment_fixed_size"] == 0, (k, res[k])
 
 
-def test_resolve_rerun():
-    """resolve_rerun is pure: no device, no library.  The environment's wish is dropped on a handle that is not f16x2 with
-    trunk="onchip", an explicit one there raises, a value that is not one of the option's raises ValueError."""
-    from neural_sim_nerf_amd import wide
-    env = {"NSR_WIDE_TRUNK_RERUN": "onchip"}
-    assert wide.resolve_rerun(None, {}, "f16x2", "onchip") == "layers"
-    assert wide.resolve_rerun("onchip", {}, "f16x2", "onchip") == "onchip"
-    assert wide.resolve_rerun(None, env, "f16x2", "onchip") == "onchip"
-    assert wide.resolve_rerun("layers", env, "f16x2", "onchip") == "layers"
-    assert wide.resolve_rerun("", env, "f16x2", "onchip") == "onchip"
-    for mlp, trunk in (("f16x2", "layers"), ("bf16x3", "layers"), ("fp32", "layers"), ("bf16x3", "onchip")):
-        assert wide.resolve_rerun(None, env, mlp, trunk) == "layers", (mlp, trunk)
-        assert wide.resolve_rerun("layers", env, mlp, trunk) == "layers", (mlp, trunk)
-        with pytest.raises(NotImplementedError, match="trunk_rerun=\"onchip\".*mlp=%r, trunk=%r" % (mlp, trunk)):
-            wide.resolve_rerun("onchip", {}, mlp, trunk)
-    for bad in ("lds", "on", 1):
-        with pytest.raises(ValueError, match="trunk_rerun must be"):
-            wide.resolve_rerun(bad, {}, "f16x2", "onchip")
-    for mlp, trunk in (("f16x2", "onchip"), ("bf16x3", "layers")):
-        with pytest.raises(ValueError, match="trunk_rerun must be"):
-            wide.resolve_rerun(None, {"NSR_WIDE_TRUNK_RERUN": "lds"}, mlp, trunk)
-    # not a row of KNOBS: _trunk_flags keeps its values, the option's bit is added beside it
-    assert [k.name for k in wide.KNOBS] == ["trunk", "heads", "trunk_width", "trunk_bwd", "trunk_keep"]
-    assert wide._trunk_flags("onchip", trunk_bwd="onchip", trunk_keep="onchip") == 16 | 128 | 256
-    # (the arguments are judged before a device is asked for)
-    with pytest.raises(ValueError, match="trunk_rerun must be"):
-        wide.WideModel(None, None, n_samples=3, n_importance=0, mlp="f16x2", trunk="onchip", trunk_rerun="lds")
-    with pytest.raises(NotImplementedError, match="trunk_rerun=\"onchip\""):
-        wide.WideModel(None, None, n_samples=3, n_importance=0, mlp="f16x2", trunk="layers", trunk_rerun="onchip")
-    with pytest.raises(NotImplementedError, match="trunk_rerun=\"onchip\""):
-        wide.WideModel(None, None, n_samples=3, n_importance=0, mlp="bf16x3", trunk_rerun="onchip")
-
-
 def test_flag_and_signatures_are_declared(wide):
     hdr = open(os.path.join(ROOT, "include", "nsr_wide.h")).read()
     assert re.search(r"enum\s*\{\s*NSRW_FLAG_TRUNK_RERUN\s*=\s*\(?\s*1 << 10\s*\)?\s*\}", hdr) and wide.FLAG_TRUNK_RERUN == 1024 == 1 << 10
@@ -203,7 +170,7 @@ def test_flag_and_signatures_are_declared(wide):
     assert {"nsrw_trunk_rerun_plan", "nsrw_rerun_status"} <= set(wide.SIGNATURES) and wide.TRUNK_RERUNS == ("layers", "onchip")
     # the bit is free: no other flag of the module has it
     flags = {k: v for k, v in vars(wide).items() if k.startswith("FLAG_") and k != "FLAG_TRUNK_RERUN"}
-    assert len(flags) == 10 and not any(v & 1024 for v in flags.values()), flags
+    assert len(flags) == 12 and not any(v & 1024 for v in flags.values()), flags
     lib, C = wide.load(), wide.C
     plan = wide.NsrwTrunkPlan()
     net = _net(wide, 3, 100, 10, [0])

@@ -5,8 +5,11 @@ quoted against; for those the issued fraction of the fp16 / bf16 peak is reporte
 
     python tools/bench_wide.py [--hw 400] [--cases ycbv,w512,d10w384,small] [--steps 3] [--trunk layers|onchip|both]
                                   [--heads layers|onchip|both] [--trunk-width 128|256|both] [--trunk-bwd layers|onchip|both]
-                                  [--trunk-keep layers|onchip|both] [--trunk-rerun layers|onchip|both] [--embed layers|onchip|both]
-                                  [--stages threads|wave|both] [--cotangents rgb|all]
+                                  [--trunk-keep layers|onchip|both] [--stages threads|wave|both] [--trunk-rerun layers|onchip|both]
+                                  [--embed layers|onchip|both] [--rerun pass|rows|both] [--cotangents rgb|all]
+
+One argument per row of wide.KNOBS: a value of the option, or `both` for each in turn on the same rays in one process.  The table also
+says which combinations a handle takes; the others are not run.
 
 --trunk (f16x2): the pts_linears layer by layer (the default), in the one-launch on-chip trunk (csrc/nsr_wide_trunk.inc), or both in
 turn on the same rays in one process -- the comparison DESIGN.md 8 quotes.  --heads (with the on-chip trunk): the heads one launch
@@ -19,10 +22,12 @@ with fp32 activations kept (the default), in the one kept launch that leaves the
 pts_linears in the one launch of kw_rerun_b3, or both in turn (d8w128range: a network whose every coarse pass is re-run).  --embed (with the on-chip trunk): the encodings of a pass
 written by the kw_embed launch and read back (the default), computed inside the pass's on-chip launch, or both in turn.  --stages (any
 arithmetic): compositing, resampling and the compositing backward one thread per ray (the default), one wave per ray
-(csrc/nsr_wide_stages.inc), or both in turn on the same rays in one process.  --cotangents: the gradient call differentiates rgb_map
+(csrc/nsr_wide_stages.inc), or both in turn on the same rays in one process.  --rerun (f16x2 with the per-layer trunk): the bf16x3
+re-run of a pass that left fp16's range over the whole chunk (the default), over the flagged rows alone, or both in turn.  --cotangents: the gradient call differentiates rgb_map
 (the default) or all six outputs (the coarse pass's backward too).
 """
 import argparse
+import itertools
 import json
 import os
 import sys
@@ -32,7 +37,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from neural_sim_nerf_amd import synthetic as S  # noqa: E402
-from neural_sim_nerf_amd.wide import WideModel  # noqa: E402
+from neural_sim_nerf_amd import wide  # noqa: E402
 from bench import PowerSampler  # noqa: E402  (hwmon power / clock of the GPU while the launches run)
 
 PEAK_FP32_MFMA = 157.3
@@ -58,6 +63,9 @@ CASES = {
     "d8w128range": (8, 128, 10, 4, [4], 64, 128),
 }
 RANGE_CASES = ("d8w128range",)       # the coarse network's pts_linears.1 sends hidden unit 5 to 7e4 on every point
+# how an option that ran both ways names itself in a result's key, in the key's order
+KEY_PARTS = (("trunk", ":%s"), ("heads", ":heads-%s"), ("trunk_width", ":width-%d"), ("trunk_bwd", ":bwd-%s"), ("trunk_keep", ":keep-%s"),
+             ("trunk_rerun", ":rerun-%s"), ("embed", ":embed-%s"), ("stages", ":stages-%s"), ("rerun", ":unit-%s"))
 
 
 def net_sd(D, W, L, Lv, skips, seed):
@@ -92,46 +100,37 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--no-grad", action="store_true")
     ap.add_argument("--mlp", default=None, help="bf16x3 | fp32 | f16x2 (default: the library's)")
-    ap.add_argument("--trunk", default="layers", choices=("layers", "onchip", "both"))
-    ap.add_argument("--heads", default="layers", choices=("layers", "onchip", "both"))
-    ap.add_argument("--trunk-width", default="128", choices=("128", "256", "both"))
-    ap.add_argument("--trunk-bwd", default="layers", choices=("layers", "onchip", "both"))
-    ap.add_argument("--trunk-keep", default="layers", choices=("layers", "onchip", "both"))
-    ap.add_argument("--trunk-rerun", default="layers", choices=("layers", "onchip", "both"))
-    ap.add_argument("--embed", default="layers", choices=("layers", "onchip", "both"))
-    ap.add_argument("--stages", default="threads", choices=("threads", "wave", "both"))
+    for k in wide.KNOBS:              # --trunk ... --rerun: one value of the option, or both in turn
+        ap.add_argument("--" + k.name.replace("_", "-"), default=str(k.values[0]), choices=tuple(str(v) for v in k.values) + ("both",))
     ap.add_argument("--cotangents", default="rgb", choices=("rgb", "all"))
     a = ap.parse_args()
-    trunks = ("layers", "onchip") if a.trunk == "both" else (a.trunk,)
-    widths = (128, 256) if a.trunk_width == "both" else (int(a.trunk_width),)
-    bwds = ("layers", "onchip") if a.trunk_bwd == "both" else (a.trunk_bwd,)
-    keeps = ("layers", "onchip") if a.trunk_keep == "both" else (a.trunk_keep,)
-    reruns = ("layers", "onchip") if a.trunk_rerun == "both" else (a.trunk_rerun,)
-    embeds = ("layers", "onchip") if a.embed == "both" else (a.embed,)
-    stages_modes = ("threads", "wave") if a.stages == "both" else (a.stages,)
-    # (trunk, heads, trunk width, backward trunk, kept forward): the heads and the backward trunk run on chip, and the trunk takes
-    # widths up to 256, behind the on-chip trunk only; the kept forward runs on chip behind the on-chip backward trunk only; the
-    # re-run runs on chip behind the on-chip trunk only
-    modes = [(t, h, w, b, k, s, r, e) for t in trunks for h in (("layers", "onchip") if a.heads == "both" else (a.heads,)) for w in widths
-             for b in bwds for k in keeps for s in stages_modes for r in reruns for e in embeds
-             if (t == "onchip" or (h == "layers" and w == widths[0] and b == "layers" and r == "layers" and e == "layers")) and
-             (b == "onchip" or k == "layers")]
-    if not modes or (a.trunk == "layers" and a.trunk_width != "128"):
-        ap.error("--heads onchip, --trunk-width 256, --trunk-bwd onchip, --trunk-rerun onchip and --embed onchip need --trunk onchip or both; "
-                 "--trunk-keep onchip needs --trunk-bwd onchip or both")
+    # the modes: every combination of the values asked for that a handle of this arithmetic takes (wide.KNOBS says which), in the
+    # table's order -- so two modes never differ in an option the handle could not honour
+    mlp = a.mlp or os.environ.get("NSR_WIDE_MLP") or wide.DEFAULT_MLP
+    both = {k.name: getattr(a, k.name) == "both" for k in wide.KNOBS}
+    asked = [k.values if both[k.name] else tuple(v for v in k.values if str(v) == getattr(a, k.name)) for k in wide.KNOBS]
+    modes, refusal = [], None
+    for values in itertools.product(*asked):
+        mode = dict(zip((k.name for k in wide.KNOBS), values))
+        try:
+            wide.resolve_knobs(mlp, mode, {})
+            modes.append(mode)
+        except NotImplementedError as e:
+            refusal = refusal or str(e)
+    if not modes:
+        ap.error(refusal)
     K = S.scaled_K(400.0 / a.hw)
     pose = S.sweep_poses(1, seed=0)[0]
     out = {}
-    for name, trunk, heads, width, bwd, keep, stages, rerun, embed in [(c,) + mode for c in a.cases.split(",") for mode in modes]:
+    rows = {k.name: k for k in wide.KNOBS}
+    for name, mode in [(c, mode) for c in a.cases.split(",") for mode in modes]:
         D, W, L, Lv, skips, ns, ni = CASES[name]
         sd = net_sd(D, W, L, Lv, skips, 1)
         sd_c = sd
         if name in RANGE_CASES:
             sd_c = {k: v.copy() for k, v in sd.items()}
             sd_c["pts_linears.1.bias"][5] += 7.0e4
-        m = WideModel(sd_c, sd, n_samples=ns, n_importance=ni, mlp=a.mlp, trunk=trunk, heads=heads,
-                      trunk_width=width if trunk == "onchip" else None, trunk_bwd=bwd, trunk_keep=keep, stages=stages,
-                      trunk_rerun=rerun, embed=embed)
+        m = wide.WideModel(sd_c, sd, n_samples=ns, n_importance=ni, mlp=mlp, **mode)
         n = a.hw * a.hw
         evals = n * (ns + ns + ni)
         flop = evals * flop_per_point(sd)
@@ -147,7 +146,7 @@ def main():
         res = {"network": "%d x %d, skips %s, %d + %d samples" % (D, W, skips, ns, ni), "rays": n,
                "flop_per_point": flop_per_point(sd), "mlp": m.mlp, "trunk": m.trunk, "heads": m.heads,
                "trunk_width": m.trunk_width, "trunk_bwd": m.trunk_bwd, "trunk_keep": m.trunk_keep, "trunk_rerun": m.trunk_rerun,
-               "embed": m.embed, "stages": m.stages,
+               "embed": m.embed, "stages": m.stages, "rerun": m.rerun,
                "cotangents": a.cotangents}
         for what in ("forward",) + (() if a.no_grad else ("forward+input-gradient",)):
             ms = []
@@ -184,13 +183,9 @@ def main():
             res["keep_status"] = m.keep_status()
             res["rerun_status"] = m.rerun_status()
             res["embed_status"] = m.embed_status()
-        key = name + (":" + trunk if a.trunk == "both" else "") + (":heads-" + heads if a.heads == "both" else "") + \
-            (":width-%d" % width if a.trunk_width == "both" and trunk == "onchip" else "") + \
-            (":bwd-" + bwd if a.trunk_bwd == "both" and trunk == "onchip" else "") + \
-            (":keep-" + keep if a.trunk_keep == "both" and bwd == "onchip" else "") + \
-            (":rerun-" + rerun if a.trunk_rerun == "both" and trunk == "onchip" else "") + \
-            (":embed-" + embed if a.embed == "both" and trunk == "onchip" else "") + \
-            (":stages-" + stages if a.stages == "both" else "")
+        # an option that ran both ways names itself in the key where the mode lets it be on (heads: in every mode)
+        key = name + "".join(part % mode[n] for n, part in KEY_PARTS if both[n] and
+                             (n == "heads" or all(mode[o] == need for o, need in rows[n].needs.items() if o != "mlp")))
         out[key] = res
         print(key, json.dumps(res), flush=True)
         m.close()
