@@ -347,8 +347,12 @@ __device__ __forceinline__ uint4 relu_mask(const f32x16 (&acc)[NMO]) {
 // VALU instruction is never free here: it takes matrix-pipe issue time from the other wave on the SIMD
 // (tools/probe_pairing.py).  So: one fp64 reduction -- t = a*(2/pi) has >= 24 spare bits for |a| < 2^24, and
 // the split into quadrant n and fraction f is exact -- then the Cephes single-precision minimax polynomials on
-// [-pi/4, pi/4] (1 ulp).  ~20 instructions.  Domain: |a| < 2^24; enc_domain() turns coordinates beyond it into
-// NaN so that an out-of-range scene shows up as NaN pixels rather than as slightly wrong ones.
+// [-pi/4, pi/4] (1 ulp of their own value).  ~20 instructions.  Domain: |a| < 2^24; enc_domain() turns coordinates
+// beyond it into NaN so that an out-of-range scene shows up as NaN pixels rather than as slightly wrong ones.
+// What holds of the RESULT: within 2 ulp of the true value plus |a| 2^-52 -- the reduction's product and constant
+// round at 2^-53 each, which leaves |a| 2^-52 radians, absolute: nothing against 1, but thousands of ulp of a
+// result near a zero of sin / cos at large |a| (the same lines and the same bound as sincos_enc of nsr_wide.hip;
+// tests/test_gpu_wide_encodings.py holds both to it element by element).
 __device__ __forceinline__ float enc_trig(float a, int k) {
   const double kMagic = 6755399441055744.0;                 // 1.5 * 2^52: t + kMagic holds rint(t) in its low word
   const double t = (double)a * 0.63661977236758134308;      // a * 2/pi

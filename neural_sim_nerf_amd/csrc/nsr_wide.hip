@@ -48,8 +48,13 @@ __device__ unsigned g_wide_violation = 0u;
 // ------------------------------------------------------------------------------------------------------------------------
 // The encodings (ahead of the on-chip kernels, which compute them too: trunk_rows_encode of nsr_wide_trunk.inc)
 // ------------------------------------------------------------------------------------------------------------------------
-// gamma(x) (RH:18-48): sin / cos of the fp32 argument 2^l x (the scaling is exact) by sincos_enc: <= 1 ulp from the true value,
-// i.e. inside the reference's own libm error.  sin / cos of inf / NaN are NaN, as in torch.
+// gamma(x) (RH:18-48): sin / cos of the fp32 argument a = 2^l x (the scaling is exact) by sincos_enc.  For |a| < 2^24 the result is
+// within 2 ulp OF THE TRUE VALUE plus |a| 2^-52: the one-product reduction leaves an absolute |a| 2^-52 radians (2 / pi and the
+// product round at 2^-53 each), which is far below an ulp of 1 (3.7e-9 at 2^24) but many ulp of a result near a zero of sin or cos
+// -- 4464 ulp of the -3.4e-8 that is cos(267058.94), 1.6e-11 absolute.  (The reference's libm stays within 0.61 ulp of the result
+// over the whole argument set of the tests.)  Beyond 2^24: the fp64 library value rounded once, < 1 ulp.  sin / cos of inf / NaN are
+// NaN, as in torch.  Held element by element by tests/test_gpu_wide_encodings.py (measured: 0.79 of that bound at worst;
+// profiles/r20/extra/encodings.txt).
 struct EmbedArgs {
   const float* rays_o; const float* rays_d;   // rays form: point (r, s) = o + d z[r][s]  (RN:463, RN:478)
   const float* z; const float* vd;            // [R,S], [R,3]
@@ -63,10 +68,11 @@ struct EmbedArgs {
 
 // sin and cos of the fp32 argument a for the encodings.  |a| < 2^24 (every scene: 2^14 |x| < 2^24 means |x| < 1024): ONE fp64
 // range reduction -- t = a * 2 / pi has >= 24 spare bits, the split into quadrant and fraction is exact -- and the Cephes
-// single-precision minimax polynomials on [-pi / 4, pi / 4] (1 ulp), as the fused kernels' enc_trig (nsr_kernels.hip); ~30 VALU
-// for the pair where the fp64 library sincos costs several hundred (r06: kw_embed was 2-9 % of a layered render).  Beyond that,
-// and for inf / NaN: the fp64 library routine, rounded once, as before.  (In three pieces, so that a caller with many columns a lane
-// -- trunk_rows_encode -- can keep the library routine out of its unrolled path: sincos_enc itself is what it was.)
+// single-precision minimax polynomials on [-pi / 4, pi / 4] (1 ulp of their own value; the result's bound is above), as the fused
+// kernels' enc_trig (nsr_kernels.hip); ~30 VALU for the pair where the fp64 library sincos costs several hundred (r06: kw_embed was
+// 2-9 % of a layered render).  Beyond that, and for inf / NaN: the fp64 library routine, rounded once, as before.  (In three pieces,
+// so that a caller with many columns a lane -- trunk_rows_encode -- can keep the library routine out of its unrolled path:
+// sincos_enc itself is what it was.)
 __device__ __forceinline__ bool sincos_enc_is_fast(float a) { return fabsf(a) < 16777216.0f; }
 __device__ __forceinline__ void sincos_enc_slow(float a, float& s, float& c) {
   double sd, cd;
